@@ -2,17 +2,20 @@
 """Headline benchmark: train images/sec of darkcapsule (GTSDB-shaped 416x416, n_grid 13, 3 routing
 iterations, batch 32 per GPU, fp32, recon off) on N MI355X GPUs of one node.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 One step = forward + darkcapsule_loss + backward + (N>1: one RCCL all-reduce of the flat gradient bucket)
 + fused Adam.  `value` is measured with the batch resident in HBM before the timed region (the bench contract); the
 same step fed from host memory through the device-side input pipeline is `pcie_inclusive`.  Rank 0 prints ONE JSON
-line.  Extra objects on that line:
+line.  A plain run sets up, runs W warm-up and K timed steps and prints the headline (`value`, `ms_per_step`, `config`);
+--dump-outputs DIR also writes what the last timed step computed (dump_outputs).  --full adds `pcie_inclusive`, `kernel_ms`,
+`secondary` (the other BASELINE configurations) and the objects below, all measured after the timed steps (--no-extras leaves
+out roofline_routing_c43, loss_curve_parity and secondary; --no-cpu-baseline leaves out cpu_baseline):
   roofline      dominant kernel (conv_2's fused Winograd kernel, fp32 MFMA): the MFMA FLOPs the kernel ISSUES per launch
                 (direct-convolution FLOPs / 2.25; / 4 for the F(4x4,3x3) forward / input gradient) divided by the launch's mean duration (HIP events on the launch stream
-                inside the timed steps) and by the fp32 MFMA peak; `effective_vs_direct` prices the same time against the
+                in K more steps of their own) and by the fp32 MFMA peak; `effective_vs_direct` prices the same time against the
                 direct-convolution FLOPs (can exceed 1); `traffic` = HBM bytes from the newest PMC passes in profiles/
   roofline_routing       the C = 1 routing kernel of this model (HBM-bound): algorithmic bytes / duration
   roofline_routing_c43   the general routing kernels on the C = 43 heads (CapsuleNet, DarkCapsuleNet3), timed in this run
@@ -84,14 +87,22 @@ def parse():
     ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                     help="bf16: the backbone behind the first layer on bf16 MFMA kernels (BASELINE configs[4] with --input 608 --n_iter 5)")
     ap.add_argument('--sync-bn', action='store_true', help='N>1: BatchNorm statistics over the global batch (2 small all-reduces per BN layer)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without cpu_baseline')
     ap.add_argument('--cpu-batch', type=int, default=0, help='batch of the CPU baseline step (0 = --batch: the identical step)')
     ap.add_argument('--cpu-steps', type=int, default=3, help='timed CPU-baseline steps after the warm-up step (SURVEY 8d: >= 3)')
-    ap.add_argument('--no-extras', action='store_true', help='skip loss_curve_parity, roofline_routing_c43 and secondary')
+    ap.add_argument('--no-extras', action='store_true', help='--full without loss_curve_parity, roofline_routing_c43 and secondary')
     ap.add_argument('--backend', default=os.environ.get('CAPSYOLO_DP_BACKEND', 'nccl'), choices=['nccl', 'gloo'],
                     help="torch.distributed backend for N>1: 'nccl' (= RCCL over xGMI, one GPU per rank; the default) or 'gloo' "
                          "(rehearsal: the ranks may share one GPU, collectives go through host memory)")
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: per-kernel figures and rooflines (a HIP-event-bracketed run of their own), '
+                         'pcie_inclusive, and the extras that --no-extras / --no-cpu-baseline leave out')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; rank 0)')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def host_cores():
@@ -432,6 +443,29 @@ def secondary(dev, steps=5):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, net, out, loss):
+    """What the timed path hands its caller after its last step, as float32 DIR/<name>.npy: `output` (the network's output),
+    `loss`, `param.<name>` (every parameter after the Adam update), `grad.<name>` (the gradients that update consumed) and
+    `buffer.<name>` (BatchNorm running statistics).  About 10 MB at the headline configuration: nothing is sampled."""
+    import numpy as np
+    arrays = [('output', out), ('loss', loss.reshape(1))]
+    for name, q in net.named_parameters():
+        arrays.append(('param.' + name, q))
+        if q.grad is not None:
+            arrays.append(('grad.' + name, q.grad))
+    arrays += [('buffer.' + name, b) for name, b in net.named_buffers() if b.is_floating_point()]
+    arrays = [(name, t.detach().float().cpu().numpy()) for name, t in arrays]
+    total = sum(a.nbytes for _, a in arrays)
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays:
+        np.save(os.path.join(d, name + '.npy'), a)
+
+
 def main():
     args = parse()
     import torch
@@ -470,58 +504,67 @@ def main():
         loss.backward()
         bucket.allreduce_mean()
         opt.step()
-        return loss
+        return out, loss
 
     for _ in range(args.warmup):
-        loss = step()
-    ops.timer.reset()
-    ops.timer.enabled = True
+        out, loss = step()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        out, loss = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    ops.timer.enabled = False
     final_loss = float(loss.item())
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    kt = ops.timer.summary()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, out, loss)
+    del out, loss
 
-    # PCIe-inclusive rate (never `value`): the same step fed from host memory through the device-side input pipeline
-    # (uint8 over PCIe, three pinned buffers, converted on the GPU) -- what main.py's loop does per batch
-    from capsyolo_amd.input_pipeline import DeviceFeeder, quantize_if_exact
-    n_h2d = min(args.steps, 10)
-    x_host = quantize_if_exact(synth.images(B, args.input, first=lo))      # once per data set, as main.py does
-    y_host = synth.gtsdb_labels(B, g, 43, first=lo)
-    feeder = DeviceFeeder([(x_host, y_host)] * (n_h2d + 1), dev)
-    it = iter(feeder)
-    xb, yb = next(it)
+    if args.full:
+        # per-launch HIP-event brackets around the same step, in a run of their own: the brackets are not in `value`
+        ops.timer.reset()
+        ops.timer.enabled = True
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        ops.timer.enabled = False
+        kt = ops.timer.summary()
 
-    def step_on(xb, yb):
-        out = net(xb)
-        l = loss_fns.darkcapsule_loss(out, yb, p)
-        opt.zero_grad()
-        l.backward()
-        bucket.allreduce_mean()
-        opt.step()
-    step_on(xb, yb)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for xb, yb in it:
+        # PCIe-inclusive rate (never `value`): the same step fed from host memory through the device-side input pipeline
+        # (uint8 over PCIe, three pinned buffers, converted on the GPU) -- what main.py's loop does per batch
+        from capsyolo_amd.input_pipeline import DeviceFeeder, quantize_if_exact
+        n_h2d = min(args.steps, 10)
+        x_host = quantize_if_exact(synth.images(B, args.input, first=lo))      # once per data set, as main.py does
+        y_host = synth.gtsdb_labels(B, g, 43, first=lo)
+        feeder = DeviceFeeder([(x_host, y_host)] * (n_h2d + 1), dev)
+        it = iter(feeder)
+        xb, yb = next(it)
+
+        def step_on(xb, yb):
+            out = net(xb)
+            l = loss_fns.darkcapsule_loss(out, yb, p)
+            opt.zero_grad()
+            l.backward()
+            bucket.allreduce_mean()
+            opt.step()
         step_on(xb, yb)
-    torch.cuda.synchronize()
-    h2d_elapsed = time.perf_counter() - t1
-    if world > 1:
-        t = torch.tensor([h2d_elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        h2d_elapsed = float(t.item())
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for xb, yb in it:
+            step_on(xb, yb)
+        torch.cuda.synchronize()
+        h2d_elapsed = time.perf_counter() - t1
+        if world > 1:
+            t = torch.tensor([h2d_elapsed], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            h2d_elapsed = float(t.item())
 
     # Every collective of this run is behind us: all ranks leave the process group TOGETHER, here, and what follows
     # (rank 0's roofline extras, the parity curve, the CPU baseline -- seconds of work) runs on a process that no other
@@ -533,6 +576,24 @@ def main():
         ops.SYNC_BN = False
 
     if rank == 0:
+        line = {
+            'metric': 'train images/sec darkcapsule GTSDB 416x416 @1/2/4/8 GPU; loss-curve parity',
+            'value': round(world * B * args.steps / elapsed, 3), 'unit': 'images/s', 'n_gpus': world,
+            'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(1e3 * elapsed / args.steps, 3),
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32' if args.precision == 'fp32' else 'bf16', 'data': 'synthetic',
+            'value_definition': 'whole-job images/s with each rank\'s batch resident in HBM before the timed region (bench contract); '
+                                'pcie_inclusive (--full) = the same step with the batch fed from host memory every step',
+            'config': {'workload': 'experiments/darkcapsule GTSDB-shaped %dx%d, n_grid %d, %d routing iters, batch %d per GPU, '
+                                   'recon off, %s (%s)' % (args.input, args.input, g, args.n_iter, B,
+                                                           'fp32' if args.precision == 'fp32' else 'bf16 MFMA path (bf16 activations, fp32 accumulation / statistics / master weights; first block and routing head fp32)',
+                                                           'BASELINE configs[2]' if (args.input, args.n_iter, B, args.precision) == (416, 3, 32, 'fp32')
+                                                           else 'BASELINE configs[4], one GPU\'s share' if (args.input, args.n_iter, B, args.precision) == (608, 5, 32, 'bf16')
+                                                           else 'not a BASELINE configuration'),
+                       'global_batch': world * B, 'parallelism': 'dp%d%s' % (world, '+syncbn' if (args.sync_bn and world > 1) else ''), 'final_loss': round(final_loss, 6)},
+        }
+        if not args.full:
+            print(json.dumps(line), flush=True)
+            return
         M = B * args.input * args.input
         conv2_flops = 2.0 * M * 256 * (9 * 128)          # algorithmic: 2*Cin*k^2*Cout*Ho*Wo per image
         # conv_2's three kernels (77.5 % of the model's FLOPs); the dominant one by time carries `roofline`
@@ -580,20 +641,7 @@ def main():
         rt_bytes = 4.0 * (R * 512 * 8 + 512 * 1 * 8 * 5 + R * 1 * 5)
         nr, msr = kt.get('routing_fwd', (0, float('nan')))
         rt_gbps = rt_bytes / (msr * 1e-3) / 1e9
-        line = {
-            'metric': 'train images/sec darkcapsule GTSDB 416x416 @1/2/4/8 GPU; loss-curve parity',
-            'value': round(world * B * args.steps / elapsed, 3), 'unit': 'images/s', 'n_gpus': world,
-            'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(1e3 * elapsed / args.steps, 3),
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32' if args.precision == 'fp32' else 'bf16', 'data': 'synthetic',
-            'value_definition': 'whole-job images/s with each rank\'s batch resident in HBM before the timed region (bench contract); '
-                                'pcie_inclusive = the same step with the batch fed from host memory every step',
-            'config': {'workload': 'experiments/darkcapsule GTSDB-shaped %dx%d, n_grid %d, %d routing iters, batch %d per GPU, '
-                                   'recon off, %s (%s)' % (args.input, args.input, g, args.n_iter, B,
-                                                           'fp32' if args.precision == 'fp32' else 'bf16 MFMA path (bf16 activations, fp32 accumulation / statistics / master weights; first block and routing head fp32)',
-                                                           'BASELINE configs[2]' if (args.input, args.n_iter, B, args.precision) == (416, 3, 32, 'fp32')
-                                                           else 'BASELINE configs[4], one GPU\'s share' if (args.input, args.n_iter, B, args.precision) == (608, 5, 32, 'bf16')
-                                                           else 'not a BASELINE configuration'),
-                       'global_batch': world * B, 'parallelism': 'dp%d%s' % (world, '+syncbn' if (args.sync_bn and world > 1) else ''), 'final_loss': round(final_loss, 6)},
+        line.update({
             'roofline': cands[0] if cands else None,
             'roofline_other_conv2': cands[1:],
             'roofline_routing': {'kernel': 'caps1_fwd_kernel<5,true> (fused routing, C=1, cell gather folded into the load; '
@@ -614,7 +662,7 @@ def main():
                                'note': 'batch fed from host memory every step: uint8 over PCIe, three pinned buffers, '
                                        'centring + NHWC->NCHW on the device (capsyolo_amd/input_pipeline.py)'},
             'kernel_ms': dict((k, round(v[1], 4)) for k, v in sorted(kt.items())),
-        }
+        })
         def extra(name, fn):        # an extra that fails is reported as such: it must never cost the line its headline
             try:
                 line[name] = fn()

@@ -51,9 +51,10 @@ def test_gradient_allreduce_world2_gloo(tmp_path):
 
 def _main_worker(rank, world, port, tmpdir):
     """main.py's own loop on 2 ranks (the plain-torch `cnn` baseline runs without a GPU): the epoch losses every rank
-    hands to ReduceLROnPlateau are the SAME numbers, the replicas stay identical, rank 0 writes the artefacts."""
+    hands to ReduceLROnPlateau are the SAME numbers, the replicas stay identical, rank 0 writes the artefacts.
+    CAPSYOLO_DP_BACKEND=gloo: main.py picks RCCL wherever a GPU is visible, and a one-GPU box has no GPU for rank 1."""
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR='127.0.0.1',
-                      MASTER_PORT=str(port))
+                      MASTER_PORT=str(port), CAPSYOLO_DP_BACKEND='gloo')
     import importlib.util
     import json
     spec = importlib.util.spec_from_file_location('cy_main', os.path.join(REPO, 'main.py'))

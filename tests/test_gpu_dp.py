@@ -134,7 +134,7 @@ def test_bench_two_ranks_over_gloo_on_one_gpu(tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--gpus', '2', '--batch', '2', '--input', '64',
-           '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--backend', 'gloo']
+           '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--backend', 'gloo']
     r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -161,7 +161,7 @@ def test_bench_two_ranks_sync_bn_over_gloo(tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(REPO, 'bench.py'), '--gpus', '2', '--batch', '2', '--input', '64',
-           '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-extras', '--sync-bn', '--backend', 'gloo']
+           '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-extras', '--sync-bn', '--backend', 'gloo']
     r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])

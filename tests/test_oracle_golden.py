@@ -130,7 +130,9 @@ def test_iou_and_cwh_known_answers():
 
 
 # ----------------------------------------------------------------------------- whole models
-def _check_model(tag, net, forward, steps=0, lr=1e-3, grad_tol=2e-3):
+def _check_model(tag, net, forward, steps=0, lr=1e-3, grad_tol=2e-3, bn_fed_biases=(), forward64=None):
+    """bn_fed_biases: conv biases that feed a BatchNorm besides the `.conv_*` ones.  forward64: the forward pass in float64, for a
+    curve that is held to the reference's float64 run (tests/golden/models_curve64.npz)."""
     g = load_golden('models')
     net.load_state_dict(closed_form_state(net))
     net.train()
@@ -147,12 +149,20 @@ def _check_model(tag, net, forward, steps=0, lr=1e-3, grad_tol=2e-3):
         if p.grad is None:
             assert key not in g.files
             continue
-        # conv biases that feed a BatchNorm have analytically-zero, noise-only gradients
-        if '.conv_' in name and name.endswith('bias'):
+        # conv biases that feed a BatchNorm have analytically-zero, noise-only gradients: the reference's digits
+        # are the rounding noise of its CPU's summation order, so they are held to be noise against the layer's weight gradient
+        if name in bn_fed_biases or ('.conv_' in name and name.endswith('bias')):
+            w = dict(net.named_parameters())[name[:-len('bias')] + 'weight']
+            assert float(p.grad.abs().max()) <= 1e-4 * float(w.grad.abs().max()), name
             continue
         ref = g[key]
         scale = max(1e-6, float(np.abs(ref[2:]).max()))
-        close(grad_digest(p.grad), ref, grad_tol, grad_tol * scale)
+        got = grad_digest(p.grad)
+        # digest[0] is the gradient's sum, mixed signs that cancel (darknet_d conv_2: |sum| = 1e-3 of the abs-sum): its fp32
+        # digits follow the summation order of the CPU, not the oracle, so it is held to what the element tolerance implies
+        # for a sum, grad_tol x the abs-sum (the rule of tests/test_gpu_models.py: _digest_close); abs-sum and samples as before
+        assert abs(got[0] - ref[0]) <= grad_tol * ref[1], '%s: sum %g vs %g' % (name, got[0], ref[0])
+        close(got[1:], ref[1:], grad_tol, grad_tol * scale)
         n_checked += 1
     assert n_checked > 0
     for name, b in net.named_buffers():
@@ -168,7 +178,23 @@ def _check_model(tag, net, forward, steps=0, lr=1e-3, grad_tol=2e-3):
             loss.backward()
             opt.step()
             curve.append(loss.item())
-        close(curve, g[tag + '_curve'], 2e-3, 1e-5)
+        if forward64 is None:
+            close(curve, g[tag + '_curve'], 2e-3, 1e-5)
+            return
+        # DarkNet at lr 1e-3 is chaotic in fp32 from step 1 on (a one-ulp twin of the reference's input moves its loss by 20 .. 37 %
+        # there): the fp32 curve pins step 0, and the whole curve is held in float64 to the reference's float64 run
+        close(curve[0], g[tag + '_curve'][0], 2e-3, 1e-5)
+        net.float().load_state_dict(closed_form_state(net))
+        net.double()
+        opt = torch.optim.Adam([p for p in net.parameters() if p.requires_grad], lr=lr)
+        curve64 = []
+        for _ in range(steps):
+            out, loss = forward64(net)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            curve64.append(loss.item())
+        close(curve64, load_golden('models_curve64')[tag + '_curve64'], 1e-4, 0)
 
 
 def test_capsule_net_golden():
@@ -224,7 +250,11 @@ def test_darknet_golden(tag, nb, C):
     def fwd(net):
         out = net(x)
         return out, OL.dark_loss(out, y, p)[0]
-    _check_model(tag, OM.DarkNet(p), fwd, steps=6, grad_tol=5e-3)
+
+    def fwd64(net):
+        out = net(x.double())
+        return out, OL.dark_loss(out, y, p)[0]
+    _check_model(tag, OM.DarkNet(p), fwd, steps=6, grad_tol=5e-3, forward64=fwd64)
 
 
 def test_convnet_golden():
@@ -235,7 +265,7 @@ def test_convnet_golden():
     def fwd(net):
         out = net(x)
         return out, OL.cnn_loss(out, y)
-    _check_model('cnn', OM.ConvNet(p), fwd)
+    _check_model('cnn', OM.ConvNet(p), fwd, bn_fed_biases=('cnn.0.bias', 'cnn.4.bias'))
 
 
 def test_state_dict_keys_match_reference_names():

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs ON the GPU box (through tools/gpu.sh): the judged evidence for one tree, written under gpurun_out/<tag>/.
-#   bench_n1.json                  python bench.py (defaults)
-#   bench_under_rocprof.json       the same step loop (--no-extras --no-cpu-baseline: full-size launches only) under rocprofv3 --kernel-trace --stats
+#   bench_n1.json                  python bench.py --full
+#   bench_under_rocprof.json       the same step loop (a plain run: warm-up + timed steps, full-size launches only) under rocprofv3 --kernel-trace --stats
 #   bench_kernel_stats.csv         its per-kernel summary (tools/summarize_rocpd.py)
 #   pmc_traffic.json               HBM bytes per launch: FETCH_SIZE / WRITE_SIZE passes of tools/run_kernels.py (separate runs)
 #   pmc_sq_*.json                  SQ counters (MFMA busy, LDS conflicts, issue / wait shares) of the conv and routing kernels
@@ -10,11 +10,11 @@ set -o pipefail
 TAG=${1:-rXX}; STEPS=${2:-10}
 R=$PWD; O=$R/gpurun_out/$TAG; mkdir -p $O
 HEAD=$(cat .bench_head 2>/dev/null)
-python3 bench.py > $O/bench_n1.json 2> $O/bench_n1.err || { tail -5 $O/bench_n1.err; exit 1; }
+python3 bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || { tail -5 $O/bench_n1.err; exit 1; }
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python3 $R/bench.py --steps $STEPS --warmup 3 --no-extras --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err || { tail -5 $O/bench_under_rocprof.err; exit 1; }
+rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python3 $R/bench.py --steps $STEPS --warmup 3 > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err || { tail -5 $O/bench_under_rocprof.err; exit 1; }
 DB=$(ls $O/prof/*.db $O/prof/*/*.db 2>/dev/null | head -1)
-[ -n "$DB" ] && python3 $R/tools/summarize_rocpd.py $DB $((2 * STEPS + 4)) > $O/bench_kernel_stats.csv
+[ -n "$DB" ] && python3 $R/tools/summarize_rocpd.py $DB $((STEPS + 3)) > $O/bench_kernel_stats.csv
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_f -o p --output-format csv -- python3 $R/tools/run_kernels.py all 32 1 > $O/pmc_f.log 2>&1 &&
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_w -o p --output-format csv -- python3 $R/tools/run_kernels.py all 32 1 > $O/pmc_w.log 2>&1 &&
 python3 $R/tools/pmc_traffic.py $(ls $O/pmc_f/*counter_collection.csv $O/pmc_f/*/*counter_collection.csv 2>/dev/null | head -1) $(ls $O/pmc_w/*counter_collection.csv $O/pmc_w/*/*counter_collection.csv 2>/dev/null | head -1) "$HEAD" > $O/pmc_traffic.json
