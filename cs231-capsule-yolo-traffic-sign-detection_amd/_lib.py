@@ -94,6 +94,8 @@ _SIGS = {
     'cy_act_bwd': [_P, _P, _P, _F, _L, _P],
     'cy_routing_fwd': [C.POINTER(RoutingFwd), _P],
     'cy_routing_bwd': [C.POINTER(RoutingBwd), _P],
+    'cy_routing_general_fwd': [C.POINTER(RoutingFwd), _P],
+    'cy_routing_general_bwd': [C.POINTER(RoutingBwd), _P],
     'cy_squash_fwd': [_P, _P, _L, _I, _P],
     'cy_squash_bwd': [_P, _P, _P, _L, _I, _P],
     'cy_length_fwd': [_P, _P, _L, _I, _P],
@@ -163,6 +165,9 @@ _RET = {
     'cy_conv_gemm_ws_floats': (_L, [C.POINTER(ConvGemm)]),
     'cy_routing_bwd_ws_floats': (_L, [C.POINTER(RoutingBwd)]),
     'cy_routing_fwd_ws_floats': (_L, [C.POINTER(RoutingFwd)]),
+    'cy_routing_general_bwd_ws_floats': (_L, [C.POINTER(RoutingBwd)]),
+    'cy_routing_general_fwd_ws_floats': (_L, [C.POINTER(RoutingFwd)]),
+    'cy_routing_specialised': (_I, [C.POINTER(RoutingFwd)]),
 }
 EXPORTS = sorted(list(_SIGS) + list(_RET))
 ABI_VERSION = 5     # what the signatures above were written against (include/capsyolo_hip.h, csrc/error.cpp)

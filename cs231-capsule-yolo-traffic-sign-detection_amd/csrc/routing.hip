@@ -7,7 +7,8 @@
 // u_hat is recomputed every iteration from (u, W) instead of being stored (the reference keeps a
 // [R,N,C,1,Dout] tensor and makes ~20 passes over it).
 //
-// Two code paths:
+// Every other shape of the envelope Din 1..16, Dout 1..64, C 1..256 goes to routing_general.hip.
+// Two code paths here:
 //  * C == 1 (DarkCapsuleNet head, models.py:368-370): coupling == 1 exactly, the layer is
 //    v = squash(sum_i u_i W_i): a pure HBM stream over u (R rows of 4096 floats).  One block of 4
 //    waves walks rows; wave w owns quarter w of the row, whose 16 elements per lane meet W values
@@ -545,15 +546,17 @@ int launch_bwd(const cy_routing_bwd_t* a, hipStream_t s) {
   return cyi_caps_bwd_launch(a, cdb, s);
 }
 
+// what today's kernels take: the C == 1 stream, or Din = 8, Dout in {5, 16, 21, 48}, C <= 64
+bool specialised_shape(int N, int C, int Din, int Dout) {
+  return fast_c1(N, C, Din, Dout) || (Din == 8 && (Dout == 5 || Dout == 16 || Dout == 21 || Dout == 48) && C <= 64);
+}
+bool gather_ok(int R, int N, int Din, int g, int B) { return g == 0 || (N == 512 && Din == 8 && B > 0 && R == g * g * B); }
+
 int check_shape(const char* fn, int R, int N, int C, int Din, int Dout, int n_iter, int g, int B) {
   if (R <= 0 || N <= 0 || C <= 0 || n_iter <= 0) return cy_set_error(CY_EINVAL, "%s: non-positive dimension", fn);
-  if (g != 0 && (N != 512 || Din != 8 || B <= 0 || R != g * g * B))
+  if (!gather_ok(R, N, Din, g, B))
     return cy_set_error(CY_EINVAL, "%s: cell gather needs N=512, Din=8, R=g*g*B (got N=%d Din=%d R=%d g=%d B=%d)", fn, N,
                         Din, R, g, B);
-  if (fast_c1(N, C, Din, Dout)) return 0;
-  if (Din != 8 || !(Dout == 5 || Dout == 16 || Dout == 21 || Dout == 48) || C > 64)
-    return cy_set_error(CY_EINVAL, "%s: unsupported capsule shape C=%d Din=%d Dout=%d (built: Din=8, Dout in {5,16,21,48}, C<=64)",
-                        fn, C, Din, Dout);
   return 0;
 }
 
@@ -563,6 +566,7 @@ extern "C" int cy_routing_fwd(const cy_routing_fwd_t* a, void* stream) {
   CY_REQUIRE(a && a->u && a->W && a->v_out && a->s_hist, "cy_routing_fwd: null pointer");
   int rc = check_shape("cy_routing_fwd", a->R, a->N, a->C, a->Din, a->Dout, a->n_iter, a->gather_g, a->gather_B);
   if (rc) return rc;
+  if (!specialised_shape(a->N, a->C, a->Din, a->Dout)) return cy_routing_general_fwd(a, stream);
   hipStream_t s = (hipStream_t)stream;
   if (fast_c1(a->N, a->C, a->Din, a->Dout)) {
     int blocks = a->R < C1_BLOCKS ? a->R : C1_BLOCKS;
@@ -581,8 +585,18 @@ extern "C" int cy_routing_fwd(const cy_routing_fwd_t* a, void* stream) {
   return 0;
 }
 
+extern "C" int cy_routing_specialised(const cy_routing_fwd_t* a) {
+  return a && a->R > 0 && a->N > 0 && a->C > 0 && a->n_iter > 0 && gather_ok(a->R, a->N, a->Din, a->gather_g, a->gather_B) &&
+         specialised_shape(a->N, a->C, a->Din, a->Dout);
+}
+
+// other shapes: the general kernels' workspace (0 outside their envelope: cy_routing_fwd then reports the shape)
 extern "C" long long cy_routing_fwd_ws_floats(const cy_routing_fwd_t* a) {
   if (!a || fast_c1(a->N, a->C, a->Din, a->Dout)) return 0;
+  if (!specialised_shape(a->N, a->C, a->Din, a->Dout)) {
+    const long long n = cy_routing_general_fwd_ws_floats(a);
+    return n > 0 ? n : 0;
+  }
   cyi_rows_plan_t p;
   cyi_rows_plan(a->R, a->N, a->C, a->Dout, 0, &p);
   const long long plane = (long long)a->R * a->C * a->Dout;
@@ -592,6 +606,10 @@ extern "C" long long cy_routing_fwd_ws_floats(const cy_routing_fwd_t* a) {
 extern "C" long long cy_routing_bwd_ws_floats(const cy_routing_bwd_t* a) {
   if (!a) return 0;
   if (fast_c1(a->N, a->C, a->Din, a->Dout)) return (long long)C1_BLOCKS * 4096 * 5;
+  if (!specialised_shape(a->N, a->C, a->Din, a->Dout)) {
+    const long long n = cy_routing_general_bwd_ws_floats(a);
+    return n > 0 ? n : 0;
+  }
   cyi_rows_plan_t p;
   cyi_rows_plan(a->R, a->N, a->C, a->Dout, 1, &p);
   const long long cdb = (!p.phased && a->n_iter > 1 && a->Dout <= 21) ? 2ll * (a->n_iter - 1) * a->R * a->N * a->C : 0;
@@ -602,6 +620,7 @@ extern "C" int cy_routing_bwd(const cy_routing_bwd_t* a, void* stream) {
   CY_REQUIRE(a && a->u && a->W && a->s_hist && a->dv && a->du && a->dW && a->ws, "cy_routing_bwd: null pointer");
   int rc = check_shape("cy_routing_bwd", a->R, a->N, a->C, a->Din, a->Dout, a->n_iter, a->gather_g, a->gather_B);
   if (rc) return rc;
+  if (!specialised_shape(a->N, a->C, a->Din, a->Dout)) return cy_routing_general_bwd(a, stream);
   hipStream_t s = (hipStream_t)stream;
   if (fast_c1(a->N, a->C, a->Din, a->Dout)) {
     const int blocks = a->R < C1_BLOCKS ? a->R : C1_BLOCKS;

@@ -951,6 +951,25 @@ def conv_block(x, weight, bias, gamma, beta, cfg, in_scale=None, in_shift=None):
 
 
 # ------------------------------------------------------------------------------------------------ routing
+ROUTING_FORCE_GENERAL = False   # every routing shape on the general kernels (routing_general.hip), also those the specialised kernels
+#                                 take: A/B runs and cross-checks.  Read at each call, so a forward and its backward may take different paths.
+
+
+def _routing_entry(a):
+    """'cy_routing_fwd' where the specialised kernels take the shape, else the general kernels' entry point."""
+    if ROUTING_FORCE_GENERAL or not query('cy_routing_specialised', C.byref(a)):
+        return 'cy_routing_general_fwd'
+    return 'cy_routing_fwd'
+
+
+def _routing_ws(name, a):
+    n = query(name, C.byref(a))
+    if n < 0:          # outside the general kernels' envelope: the library's message says which
+        msg = _lib.load().capsyolo_last_error()
+        raise _lib.HipExtensionError('%s failed: %s' % (name, msg.decode() if msg else '?'))
+    return n
+
+
 class _Routing(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, W, n_iter, gather_g, gather_B):
@@ -966,12 +985,13 @@ class _Routing(torch.autograd.Function):
         s_hist = _empty((n_iter, R, Cc, Dout), u)
         a = RoutingFwd(u=u.data_ptr(), W=W.data_ptr(), v_out=v.data_ptr(), s_hist=s_hist.data_ptr(), R=R, N=N, C=Cc,
                        Din=Din, Dout=Dout, n_iter=n_iter, gather_g=gather_g, gather_B=gather_B, ws=None)
-        nws = query('cy_routing_fwd_ws_floats', C.byref(a))
+        fn = _routing_entry(a)
+        nws = _routing_ws(fn + '_ws_floats', a)
         if nws:
             ws = _empty((nws,), u)
             a.ws = ws.data_ptr()
         with timer.range('routing_fwd'):
-            call('cy_routing_fwd', C.byref(a), _stream())
+            call(fn, C.byref(a), _stream())
         ctx.save_for_backward(u, W, s_hist)
         ctx.dims = (R, N, Cc, Din, Dout, n_iter, gather_g, gather_B)
         return v
@@ -985,10 +1005,12 @@ class _Routing(torch.autograd.Function):
         a = RoutingBwd(u=u.data_ptr(), W=W.data_ptr(), s_hist=s_hist.data_ptr(), dv=dv.data_ptr(), du=du.data_ptr(),
                        dW=dW.data_ptr(), ws=None, R=R, N=N, C=Cc, Din=Din, Dout=Dout, n_iter=n_iter, gather_g=g,
                        gather_B=gB)
-        ws = _empty((query('cy_routing_bwd_ws_floats', C.byref(a)),), u)
+        fwd = RoutingFwd(R=R, N=N, C=Cc, Din=Din, Dout=Dout, n_iter=n_iter, gather_g=g, gather_B=gB)
+        fn = _routing_entry(fwd).replace('_fwd', '_bwd')
+        ws = _empty((_routing_ws(fn + '_ws_floats', a),), u)
         a.ws = ws.data_ptr()
         with timer.range('routing_bwd'):
-            call('cy_routing_bwd', C.byref(a), _stream())
+            call(fn, C.byref(a), _stream())
         return du, dW, None, None, None
 
 

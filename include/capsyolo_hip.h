@@ -369,6 +369,19 @@ typedef struct {
 long long cy_routing_bwd_ws_floats(const cy_routing_bwd_t* a);
 int cy_routing_bwd(const cy_routing_bwd_t* a, void* stream);
 
+/* Built shapes: the specialised kernels take C == 1 with N*Din == 4096, Dout == 5, and Din == 8, Dout in {5, 16, 21, 48},
+ * C <= 64.  Every other shape of the envelope Din 1..16, Dout 1..64, C 1..256 (any R, N, n_iter; with the cell gather
+ * N == 512, Din == 8) runs on the general kernels (csrc/routing_general.hip): cy_routing_fwd / cy_routing_bwd send them
+ * there, and the entry points below call them for any shape of the envelope (A/B runs, cross-checks).  They keep the
+ * contracts of the specialised ones: the same s_hist, so a forward on one path feeds a backward on the other; bitwise
+ * run-to-run determinism; no allocation or host synchronisation (workspace from the _ws_floats queries).  Outside the
+ * envelope they return CY_EINVAL and the _ws_floats queries -1. */
+int cy_routing_specialised(const cy_routing_fwd_t* a);    /* 1: cy_routing_fwd / _bwd take the shape on the specialised kernels */
+long long cy_routing_general_fwd_ws_floats(const cy_routing_fwd_t* a);
+int cy_routing_general_fwd(const cy_routing_fwd_t* a, void* stream);
+long long cy_routing_general_bwd_ws_floats(const cy_routing_bwd_t* a);
+int cy_routing_general_bwd(const cy_routing_bwd_t* a, void* stream);
+
 /* squash over the last dim (models.py:64-67), rows of D floats; and its backward */
 int cy_squash_fwd(const float* s, float* v, long long rows, int D, void* stream);
 int cy_squash_bwd(const float* s, const float* dv, float* ds, long long rows, int D, void* stream);
