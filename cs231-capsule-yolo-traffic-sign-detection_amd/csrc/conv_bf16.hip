@@ -533,21 +533,46 @@ __global__ void cast_kernel_b2f(const u16* __restrict__ in, float* __restrict__ 
   }
 }
 
-template <int BM, int BN, int WM, int WN, bool OUT_F32, bool BNF = false, bool TAPIN = false>
-int launch(Geo g, hipStream_t s) {
-  if constexpr (!TAPIN) {
-    // taps inside a channel chunk where a tile's lines would not survive in L2 between two taps (see step_done)
-    if ((g.Cin / BK) * BM > 768 && g.TH * g.TW > 1) return launch<BM, BN, WM, WN, OUT_F32, BNF, true>(g, s);
-  }
+// The plan of one launch: which compiled tile, which K order, how many tiles and persistent blocks.  Host arithmetic only: the
+// launcher dispatches on it and cy_conv_gemm_bf16_plan hands the same answer out without a GPU.
+struct Plan {
+  int BM, BN;                                       // block tile
+  int tapin;                                        // taps inside a channel chunk (TAPIN, see step_done)
+  int ntiles, nblk;                                 // (m tile, n tile, class) triples; persistent blocks launched
+};
+
+// the shape checks of cy_conv_gemm_bf16_classes (pointers are checked by the launcher) and the plan
+int make_plan(const cy_conv_gemm_t* a, int ncls, int out_f32, Plan* p) {
+  CY_REQUIRE(a && ncls >= 1 && ncls <= 4, "cy_conv_gemm_bf16_classes: 1 to 4 class descriptors");
+  CY_REQUIRE(a->Cin % 64 == 0 && a->N % 64 == 0, "cy_conv_gemm_bf16: Cin=%d and N=%d must be multiples of 64", a->Cin, a->N);
+  CY_REQUIRE(a->xs_c == 1 && a->xs_x == a->Cin && a->xs_y == (long long)a->Wi * a->Cin &&
+             a->xs_b == (long long)a->Hi * a->Wi * a->Cin, "cy_conv_gemm_bf16: X must be plain NHWC");
+  CY_REQUIRE(a->bn_red == nullptr || !out_f32, "cy_conv_gemm_bf16: the fused BatchNorm-backward sums are built for the bf16 output");
+  CY_REQUIRE(a->act >= 0 && a->act <= 2 && (a->act != 2 || (a->act_slope >= 0.f && a->act_slope <= 1.f)),
+             "cy_conv_gemm_bf16: act=%d / act_slope=%g (LeakyReLU slope must be in [0, 1])", a->act, (double)a->act_slope);
+  const long long M = (long long)a->B * a->Ho * a->Wo;
+  CY_REQUIRE(M < (1ll << 31) - 512, "cy_conv_gemm_bf16: more than 2^31 output pixels");
+  CY_REQUIRE(M * ncls * ((a->N + 63) / 64) < (1ll << 31), "cy_conv_gemm_bf16: too many tiles");
+  if (a->N % 256 == 0) { p->BM = 256; p->BN = 256; }
+  else if (a->N % 128 == 0) { p->BM = 512; p->BN = 128; }  // the same 128 x 64 wave tiles (256 x 128 had 16 MFMAs per wave and K step: 0.30)
+  else if (M >= 512 * 256) { p->BM = 512; p->BN = 64; }    // N = 64 (conv_3): 8 waves of 64 x 64 instead of 4 of 32 x 64
+  else { p->BM = 128; p->BN = 64; }
+  // taps inside a channel chunk where a tile's lines would not survive in L2 between two taps (see step_done)
+  p->tapin = (a->Cin / BK) * p->BM > 768 && a->TH * a->TW > 1;
+  p->ntiles = (int)(cy_ceil_div(M, p->BM) * cy_ceil_div(a->N, p->BN) * ncls);
+  const int resident = (p->BM == 128) ? 512 : 256;        // persistent blocks: what fits the chip at once (8-wave tiles: one per CU)
+  p->nblk = p->ntiles < resident ? p->ntiles : resident;
+  return 0;
+}
+
+template <int BM, int BN, int WM, int WN, bool OUT_F32, bool BNF, bool TAPIN>
+int launch(Geo g, const Plan& p, hipStream_t s) {
   const size_t lds = (size_t)2 * (BM + BN) * ROWB;
   int rc = cy_allow_lds(conv_bf16_kernel<BM, BN, WM, WN, OUT_F32, BNF, TAPIN>, lds);
   if (rc) return rc;
   g.ntm = (int)cy_ceil_div(g.M, BM);
   g.ntn = (int)cy_ceil_div(g.N, BN);
-
-  const long long ntiles = (long long)g.ntm * g.ntn * g.ncls;
-  const int resident = 256 * ((WM * WN == 8) ? 1 : 2);               // persistent blocks: what fits the chip at once
-  const unsigned nblk = (unsigned)(ntiles < resident ? ntiles : resident);
+  const unsigned nblk = (unsigned)p.nblk;
   g.prof = nullptr;
   static const bool prof_on = getenv("CY_BF16_PROF") != nullptr;      // developer instrumentation: synchronous, prints per launch
   if (prof_on) {
@@ -568,12 +593,17 @@ int launch(Geo g, hipStream_t s) {
   }
   return 0;
 }
+template <int BM, int BN, int WM, int WN, bool OUT_F32, bool BNF>
+int launch_k(const Geo& g, const Plan& p, hipStream_t s) {
+  return p.tapin ? launch<BM, BN, WM, WN, OUT_F32, BNF, true>(g, p, s) : launch<BM, BN, WM, WN, OUT_F32, BNF, false>(g, p, s);
+}
+// 4 tiles x TAPIN 0 / 1 per output variant (bf16, bf16 + BNF, fp32): the 24 kernels
 template <bool OUT_F32, bool BNF = false>
-int launch_n(const Geo& g, hipStream_t s) {
-  if (g.N % 256 == 0) return launch<256, 256, 2, 4, OUT_F32, BNF>(g, s);
-  if (g.N % 128 == 0) return launch<512, 128, 4, 2, OUT_F32, BNF>(g, s);   // the same 128 x 64 wave tiles (256 x 128 had 16 MFMAs per wave and K step: 0.30)
-  if (g.M >= 512 * 256) return launch<512, 64, 8, 1, OUT_F32, BNF>(g, s);     // N = 64 (conv_3): 8 waves of 64 x 64 instead of 4 of 32 x 64
-  return launch<128, 64, 4, 1, OUT_F32, BNF>(g, s);
+int launch_plan(const Geo& g, const Plan& p, hipStream_t s) {
+  if (p.BN == 256) return launch_k<256, 256, 2, 4, OUT_F32, BNF>(g, p, s);
+  if (p.BN == 128) return launch_k<512, 128, 4, 2, OUT_F32, BNF>(g, p, s);
+  if (p.BM == 512) return launch_k<512, 64, 8, 1, OUT_F32, BNF>(g, p, s);
+  return launch_k<128, 64, 4, 1, OUT_F32, BNF>(g, p, s);
 }
 
 }  // namespace
@@ -594,12 +624,20 @@ extern "C" int cy_conv_bf16_pack_weights(const float* W, void* Wp, int Cout, int
 }
 
 // ncls descriptors that differ only in Wp, dy0, dx0, out_oy, out_ox: the output-parity classes of a strided input gradient in ONE launch
+extern "C" int cy_conv_gemm_bf16_plan(const cy_conv_gemm_t* a, int ncls, int out_f32, int* plan5) {
+  CY_REQUIRE(plan5, "cy_conv_gemm_bf16_plan: null plan5");
+  Plan p;
+  const int rc = make_plan(a, ncls, out_f32, &p);
+  if (rc) return rc;
+  plan5[0] = p.BM; plan5[1] = p.BN; plan5[2] = p.tapin; plan5[3] = p.ntiles; plan5[4] = p.nblk;
+  return 0;
+}
+
 extern "C" int cy_conv_gemm_bf16_classes(const cy_conv_gemm_t* a, int ncls, int out_f32, void* stream) {
-  CY_REQUIRE(a && ncls >= 1 && ncls <= 4, "cy_conv_gemm_bf16_classes: 1 to 4 class descriptors");
+  Plan p;
+  const int prc = make_plan(a, ncls, out_f32, &p);
+  if (prc) return prc;
   CY_REQUIRE(a->X && a->Wp && a->Y, "cy_conv_gemm_bf16: null pointer");
-  CY_REQUIRE(a->Cin % 64 == 0 && a->N % 64 == 0, "cy_conv_gemm_bf16: Cin=%d and N=%d must be multiples of 64", a->Cin, a->N);
-  CY_REQUIRE(a->xs_c == 1 && a->xs_x == a->Cin && a->xs_y == (long long)a->Wi * a->Cin &&
-             a->xs_b == (long long)a->Hi * a->Wi * a->Cin, "cy_conv_gemm_bf16: X must be plain NHWC");
   CY_REQUIRE(a->bn_red == nullptr || (!out_f32 && a->bn_z && a->bn_scale && a->bn_shift && a->bn_mean && a->bn_invstd && (((uintptr_t)a->bn_z) & 15) == 0),
              "cy_conv_gemm_bf16: the fused BatchNorm-backward sums need the bf16 output, bn_z (bf16, 16-byte aligned) and scale / shift / mean / invstd");
   CY_REQUIRE((((uintptr_t)a->X | (uintptr_t)a->Wp | (uintptr_t)a->Y) & 15) == 0, "cy_conv_gemm_bf16: pointers must be 16-byte aligned");
@@ -608,8 +646,6 @@ extern "C" int cy_conv_gemm_bf16_classes(const cy_conv_gemm_t* a, int ncls, int 
   g.B = a->B; g.Hi = a->Hi; g.Wi = a->Wi; g.Cin = a->Cin; g.Ho = a->Ho; g.Wo = a->Wo; g.N = a->N; g.TH = a->TH; g.TW = a->TW;
   g.in_stride = a->in_stride; g.dy0 = a->dy0; g.dx0 = a->dx0; g.dstep = a->dstep; g.Hy = a->Hy; g.Wy = a->Wy;
   g.out_stride = a->out_stride; g.out_oy = a->out_oy; g.out_ox = a->out_ox; g.act = a->act; g.act_slope = a->act_slope;
-  CY_REQUIRE(a->act >= 0 && a->act <= 2 && (a->act != 2 || (a->act_slope >= 0.f && a->act_slope <= 1.f)),
-             "cy_conv_gemm_bf16: act=%d / act_slope=%g (LeakyReLU slope must be in [0, 1])", a->act, (double)a->act_slope);
   g.ncls = ncls;
   for (int c = 0; c < 4; ++c) {
     const cy_conv_gemm_t* q = a + (c < ncls ? c : 0);
@@ -624,15 +660,13 @@ extern "C" int cy_conv_gemm_bf16_classes(const cy_conv_gemm_t* a, int ncls, int 
     }
     g.c_dy0[c] = q->dy0; g.c_dx0[c] = q->dx0; g.c_oy[c] = q->out_oy; g.c_ox[c] = q->out_ox; g.c_wp[c] = (const u16*)q->Wp;
   }
-  g.M = (long long)a->B * a->Ho * a->Wo;
-  CY_REQUIRE(g.M < (1ll << 31) - 512, "cy_conv_gemm_bf16: more than 2^31 output pixels");
-  CY_REQUIRE(g.M * ncls * ((a->N + 63) / 64) < (1ll << 31), "cy_conv_gemm_bf16: too many tiles");
+  g.M = (long long)a->B * a->Ho * a->Wo;          // (below 2^31 - 512, and ntiles below 2^31: make_plan)
   g.K = a->TH * a->TW * a->Cin;
   hipStream_t s = (hipStream_t)stream;
   int rc;
   g.bn_z = (const u16*)a->bn_z; g.bn_scale = a->bn_scale; g.bn_shift = a->bn_shift; g.bn_mean = a->bn_mean; g.bn_invstd = a->bn_invstd;
   g.bn_red = a->bn_red; g.bn_slope = a->bn_slope;
-  rc = out_f32 ? launch_n<true>(g, s) : (a->bn_red != nullptr ? launch_n<false, true>(g, s) : launch_n<false>(g, s));
+  rc = out_f32 ? launch_plan<true>(g, p, s) : (a->bn_red != nullptr ? launch_plan<false, true>(g, p, s) : launch_plan<false>(g, p, s));
   if (rc) return rc;
   CY_LAUNCH_CHECK("cy_conv_gemm_bf16");
   return 0;

@@ -752,11 +752,9 @@ def conv_forward_bf16(x, weight, bias, k, stride, pad, stats=None, tag='conv', l
     wp = torch.empty((query('cy_conv_bf16_packed_elems', k * k * Cin, Cout),), dtype=torch.bfloat16, device=x.device)
     call('cy_conv_bf16_pack_weights', _ptr(weight), _ptr(wp), Cout, Cin, k, k, k, k, 0, 0, 1, 0, st)
     z = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
-    a = ConvGemm(X=x.data_ptr(), Wp=wp.data_ptr(), Y=z.data_ptr(), bias=bias.data_ptr() if bias is not None else None,
-                 stats=stats.data_ptr() if stats is not None else None,
-                 xs_b=Hi * Wi * Cin, xs_y=Wi * Cin, xs_x=Cin, xs_c=1, B=B, Hi=Hi, Wi=Wi, Cin=Cin, Ho=Ho, Wo=Wo, N=Cout,
-                 TH=k, TW=k, in_stride=stride, dy0=-pad, dx0=-pad, dstep=1, Hy=Ho, Wy=Wo, out_stride=1, out_oy=0, out_ox=0,
-                 act=0 if lrelu is None else 2, act_slope=1.0 if lrelu is None else float(lrelu))
+    a = _fwd_desc_bf16(x.shape, Cout, k, stride, pad, lrelu)
+    a.X, a.Wp, a.Y = x.data_ptr(), wp.data_ptr(), z.data_ptr()
+    a.bias, a.stats = bias.data_ptr() if bias is not None else None, stats.data_ptr() if stats is not None else None
     with timer.range('conv_bf16_fwd/' + tag):
         call('cy_conv_gemm_bf16', C.byref(a), 1 if out_f32 else 0, st)
     return z
@@ -778,26 +776,19 @@ def conv_dgrad_bf16(dz, weight, in_shape, k, stride, pad, out_f32=False, tag='co
     _, Ho, Wo, Cout = dz.shape
     st = _stream()
     dx = torch.empty((B, Hi, Wi, Cin), dtype=torch.float32 if out_f32 else torch.bfloat16, device=dz.device)
-    classes = dgrad_classes(Hi, Wi, k, stride, pad)
+    classes, descs, one_launch = _dgrad_descs_bf16(in_shape, dz.shape, k, stride, pad)
     nel = query('cy_conv_bf16_packed_elems', ((k + stride - 1) // stride) ** 2 * Cout, Cin)
     wp = torch.empty((len(classes), nel), dtype=torch.bfloat16, device=dz.device)
-    descs = (ConvGemm * len(classes))()
     for i, c in enumerate(classes):
         call('cy_conv_bf16_pack_weights', _ptr(weight), _ptr(wp[i]), Cout, Cin, k, k, c['TH'], c['TW'], c['kh0'], c['kw0'],
              c['kstep'], 1, st)
-        a = ConvGemm(X=dz.data_ptr(), Wp=wp[i].data_ptr(), Y=dx.data_ptr(), bias=None, stats=None,
-                     xs_b=Ho * Wo * Cout, xs_y=Wo * Cout, xs_x=Cout, xs_c=1, B=B, Hi=Ho, Wi=Wo, Cin=Cout,
-                     Ho=c['Ho'], Wo=c['Wo'], N=Cin, TH=c['TH'], TW=c['TW'], in_stride=1, dy0=c['dy0'], dx0=c['dx0'],
-                     dstep=c['dstep'], Hy=Hi, Wy=Wi, out_stride=c['out_stride'], out_oy=c['out_oy'], out_ox=c['out_ox'], act=0)
+        a = descs[i]
+        a.X, a.Wp, a.Y = dz.data_ptr(), wp[i].data_ptr(), dx.data_ptr()
         if bn_fuse is not None:
             bz, bsc, bsh, bmu, bis, bsl, bred = bn_fuse
             a.bn_z, a.bn_scale, a.bn_shift = _bf(bz, 'producer z').data_ptr(), bsc.data_ptr(), bsh.data_ptr()
             a.bn_mean, a.bn_invstd, a.bn_red, a.bn_slope = bmu.data_ptr(), bis.data_ptr(), bred.data_ptr(), float(bsl)
-        descs[i] = a
-    same = all((c['TH'], c['TW'], c['Ho'], c['Wo'], c['dstep'], c['out_stride']) ==
-               (classes[0]['TH'], classes[0]['TW'], classes[0]['Ho'], classes[0]['Wo'], classes[0]['dstep'], classes[0]['out_stride'])
-               for c in classes)
-    if BF16_DGRAD_ONE_LAUNCH and 1 < len(classes) <= 4 and same:
+    if one_launch:
         # the parity classes of a strided layer in ONE launch (even sizes: all classes have the same grid and taps)
         with timer.range('conv_bf16_dgrad/' + tag):
             call('cy_conv_gemm_bf16_classes', descs, len(classes), 1 if out_f32 else 0, st)
@@ -806,6 +797,57 @@ def conv_dgrad_bf16(dz, weight, in_shape, k, stride, pad, out_f32=False, tag='co
             with timer.range('conv_bf16_dgrad/' + tag):
                 call('cy_conv_gemm_bf16', C.byref(descs[i]), 1 if out_f32 else 0, st)
     return dx
+
+
+def _fwd_desc_bf16(x_shape, Cout, k, stride, pad, lrelu=None):
+    """The forward's cy_conv_gemm_t without its pointers."""
+    B, Hi, Wi, Cin = x_shape
+    Ho, Wo = (Hi + 2 * pad - k) // stride + 1, (Wi + 2 * pad - k) // stride + 1
+    return ConvGemm(xs_b=Hi * Wi * Cin, xs_y=Wi * Cin, xs_x=Cin, xs_c=1, B=B, Hi=Hi, Wi=Wi, Cin=Cin, Ho=Ho, Wo=Wo, N=Cout,
+                    TH=k, TW=k, in_stride=stride, dy0=-pad, dx0=-pad, dstep=1, Hy=Ho, Wy=Wo, out_stride=1, out_oy=0, out_ox=0,
+                    act=0 if lrelu is None else 2, act_slope=1.0 if lrelu is None else float(lrelu))
+
+
+def _dgrad_descs_bf16(in_shape, dz_shape, k, stride, pad):
+    """The input gradient's parity classes, their cy_conv_gemm_t without pointers, and whether they go in one launch."""
+    B, Hi, Wi, Cin = in_shape
+    _, Ho, Wo, Cout = dz_shape
+    classes = dgrad_classes(Hi, Wi, k, stride, pad)
+    descs = (ConvGemm * len(classes))()
+    for i, c in enumerate(classes):
+        descs[i] = ConvGemm(xs_b=Ho * Wo * Cout, xs_y=Wo * Cout, xs_x=Cout, xs_c=1, B=B, Hi=Ho, Wi=Wo, Cin=Cout,
+                            Ho=c['Ho'], Wo=c['Wo'], N=Cin, TH=c['TH'], TW=c['TW'], in_stride=1, dy0=c['dy0'], dx0=c['dx0'],
+                            dstep=c['dstep'], Hy=Hi, Wy=Wi, out_stride=c['out_stride'], out_oy=c['out_oy'], out_ox=c['out_ox'], act=0)
+    same = all((c['TH'], c['TW'], c['Ho'], c['Wo'], c['dstep'], c['out_stride']) ==
+               (classes[0]['TH'], classes[0]['TW'], classes[0]['Ho'], classes[0]['Wo'], classes[0]['dstep'], classes[0]['out_stride'])
+               for c in classes)
+    return classes, descs, BF16_DGRAD_ONE_LAUNCH and 1 < len(classes) <= 4 and same
+
+
+def _plan_bf16(descs, ncls, out_f32, bnf):
+    plan = (C.c_int * 5)()
+    if bnf:
+        for i in range(ncls):
+            descs[i].bn_red = 1                          # (the plan reads no pointer: only whether the sums are fused)
+    rc = query('cy_conv_gemm_bf16_plan', descs, ncls, 1 if out_f32 else 0, plan)
+    if rc != 0:
+        raise _lib.HipExtensionError('cy_conv_gemm_bf16_plan failed (code %d): %s' % (rc, query('capsyolo_last_error').decode()))
+    return dict(BM=plan[0], BN=plan[1], TAPIN=plan[2], ntiles=plan[3], blocks=plan[4])
+
+
+def conv_bf16_plans(op, in_shape, Cout, k, stride, pad, out_f32=False, bnf=False):
+    """The launches of conv_forward_bf16 (op 'fwd', in_shape = x's NHWC shape) or conv_dgrad_bf16 (op 'dgrad', in_shape = dx's)
+    for these shapes: one dict {BM, BN, TAPIN, ntiles, blocks} per launch, from cy_conv_gemm_bf16_plan (host arithmetic, no GPU)."""
+    B, Hi, Wi, Cin = in_shape
+    if op == 'fwd':
+        if bnf:
+            raise ValueError('the fused BatchNorm-backward sums belong to the input gradient')
+        return [_plan_bf16((ConvGemm * 1)(_fwd_desc_bf16(in_shape, Cout, k, stride, pad)), 1, out_f32, False)]
+    Ho, Wo = (Hi + 2 * pad - k) // stride + 1, (Wi + 2 * pad - k) // stride + 1
+    classes, descs, one_launch = _dgrad_descs_bf16(in_shape, (B, Ho, Wo, Cout), k, stride, pad)
+    if one_launch:
+        return [_plan_bf16(descs, len(classes), out_f32, bnf)]
+    return [_plan_bf16((ConvGemm * 1)(descs[i]), 1, out_f32, bnf) for i in range(len(classes))]
 
 
 def conv_wgrad_bf16(x, dz, k, stride, pad, tag='conv'):

@@ -278,6 +278,10 @@ int cy_conv_gemm_bf16(const cy_conv_gemm_t* a, int out_f32, void* stream);
  * input gradient (models.py:352-363 backward) -- in ONE launch: the classes of a pixel tile run on neighbouring blocks at the same
  * time, so X is fetched from HBM once instead of once per class. */
 int cy_conv_gemm_bf16_classes(const cy_conv_gemm_t* a, int ncls, int out_f32, void* stream);
+/* The plan the two entry points above launch for the same arguments, without a GPU (host arithmetic; pointers are not read):
+ * plan5 = {BM, BN, TAPIN (taps inside a channel chunk), ntiles, blocks}.  Returns what the launch would return for the shape
+ * (0, or CY_EINVAL with capsyolo_last_error() set). */
+int cy_conv_gemm_bf16_plan(const cy_conv_gemm_t* a, int ncls, int out_f32, int* plan5);
 /* weight gradient dW[Cout][Cin][KH][KW] (fp32) of a pad-1 3x3/stride-1 or 4x4/stride-2 layer from bf16 X and dZ;
  * ws: cy_conv_wgrad_bf16_ws_floats() floats of per-split partial sums, added in a fixed order (-1: unsupported shape) */
 long long cy_conv_wgrad_bf16_ws_floats(int B, int Ho, int Wo, int Cin, int Cout, int KH, int stride);
