@@ -136,21 +136,18 @@ class FusedBackbone(nn.Sequential):
                 # Winograd forward and weight-gradient kernels apply BatchNorm + LeakyReLU on their loads: the
                 # activation tensor (5.7 GB after conv_2 at the headline shape) is never written
                 defer = False
+                B, hin, win = x.shape[0], x.shape[2 if nchw_in else 1], x.shape[3 if nchw_in else 2]
+                ho = (hin + 2 * m.padding - m.k) // m.stride + 1
+                wo = (win + 2 * m.padding - m.k) // m.stride + 1
                 if (ops.FUSE_INPUT_AFFINE and self.training and bn is not None and slope is not None and 0.0 < slope <= 1.0
                         and nxt < len(mods) and isinstance(mods[nxt], HipConv2d)):
                     n = mods[nxt]
-                    hin = x.shape[2] if nchw_in else x.shape[1]
-                    win = x.shape[3] if nchw_in else x.shape[2]
-                    ho = (hin + 2 * m.padding - m.k) // m.stride + 1
-                    wo = (win + 2 * m.padding - m.k) // m.stride + 1
-                    defer = ops.s2_fusable(n.k, n.stride, n.padding, m.weight.shape[0], n.weight.shape[0], ho, wo)
+                    defer = ops.conv_plan((B, ho, wo, m.weight.shape[0]), n.weight.shape[0], n.k, n.stride, n.padding).in_affine
                 # ... and when a max-pool follows (DarkNet): activation + pooling in ONE pass over z, the pooling's backward with this
                 # block's BatchNorm-backward sums in one pass (not for the first layer: its recompute kernels keep their own path)
                 pool = False
                 if (self.training and bn is not None and bn.training and nxt < len(mods) and isinstance(mods[nxt], HipMaxPool2)
-                        and not (nchw_in and ops.conv1_ok(x, m.weight, m.k, m.stride, m.padding, nchw_in)) and not nchw_in):
-                    ho = (x.shape[1] + 2 * m.padding - m.k) // m.stride + 1
-                    wo = (x.shape[2] + 2 * m.padding - m.k) // m.stride + 1
+                        and not nchw_in):
                     pool = defer = ops.pool_fusable(m.weight.shape[0], ho, wo, slope)
                 cfg = ops.ConvBlockCfg(m.k, m.stride, m.padding, nchw_in, bn, slope, names[i], defer_act=defer,
                                        in_slope=lazy[2] if lazy is not None else None)
@@ -159,10 +156,10 @@ class FusedBackbone(nn.Sequential):
                                      bn.bias if bn is not None else None, cfg,
                                      lazy[0] if lazy is not None else None, lazy[1] if lazy is not None else None)
                 if pool:
-                    x, lazy = ops.affine_act_maxpool(out[0], out[1], out[2], slope, getattr(cfg, 'out_holder', None)), None
+                    x, lazy = ops.affine_act_maxpool(out[0], out[1], out[2], slope, cfg.out_holder), None
                     nxt += 1                                  # the max-pool module is done
                 elif defer:
-                    x, lazy = out[0], (out[1], out[2], slope, getattr(cfg, 'out_holder', None))
+                    x, lazy = out[0], (out[1], out[2], slope, cfg.out_holder)
                 else:
                     x, lazy = out, None
                 nchw_in = False

@@ -4,7 +4,9 @@ PyTorch supplies device memory, the current HIP stream and the autograd graph; e
 arithmetic step below is a call into libcapsyolo_hip.so.  All activations are NHWC fp32
 tensors ([B,H,W,C], plain contiguous).  No function here has a CPU or ATen fallback.
 """
+import collections
 import ctypes as C
+import functools
 
 import torch
 
@@ -151,27 +153,80 @@ WINOGRAD4_MIN_PIXELS = 1 << 17   # 512 output pixels x 64 channels per block: fa
 FUSE_BN_BWD_REDUCE = True  # ... and that block's input-gradient epilogue sums the producer's BatchNorm backward
 FUSE_BN_BWD_APPLY = True   # 3x3 blocks whose weight gradient is the Winograd kernel: BatchNorm backward pass 2 inside that kernel
 FUSE_INPUT_AFFINE = True  # a BN+LeakyReLU block in front of a 4x4/stride-2 block hands over its raw output + scale/shift
+USE_WINOGRAD4_WGRAD = True   # the 3x3 layers' weight gradient on F(3x3,4x4) (winograd4_wgrad.hip) where its shape conditions hold and the
+                             # map has WINOGRAD4_MIN_PIXELS output pixels (below, the F(3x3,2x2) kernel)
+
+ConvPlan = collections.namedtuple('ConvPlan', [
+    'fwd', 'dgrad', 'wgrad',   # the kernel family of each pass, named by its timer.range prefix (dgrad None: NCHW input, not implemented)
+    'in_affine',               # forward AND weight gradient take the producer's BatchNorm + LeakyReLU on their input loads (4x4 / stride 2)
+    'dgrad_bn_fuse',           # the input gradient's epilogue can sum the producer's BatchNorm backward (conv_dgrad's bn_fuse) ...
+    'dgrad_premasks',          # ... and then stores dx * lrelu'(y), not dx (the 4x4 / stride-2 Winograd kernels, capsyolo_hip.h)
+    'wgrad_bn',                # the weight gradient has the form with BatchNorm-backward pass 2 inside (conv_wino_wgrad_bn) ...
+    'wgrad_bn4',               # ... and, for a premasked gradient only, its F(3x3,4x4) form (conv_wino4_wgrad_bn)
+    'conv1',                   # a first-layer shape (csrc/conv1.hip: 3 -> {32, 64, 128} channels, 3x3 s1 p1, NCHW image)
+    'conv1_bwd',               # ... whose training block runs without z / dz in memory
+    'conv1_moments',           # ... taking its statistics from the moment matrix of the input patches
+    'conv1_onepass'])          # ... and, behind those statistics, its backward in one pass over the gradient
+_WINO3_DGRAD = ('conv_wino_dgrad', 'conv_wino4_dgrad')
 
 
-def s2_fusable(k, stride, pad, cin, cout, hi, wi, nchw=False):
-    """The 4x4 / stride-2 Winograd forward AND weight-gradient kernels both take this layer (then they can apply the
-    producer's BatchNorm + LeakyReLU on their input loads)."""
-    return (USE_WINOGRAD and USE_WINOGRAD_S2 and k == 4 and stride == 2 and pad == 1 and not nchw and cin % 32 == 0
-            and cout % 64 == 0 and hi % 2 == 0 and wi % 2 == 0)
+@functools.lru_cache(maxsize=None)
+def _shape_ok(name, *shape):
+    """One of the library's cy_*_ok host queries: a pure function of the shape, asked once per shape."""
+    return bool(query(name, *shape))
 
 
-def _winograd_ok(k, stride, pad, cin, nchw):
-    return USE_WINOGRAD and k == 3 and stride == 1 and pad == 1 and not nchw and cin % 8 == 0 and cin >= 8
+def conv_plan(in_shape, cout, k, stride, pad, nchw=False, relu=False, lrelu=False):
+    """Which kernel family runs each pass of one fp32 convolution, and what its block may fuse: a ConvPlan.  Host arithmetic
+    on the shape (in_shape = x.shape: NCHW if nchw, else NHWC), the epilogue (relu: fused ReLU; lrelu: the eval-mode LeakyReLU
+    epilogue) and the switches and thresholds above AS THEY STAND NOW -- every conv_forward / conv_dgrad / conv_wgrad / conv_block
+    call asks again, nothing is cached across a switch change.  This is the only place that decides."""
+    if nchw:
+        B, Cin, Hi, Wi = in_shape
+    else:
+        B, Hi, Wi, Cin = in_shape
+    fwd, dgrad, wgrad = 'conv_gemm_fwd', None if nchw else 'conv_gemm_dgrad', 'conv_wgrad'
+    in_affine = wgrad_bn = wgrad_bn4 = conv1 = False
+    if k == 3 and stride == 1 and pad == 1:
+        px = B * Hi * Wi
+        if nchw:
+            conv1 = bool(USE_CONV1 and Cin == 3 and cout in (32, 64, 128) and Wi % 32 == 0)
+            if conv1:
+                fwd, wgrad = fwd if relu or lrelu else 'conv1_fwd', 'conv1_wgrad'
+        elif USE_WINOGRAD:
+            f4 = USE_WINOGRAD4 and px >= WINOGRAD4_MIN_PIXELS
+            if not relu and Cin % 8 == 0 and Cin >= 8:
+                fwd = 'conv_wino4_fwd' if f4 else 'conv_wino_fwd'
+            if cout % 8 == 0 and cout >= 8:
+                dgrad = 'conv_wino4_dgrad' if f4 else 'conv_wino_dgrad'
+            w3 = Cin % 64 == 0 and cout % 64 == 0
+            w4 = bool(USE_WINOGRAD4_WGRAD and px >= WINOGRAD4_MIN_PIXELS and _shape_ok('cy_wino4_wgrad_ok', B, Hi, Wi, Cin, cout))
+            wgrad = 'conv_wino4_wgrad' if w4 else 'conv_wino_wgrad' if w3 else wgrad
+            wgrad_bn = bool(FUSE_BN_BWD_APPLY and w3)
+            wgrad_bn4 = wgrad_bn and w4
+    elif (k == 4 and stride == 2 and pad == 1 and not nchw and USE_WINOGRAD and USE_WINOGRAD_S2 and Hi % 2 == 0 and Wi % 2 == 0):
+        f4 = USE_WINOGRAD4_S2 and B * (Hi // 2) * (Wi // 2) >= WINOGRAD4_S2_MIN_PIXELS
+        if not relu and Cin % 8 == 0:
+            fwd = 'conv_wino42_fwd' if f4 and _shape_ok('cy_wino4s2_ok', B, Hi, Wi, Cin, cout) else 'conv_wino2_fwd'
+        if USE_WINOGRAD_S2_DGRAD and Cin % 64 == 0 and cout % 8 == 0:
+            dgrad = ('conv_wino42_dgrad' if f4 and USE_WINOGRAD4_S2_DGRAD and _shape_ok('cy_wino4s2_dgrad_ok', B, Hi, Wi, Cin, cout)
+                     else 'conv_wino2_dgrad')
+        if Cin % 32 == 0 and cout % 64 == 0:
+            wgrad, in_affine = 'conv_wino2_wgrad', not relu
+    dgrad_bn_fuse = bool(FUSE_BN_BWD_REDUCE and dgrad is not None and dgrad not in _WINO3_DGRAD and Cin % 4 == 0)
+    conv1_bwd = bool(conv1 and USE_CONV1_BWD)
+    return ConvPlan(fwd, dgrad, wgrad, in_affine, dgrad_bn_fuse, dgrad_bn_fuse and dgrad in ('conv_wino2_dgrad', 'conv_wino42_dgrad'),
+                    wgrad_bn, wgrad_bn4, conv1, conv1_bwd,
+                    bool(conv1_bwd and USE_CONV1_MOMENTS and B * Hi * Wi >= CONV1_MOMENTS_MIN_PIXELS), bool(conv1 and USE_CONV1_ONEPASS))
 
 
-def _winograd(x, weight, bias, stats, transpose, tag, out_slope=1.0):
-    """x [B,H,W,Cg] NHWC; weight in PyTorch layout; transpose=True computes the input gradient of the layer.
+def _winograd(x, weight, bias, stats, transpose, f4, tag, out_slope=1.0):
+    """x [B,H,W,Cg] NHWC; weight in PyTorch layout; transpose=True computes the input gradient of the layer; f4: on F(4x4,3x3).
     out_slope != 1: LeakyReLU epilogue (eval forward with the BatchNorm folded into weight / bias)."""
     B, H, W_, Cg = x.shape
     Cout_l, Cin_l = weight.shape[0], weight.shape[1]
     n = Cin_l if transpose else Cout_l
     st = _stream()
-    f4 = USE_WINOGRAD4 and B * H * W_ >= WINOGRAD4_MIN_PIXELS
     u = _empty((query('cy_wino4_packed_floats' if f4 else 'cy_wino_packed_floats', Cg, n),), x)
     call('cy_wino4_pack_weights' if f4 else 'cy_wino_pack_weights', _ptr(weight), _ptr(u), Cout_l, Cin_l, 1 if transpose else 0, st)
     y = _empty((B, H, W_, n), x)
@@ -185,12 +240,6 @@ def _winograd(x, weight, bias, stats, transpose, tag, out_slope=1.0):
             call('cy_conv3x3_winograd_ws', _ptr(x), _ptr(u), _ptr(y), _ptr(bias), _ptr(stats), float(out_slope), B, H, W_, Cg, n,
                  _ptr(ws), nws, st)
     return y
-
-
-def conv1_ok(x, weight, k, stride, pad, nchw):
-    """The dedicated first-layer kernels (csrc/conv1.hip) apply: 3 -> {32, 64, 128} channels, 3x3 s1 p1, NCHW image."""
-    return (USE_CONV1 and nchw and k == 3 and stride == 1 and pad == 1 and x.dim() == 4 and x.shape[1] == 3
-            and weight.shape[0] in (32, 64, 128) and x.shape[3] % 32 == 0 and x.is_contiguous())
 
 
 def conv1_affine_act(x, weight, bias, scale, shift, slope, tag='conv', out_bf16=False):
@@ -222,38 +271,29 @@ def conv_forward(x, weight, bias, k, stride, pad, nchw=False, stats=None, relu=F
     B, Hi, Wi, Cin, xs = _x_geometry(x, nchw)
     Cout = weight.shape[0]
     Ho, Wo = (Hi + 2 * pad - k) // stride + 1, (Wi + 2 * pad - k) // stride + 1
-    if in_affine is not None and not s2_fusable(k, stride, pad, Cin, Cout, Hi, Wi, nchw):
-        raise _lib.HipExtensionError('a fused input affine needs the 4x4/stride-2 Winograd kernels (got k=%d s=%d Cin=%d Cout=%d)'
-                                     % (k, stride, Cin, Cout))
-    if not relu and _winograd_ok(k, stride, pad, Cin, nchw):
-        return _winograd(x, weight, bias, stats, False, tag, osl)
-    if (USE_WINOGRAD and USE_WINOGRAD_S2 and not relu and k == 4 and stride == 2 and pad == 1 and not nchw
-            and Cin % 8 == 0 and Hi % 2 == 0 and Wi % 2 == 0 and x.is_contiguous()):
-        st = _stream()
+    plan = conv_plan(x.shape, Cout, k, stride, pad, nchw, relu, lrelu is not None)
+    if in_affine is not None and not plan.in_affine:
+        raise _lib.HipExtensionError('a fused input affine needs the 4x4/stride-2 Winograd kernels (got k=%d s=%d Cin=%d Cout=%d)' % (k, stride, Cin, Cout))
+    if plan.fwd in ('conv_wino_fwd', 'conv_wino4_fwd'):
+        return _winograd(x, weight, bias, stats, False, plan.fwd == 'conv_wino4_fwd', tag, osl)
+    st = _stream()
+    if plan.fwd in ('conv_wino2_fwd', 'conv_wino42_fwd'):
+        pk, f4 = ('cy_wino4s2', '4') if plan.fwd == 'conv_wino42_fwd' else ('cy_wino2', '')
         y = _empty((B, Ho, Wo, Cout), x)
         isc, ish, isl = in_affine if in_affine is not None else (None, None, 1.0)
-        if USE_WINOGRAD4_S2 and B * Ho * Wo >= WINOGRAD4_S2_MIN_PIXELS and query('cy_wino4s2_ok', B, Hi, Wi, Cin, Cout):
-            u = _empty((query('cy_wino4s2_packed_floats', Cin, Cout),), x)
-            call('cy_wino4s2_pack_weights', _ptr(weight), _ptr(u), Cout, Cin, st)
-            with timer.range('conv_wino42_fwd/' + tag):
-                call('cy_conv4x4s2_winograd4', _ptr(x), _ptr(u), _ptr(y), _ptr(bias), _ptr(stats), _ptr(isc), _ptr(ish),
-                     float(isl), osl, B, Hi, Wi, Cin, Cout, st)
-            return y
-        u = _empty((query('cy_wino2_packed_floats', Cin, Cout),), x)
-        call('cy_wino2_pack_weights', _ptr(weight), _ptr(u), Cout, Cin, st)
-        with timer.range('conv_wino2_fwd/' + tag):
-            call('cy_conv4x4s2_winograd', _ptr(x), _ptr(u), _ptr(y), _ptr(bias), _ptr(stats), _ptr(isc), _ptr(ish),
+        u = _empty((query(pk + '_packed_floats', Cin, Cout),), x)
+        call(pk + '_pack_weights', _ptr(weight), _ptr(u), Cout, Cin, st)
+        with timer.range(plan.fwd + '/' + tag):
+            call('cy_conv4x4s2_winograd' + f4, _ptr(x), _ptr(u), _ptr(y), _ptr(bias), _ptr(stats), _ptr(isc), _ptr(ish),
                  float(isl), osl, B, Hi, Wi, Cin, Cout, st)
         return y
-    if not relu and lrelu is None and conv1_ok(x, weight, k, stride, pad, nchw):
+    if plan.fwd == 'conv1_fwd':
         # the backbones' first layer (store-bound): persistent waves, operands from registers / L2
-        st = _stream()
         z = _empty((B, Ho, Wo, Cout), x)
         with timer.range('conv1_fwd/' + tag):
             call('cy_conv1_3x3_fwd', _ptr(x), _ptr(weight.contiguous()), _ptr(bias), _ptr(z), _ptr(stats), None, None, 1.0,
                  B, Hi, Wi, Cout, st)
         return z
-    st = _stream()
     wp = _empty((query('cy_conv_packed_floats', k * k * Cin, Cout),), x)
     call('cy_conv_pack_weights', _ptr(weight), _ptr(wp), Cout, Cin, k, k, k, k, 0, 0, 1, 0, st)
     z = _empty((B, Ho, Wo, Cout), x)
@@ -306,40 +346,29 @@ def dgrad_classes(Hi, Wi, k, stride, pad):
     return out
 
 
-def conv_dgrad(dz, weight, in_shape, k, stride, pad, tag='conv', bn_fuse=None, info=None):
+def conv_dgrad(dz, weight, in_shape, k, stride, pad, tag='conv', bn_fuse=None, plan=None):
     """dx[B,Hi,Wi,Cin] (NHWC) from dz[B,Ho,Wo,Cout]: one GEMM per output-parity class of the stride.
     bn_fuse = (z, scale, shift, mean, invstd, slope, red): dx is the gradient with respect to lrelu(z*scale+shift) of the
-    producer block; the epilogues also accumulate that BatchNorm's backward sums into red[STATS_COPIES][Cin][2]."""
+    producer block; the epilogues also accumulate that BatchNorm's backward sums into red[STATS_COPIES][Cin][2], and the 4x4 /
+    stride-2 Winograd kernels then store dx * lrelu'(y), not dx (conv_plan(...).dgrad_premasks)."""
     dz, weight = _f32(dz, 'grad'), _f32(weight, 'conv weight')
     B, Hi, Wi, Cin = in_shape
     _, Ho, Wo, Cout = dz.shape
-    if _winograd_ok(k, stride, pad, Cout, False):
+    plan = plan or conv_plan(in_shape, Cout, k, stride, pad)      # (a block's backward passes the one it asked for)
+    if plan.dgrad in _WINO3_DGRAD:
         if bn_fuse is not None:
             raise _lib.HipExtensionError('bn_fuse is implemented in the direct input-gradient kernel only')
-        return _winograd(dz, weight, None, None, True, tag)
+        return _winograd(dz, weight, None, None, True, plan.dgrad == 'conv_wino4_dgrad', tag)
     st = _stream()
     dx = _empty((B, Hi, Wi, Cin), dz)
-    if (USE_WINOGRAD and USE_WINOGRAD_S2 and USE_WINOGRAD_S2_DGRAD and k == 4 and stride == 2 and pad == 1 and Cin % 64 == 0
-            and Cout % 8 == 0 and Hi % 2 == 0 and Wi % 2 == 0 and dz.is_contiguous()):
-        bz = bsc = bsh = bmu = bis = bred = None
-        bsl = 0.0
-        if bn_fuse is not None:
-            bz, bsc, bsh, bmu, bis, bsl, bred = bn_fuse
-        if (USE_WINOGRAD4_S2 and USE_WINOGRAD4_S2_DGRAD and B * Ho * Wo >= WINOGRAD4_S2_MIN_PIXELS
-                and query('cy_wino4s2_dgrad_ok', B, Hi, Wi, Cin, Cout)):
-            u = _empty((query('cy_wino4s2_dgrad_packed_floats', Cin, Cout),), dz)
-            call('cy_wino4s2_pack_dgrad_weights', _ptr(weight), _ptr(u), Cout, Cin, st)
-            with timer.range('conv_wino42_dgrad/' + tag):
-                call('cy_conv4x4s2_winograd4_dgrad', _ptr(dz), _ptr(u), _ptr(dx), _ptr(bz), _ptr(bsc), _ptr(bsh), _ptr(bmu),
-                     _ptr(bis), float(bsl), _ptr(bred), B, Hi, Wi, Cin, Cout, st)
-        else:
-            u = _empty((query('cy_wino2_dgrad_packed_floats', Cin, Cout),), dz)
-            call('cy_wino2_pack_dgrad_weights', _ptr(weight), _ptr(u), Cout, Cin, st)
-            with timer.range('conv_wino2_dgrad/' + tag):
-                call('cy_conv4x4s2_winograd_dgrad', _ptr(dz), _ptr(u), _ptr(dx), _ptr(bz), _ptr(bsc), _ptr(bsh), _ptr(bmu),
-                     _ptr(bis), float(bsl), _ptr(bred), B, Hi, Wi, Cin, Cout, st)
-        if info is not None and bn_fuse is not None:
-            info['premasked'] = True      # with the fused sums this kernel stores dx * lrelu'(y), not dx (capsyolo_hip.h)
+    if plan.dgrad in ('conv_wino2_dgrad', 'conv_wino42_dgrad'):
+        pk, f4 = ('cy_wino4s2', '4') if plan.dgrad == 'conv_wino42_dgrad' else ('cy_wino2', '')
+        bz, bsc, bsh, bmu, bis, bsl, bred = bn_fuse if bn_fuse is not None else (None,) * 5 + (0.0, None)
+        u = _empty((query(pk + '_dgrad_packed_floats', Cin, Cout),), dz)
+        call(pk + '_pack_dgrad_weights', _ptr(weight), _ptr(u), Cout, Cin, st)
+        with timer.range(plan.dgrad + '/' + tag):
+            call('cy_conv4x4s2_winograd%s_dgrad' % f4, _ptr(dz), _ptr(u), _ptr(dx), _ptr(bz), _ptr(bsc), _ptr(bsh), _ptr(bmu),
+                 _ptr(bis), float(bsl), _ptr(bred), B, Hi, Wi, Cin, Cout, st)
         return dx
     wp = _empty((query('cy_conv_packed_floats', ((k + stride - 1) // stride) ** 2 * Cout, Cin),), dz)
     for c in dgrad_classes(Hi, Wi, k, stride, pad):
@@ -361,57 +390,41 @@ def conv_dgrad(dz, weight, in_shape, k, stride, pad, tag='conv', bn_fuse=None, i
     return dx
 
 
-def _wino_wgrad_ok(k, stride, pad, cin, cout):
-    return USE_WINOGRAD and k == 3 and stride == 1 and pad == 1 and cin % 64 == 0 and cout % 64 == 0
-
-
-USE_WINOGRAD4_WGRAD = True   # the 3x3 layers' weight gradient on F(3x3,4x4) (winograd4_wgrad.hip) where its shape conditions hold and the
-                             # map has WINOGRAD4_MIN_PIXELS output pixels (below, the F(3x3,2x2) kernel)
-
-
-def _wino4_wgrad_ok(B, H, W, cin, cout):
-    return (USE_WINOGRAD4_WGRAD and B * H * W >= WINOGRAD4_MIN_PIXELS and bool(query('cy_wino4_wgrad_ok', B, H, W, cin, cout)))
-
-
-def conv_wgrad(x, dz, k, stride, pad, nchw=False, tag='conv', in_affine=None):
+def conv_wgrad(x, dz, k, stride, pad, nchw=False, tag='conv', in_affine=None, plan=None):
     x, dz = _f32(x, 'conv input'), _f32(dz, 'grad')
     B, Hi, Wi, Cin, xs = _x_geometry(x, nchw)
     _, Ho, Wo, Cout = dz.shape
     st = _stream()
     dW = _empty((Cout, Cin, k, k), dz)
-    if not nchw and USE_WINOGRAD and k == 3 and stride == 1 and pad == 1 and _wino4_wgrad_ok(B, Hi, Wi, Cin, Cout):
+    plan = plan or conv_plan(x.shape, Cout, k, stride, pad, nchw)
+    if in_affine is not None and not plan.in_affine:
+        raise _lib.HipExtensionError('a fused input affine needs the 4x4/stride-2 Winograd weight-gradient kernel')
+    if plan.wgrad == 'conv_wino4_wgrad':
         ws = _empty((query('cy_wino4_wgrad_ws_floats', B, Hi, Wi, Cin, Cout),), dz)
         with timer.range('conv_wino4_wgrad/' + tag):
             call('cy_conv3x3_winograd4_wgrad', _ptr(x), _ptr(dz), _ptr(dW), _ptr(ws), B, Hi, Wi, Cin, Cout, st)
-        return dW
-    if not nchw and _wino_wgrad_ok(k, stride, pad, Cin, Cout):
+    elif plan.wgrad == 'conv_wino_wgrad':
         ws = _empty((query('cy_wino_wgrad_ws_floats', B, Cin, Cout),), dz)
         with timer.range('conv_wino_wgrad/' + tag):
             call('cy_conv3x3_winograd_wgrad', _ptr(x), _ptr(dz), _ptr(dW), _ptr(ws), B, Hi, Wi, Cin, Cout, st)
-        return dW
-    if (USE_WINOGRAD and USE_WINOGRAD_S2 and k == 4 and stride == 2 and pad == 1 and not nchw and Cin % 32 == 0
-            and Cout % 64 == 0 and Hi % 2 == 0 and Wi % 2 == 0 and x.is_contiguous() and dz.is_contiguous()):
+    elif plan.wgrad == 'conv_wino2_wgrad':
         ws = _empty((query('cy_wino2_wgrad_ws_floats', B, Cin, Cout),), dz)
         isc, ish, isl = in_affine if in_affine is not None else (None, None, 1.0)
         with timer.range('conv_wino2_wgrad/' + tag):
             call('cy_conv4x4s2_winograd_wgrad', _ptr(x), _ptr(dz), _ptr(dW), _ptr(ws), _ptr(isc), _ptr(ish), float(isl),
                  B, Hi, Wi, Cin, Cout, st)
-        return dW
-    if (USE_CONV1 and nchw and k == 3 and stride == 1 and pad == 1 and Cin == 3 and Cout in (32, 64, 128) and Wi % 32 == 0
-            and in_affine is None and x.is_contiguous() and dz.is_contiguous()):
+    elif plan.wgrad == 'conv1_wgrad':
         ws = _empty((query('cy_conv1_3x3_wgrad_ws_floats', B, Hi, Wi, Cout),), dz)
         with timer.range('conv1_wgrad/' + tag):
             call('cy_conv1_3x3_wgrad', _ptr(x), _ptr(dz), _ptr(dW), _ptr(ws), B, Hi, Wi, Cout, st)
-        return dW
-    if in_affine is not None:
-        raise _lib.HipExtensionError('a fused input affine needs the 4x4/stride-2 Winograd weight-gradient kernel')
-    a = ConvWgrad(X=x.data_ptr(), dZ=dz.data_ptr(), dW=dW.data_ptr(), slabs=None,
-                  xs_b=xs[0], xs_y=xs[1], xs_x=xs[2], xs_c=xs[3], B=B, Hi=Hi, Wi=Wi, Cin=Cin, Ho=Ho, Wo=Wo, N=Cout,
-                  KH=k, KW=k, stride=stride, pad=pad)
-    ws = _empty((query('cy_conv_wgrad_ws_floats', C.byref(a)),), dz)
-    a.slabs = ws.data_ptr()
-    with timer.range('conv_wgrad/' + tag):
-        call('cy_conv_wgrad', C.byref(a), st)
+    else:
+        a = ConvWgrad(X=x.data_ptr(), dZ=dz.data_ptr(), dW=dW.data_ptr(), slabs=None,
+                      xs_b=xs[0], xs_y=xs[1], xs_x=xs[2], xs_c=xs[3], B=B, Hi=Hi, Wi=Wi, Cin=Cin, Ho=Ho, Wo=Wo, N=Cout,
+                      KH=k, KW=k, stride=stride, pad=pad)
+        ws = _empty((query('cy_conv_wgrad_ws_floats', C.byref(a)),), dz)
+        a.slabs = ws.data_ptr()
+        with timer.range('conv_wgrad/' + tag):
+            call('cy_conv_wgrad', C.byref(a), st)
     return dW
 
 
@@ -449,6 +462,9 @@ class ConvBlockCfg(object):
         self.defer_act = defer_act   # return (z, scale, shift): the consumer applies BatchNorm + LeakyReLU on its loads
         self.in_slope = in_slope     # not None: x is the producer's raw output, in_scale / in_shift come with it
         self.in_holder = None        # the producer's hand-over dict (mean, invstd; this block's backward fills 'red')
+        self.out_holder = None       # this block's own hand-over dict, for its consumer (set by a deferring forward / the bf16 walk)
+        self.out_bf16 = False        # fp32 first block of the bf16 backbone: the activation leaves as bf16, the gradient arrives as bf16
+        self.in_f32 = self.out_f32 = False   # bf16 block: x comes from an fp32 producer / the activation leaves for an fp32 consumer
         self.bn = bn            # module with running_mean / running_var / momentum / eps / training, or None
         self.slope = slope      # None: no activation; 0.0: ReLU; else LeakyReLU slope
 
@@ -464,21 +480,39 @@ def _sync_world():
     return None, 1
 
 
+def _bn_finalize(stats, P, gamma, beta, bn, scale, shift, mean, invstd, N, st):
+    """Batch statistics (summed over all ranks under SYNC_BN) -> scale / shift / mean / invstd and the running statistics."""
+    dist, world = _sync_world()
+    if dist is not None:              # sum z / sum z^2 over the global batch (equal shards: dp.shard_range)
+        dist.all_reduce(stats)
+    call('cy_bn_finalize', _ptr(stats), P * world, _ptr(gamma), _ptr(beta), _ptr(bn.running_mean),
+         _ptr(bn.running_var), float(bn.momentum), float(bn.eps), _ptr(scale), _ptr(shift), _ptr(mean),
+         _ptr(invstd), N, _ptr(bn.num_batches_tracked), st)
+    _bump_param_epoch()               # running statistics were written through raw pointers
+
+
+def _leave(out, cfg, st):
+    """The fp32 activation on its way out: as bf16 where the consumer is a bf16 block (FusedBackbone._forward_bf16)."""
+    if not cfg.out_bf16:
+        return out
+    ob = torch.empty(out.shape, dtype=torch.bfloat16, device=out.device)
+    call('cy_cast_f32_bf16', _ptr(out), _ptr(ob), out.numel(), st)
+    return ob
+
+
 class _ConvBlock(torch.autograd.Function):
     """conv -> [BatchNorm (batch statistics from the conv epilogue)] -> [Leaky]ReLU, saving only x and z."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, cfg, in_scale=None, in_shift=None):
-        x = _f32(x, 'conv input')
-        weight = _f32(weight, 'conv weight')
+        x, weight = _f32(x, 'conv input'), _f32(weight, 'conv weight')
         st = _stream()
         N = weight.shape[0]
         bn = cfg.bn
         ctx.cfg, ctx.has_bias, ctx.bn_train = cfg, bias is not None, False
         ctx.set_materialize_grads(False)      # the (scale, shift) side outputs never get a gradient: no zero tensors for them
         ctx.holder = None
-        ina = (in_scale, in_shift, float(cfg.in_slope)) if cfg.in_slope is not None else None
-        ctx.in_affine = ina
+        ctx.in_affine = ina = (in_scale, in_shift, float(cfg.in_slope)) if cfg.in_slope is not None else None
         if bn is None:
             if cfg.defer_act:
                 raise _lib.HipExtensionError('defer_act needs a BatchNorm block')
@@ -490,19 +524,18 @@ class _ConvBlock(torch.autograd.Function):
                 call('cy_affine_act', _ptr(z), _ptr(out), None, None, float(cfg.slope), z.numel() // N, N, st)
             ctx.save_for_backward(x, weight, z)
             return out
-        scale, shift = _empty((N,), x), _empty((N,), x)
-        mean, invstd = _empty((N,), x), _empty((N,), x)
+        scale, shift, mean, invstd = (_empty((N,), x) for _ in range(4))
         slope = 1.0 if cfg.slope is None else float(cfg.slope)
+        plan = conv_plan(x.shape, N, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in)
         # the first block (csrc/conv1.hip): z is never written -- this pass only takes the statistics, the activation
         # pass and both backward passes recompute the convolution
         ctx.conv1_m2 = None
-        ctx.conv1_fused = bool(USE_CONV1_BWD and bn.training and not cfg.defer_act and not x.requires_grad
-                               and 0.0 <= slope <= 1.0 and conv1_ok(x, weight, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in))
+        ctx.conv1_fused = bool(plan.conv1_bwd and bn.training and not cfg.defer_act and not x.requires_grad and 0.0 <= slope <= 1.0)
         if bn.training:
             stats = zero_pool.take((STATS_COPIES, N, 2), torch.float64, x.device)
             if ctx.conv1_fused:
                 Bx, _, Hx, Wx = x.shape
-                if USE_CONV1_MOMENTS and Bx * Hx * Wx >= CONV1_MOMENTS_MIN_PIXELS:
+                if plan.conv1_moments:
                     # sum z and sum z^2 from the moment matrix of the input patches: the layer is not computed for them
                     wsm = _empty((query('cy_conv1_3x3_stats_ws_floats', Bx, Hx),), x)
                     with timer.range('conv1_fwd_stats/' + cfg.name):
@@ -519,32 +552,20 @@ class _ConvBlock(torch.autograd.Function):
             else:
                 z = conv_forward(x, weight, bias, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, stats, False, cfg.name, ina)
                 P = z.numel() // N
-            dist, world = _sync_world()
-            if dist is not None:              # sum z / sum z^2 over the global batch (equal shards: dp.shard_range)
-                dist.all_reduce(stats)
-            call('cy_bn_finalize', _ptr(stats), P * world, _ptr(gamma), _ptr(beta), _ptr(bn.running_mean),
-                 _ptr(bn.running_var), float(bn.momentum), float(bn.eps), _ptr(scale), _ptr(shift), _ptr(mean),
-                 _ptr(invstd), N, _ptr(bn.num_batches_tracked), st)
+            _bn_finalize(stats, P, gamma, beta, bn, scale, shift, mean, invstd, N, st)
             ctx.bn_train = True
-            _bump_param_epoch()               # running statistics were written through raw pointers
         else:
-            ctx.folded = False
-            if FOLD_EVAL_BN and not cfg.defer_act and ina is None and 0.0 <= slope <= 1.0:
+            ctx.folded = bool(FOLD_EVAL_BN and not cfg.defer_act and ina is None and 0.0 <= slope <= 1.0)
+            if ctx.folded:
                 # eval mode (predict_fns.py:38-43, 65-69): ONE launch per block.  The first layer applies scale / shift in its
                 # own epilogue (its kernel takes them); every other layer runs on weights and bias with the BatchNorm folded in
-                ctx.folded = True
                 ctx.save_for_backward()
-                if conv1_ok(x, weight, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in):
+                if plan.conv1:
                     call('cy_bn_eval_scale_shift', _ptr(gamma), _ptr(beta), _ptr(bn.running_mean), _ptr(bn.running_var),
                          float(bn.eps), _ptr(scale), _ptr(shift), N, st)
-                    return conv1_affine_act(x, weight, bias, scale, shift, slope, cfg.name, bool(getattr(cfg, 'out_bf16', False)))
+                    return conv1_affine_act(x, weight, bias, scale, shift, slope, cfg.name, cfg.out_bf16)
                 Wf, bf = fold_eval_bn(weight, bias, gamma, beta, bn)
-                out = conv_forward(x, Wf, bf, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, None, False, cfg.name, None, lrelu=slope)
-                if getattr(cfg, 'out_bf16', False):
-                    ob = torch.empty(out.shape, dtype=torch.bfloat16, device=out.device)
-                    call('cy_cast_f32_bf16', _ptr(out), _ptr(ob), out.numel(), st)
-                    return ob
-                return out
+                return _leave(conv_forward(x, Wf, bf, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, None, False, cfg.name, None, lrelu=slope), cfg, st)
             z = conv_forward(x, weight, bias, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, None, False, cfg.name, ina)
             P = z.numel() // N
             call('cy_bn_eval_scale_shift', _ptr(gamma), _ptr(beta), _ptr(bn.running_mean), _ptr(bn.running_var),
@@ -557,17 +578,11 @@ class _ConvBlock(torch.autograd.Function):
             # BatchNorm-backward sums (it has z and the gradient in registers) and leaves them in holder['red']
             ctx.holder = cfg.out_holder = {'mean': mean, 'invstd': invstd, 'red': None} if ctx.bn_train else None
             return z, scale, shift
-        ctx.holder = None
-        out_bf16 = bool(getattr(cfg, 'out_bf16', False))     # the consumer is a bf16 block (FusedBackbone._forward_bf16)
-        if conv1_ok(x, weight, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in) and 0.0 <= slope <= 1.0:
-            return conv1_affine_act(x, weight, bias, scale, shift, slope, cfg.name, out_bf16)
+        if plan.conv1 and 0.0 <= slope <= 1.0:
+            return conv1_affine_act(x, weight, bias, scale, shift, slope, cfg.name, cfg.out_bf16)
         out = torch.empty_like(z)
         call('cy_affine_act', _ptr(z), _ptr(out), _ptr(scale), _ptr(shift), slope, P, N, st)
-        if out_bf16:
-            ob = torch.empty(out.shape, dtype=torch.bfloat16, device=out.device)
-            call('cy_cast_f32_bf16', _ptr(out), _ptr(ob), out.numel(), st)
-            return ob
-        return out
+        return _leave(out, cfg, st)
 
     @staticmethod
     def backward(ctx, da, *unused):
@@ -576,7 +591,7 @@ class _ConvBlock(torch.autograd.Function):
             raise _lib.HipExtensionError('conv block %s: no gradient reached its output' % cfg.name)
         if getattr(ctx, 'folded', False):
             raise _lib.HipExtensionError('backward through an eval-mode BatchNorm block is not implemented')
-        da_bf16 = da.dtype == torch.bfloat16 and bool(getattr(cfg, 'out_bf16', False))
+        da_bf16 = da.dtype == torch.bfloat16 and cfg.out_bf16
         if da_bf16 and not (cfg.bn is not None and ctx.bn_train and ctx.conv1_fused):
             daf = torch.empty(da.shape, dtype=torch.float32, device=da.device)   # only the first-layer kernels read a bf16 gradient
             call('cy_cast_bf16_f32', _ptr(da.contiguous()), _ptr(daf), da.numel(), _stream())
@@ -588,8 +603,8 @@ class _ConvBlock(torch.autograd.Function):
         x, weight, z = saved[0], saved[1], saved[2]
         N = weight.shape[0]
         P = ctx.P if cfg.bn is not None else z.numel() // N
-        dgamma = dbeta = dbias = None
-        fused_wgrad = False
+        plan = conv_plan(x.shape, N, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in)
+        dgamma = dbeta = dbias = dW = None
         if cfg.bn is None:
             if cfg.slope is not None:
                 dz = torch.empty_like(z)
@@ -611,34 +626,29 @@ class _ConvBlock(torch.autograd.Function):
                 bias_t = saved[8] if ctx.has_bias else None
                 B, _, Hi, Wi = x.shape
                 redc = zero_pool.take((STATS_COPIES, N, 2), torch.float64, z.device)
-                if USE_CONV1_ONEPASS and getattr(ctx, 'conv1_m2', None) is not None and _sync_world()[0] is None:
+                dW, dbeta, dgamma = _empty(tuple(weight.shape), z), _empty((N,), z), _empty((N,), z)
+                ws = _empty((query('cy_conv1_bn_bwd_wgrad_ws_floats', B, Hi, Wi, N),), z)
+                dbias = _const_zeros(N, z) if ctx.has_bias else None
+                if plan.conv1_onepass and ctx.conv1_m2 is not None and _sync_world()[0] is None:
                     # one pass over da: sum d and the weight gradient OF d; the rest follows from the forward's patch moments
-                    dW = _empty(tuple(weight.shape), z)
-                    dbeta, dgamma = _empty((N,), z), _empty((N,), z)
-                    ws = _empty((query('cy_conv1_bn_bwd_wgrad_ws_floats', B, Hi, Wi, N),), z)
                     with timer.range('conv1_bn_bwd_onepass/' + cfg.name):
                         call('cy_conv1_bn_bwd_onepass_bf16' if da_bf16 else 'cy_conv1_bn_bwd_onepass', _ptr(x), _ptr(weight),
                              _ptr(bias_t), _ptr(da), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), slope,
                              _ptr(ctx.conv1_m2), _ptr(redc), _ptr(dW), _ptr(dgamma), _ptr(dbeta), None, _ptr(ws), B, Hi, Wi, N, st)
-                    dbias = _const_zeros(N, z) if ctx.has_bias else None
                     return None, dW, dbias, dgamma, dbeta, None, None, None
                 with timer.range('conv1_bn_bwd_reduce/' + cfg.name):
                     call('cy_conv1_bn_bwd_reduce_bf16' if da_bf16 else 'cy_conv1_bn_bwd_reduce', _ptr(x), _ptr(weight), _ptr(bias_t), _ptr(da), _ptr(scale), _ptr(shift),
                          _ptr(mean), _ptr(invstd), slope, _ptr(redc), B, Hi, Wi, N, st)
                 red = _empty((N, 2), z, torch.float64)
-                dbeta, dgamma = _empty((N,), z), _empty((N,), z)
                 dist, world = _sync_world()
                 # copies folded (and, data parallel, pre-scaled by 1 / world so that the all-reduce SUM is the mean)
                 call('cy_bn_red_fold', _ptr(redc), STATS_COPIES, 1.0 / world, _ptr(red), _ptr(dgamma), _ptr(dbeta), N, st)
                 if dist is not None:
                     dist.all_reduce(red)
                     call('cy_bn_red_fold', _ptr(red), 1, 1.0, None, _ptr(dgamma), _ptr(dbeta), N, st)
-                dW = _empty(tuple(weight.shape), z)
-                ws = _empty((query('cy_conv1_bn_bwd_wgrad_ws_floats', B, Hi, Wi, N),), z)
                 with timer.range('conv1_bn_bwd_wgrad/' + cfg.name):
                     call('cy_conv1_bn_bwd_wgrad_bf16' if da_bf16 else 'cy_conv1_bn_bwd_wgrad', _ptr(x), _ptr(weight), _ptr(bias_t), _ptr(da), _ptr(scale), _ptr(shift),
                          _ptr(mean), _ptr(invstd), slope, _ptr(red), P, _ptr(dW), _ptr(ws), B, Hi, Wi, N, st)
-                dbias = _const_zeros(N, z) if ctx.has_bias else None
                 return None, dW, dbias, dgamma, dbeta, None, None, None
             premasked = False
             if ctx.holder is not None and ctx.holder.get('red') is not None:
@@ -664,15 +674,14 @@ class _ConvBlock(torch.autograd.Function):
             if ctx.has_bias:
                 # a bias in front of BatchNorm has an analytically zero gradient: sum(dz) == 0
                 dbias = _const_zeros(N, z)
-            if (FUSE_BN_BWD_APPLY and ctx.in_affine is None and not cfg.nchw_in
-                    and _wino_wgrad_ok(cfg.k, cfg.stride, cfg.pad, x.shape[3], N)):
+            if plan.wgrad_bn and ctx.in_affine is None:
                 # pass 2 of the BatchNorm backward inside the Winograd weight-gradient kernel, which has every dz element in
                 # registers on its way to LDS anyway and writes it out for the input-gradient kernel
                 red = red.contiguous()
                 call('cy_bn_param_grad', _ptr(red), _ptr(dgamma), _ptr(dbeta), N, st)
                 B_, Hi, Wi, Cin = x.shape
                 dW = _empty(tuple(weight.shape), z)
-                if premasked and _wino4_wgrad_ok(B_, Hi, Wi, Cin, N):
+                if premasked and plan.wgrad_bn4:
                     ws = _empty((query('cy_wino4_wgrad_ws_floats', B_, Hi, Wi, Cin, N),), z)
                     with timer.range('conv_wino4_wgrad_bn/' + cfg.name):
                         call('cy_conv3x3_winograd4_wgrad_bn', _ptr(_f32(x, 'conv input')), _ptr(z), _ptr(da), _ptr(dz), _ptr(scale),
@@ -683,25 +692,22 @@ class _ConvBlock(torch.autograd.Function):
                         call('cy_conv3x3_winograd_wgrad_bn', _ptr(_f32(x, 'conv input')), _ptr(z), _ptr(da), _ptr(dz), _ptr(scale),
                              _ptr(shift), _ptr(mean), _ptr(invstd), slope, 1 if premasked else 0, _ptr(red), P, _ptr(dW), _ptr(ws),
                              B_, Hi, Wi, Cin, N, st)
-                fused_wgrad = True
             else:
                 call('cy_bn_bwd_apply', _ptr(z), _ptr(da), _ptr(dz), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd),
                      _ptr(gamma), slope, _ptr(red), _ptr(dgamma), _ptr(dbeta), P, N, st)
-        if not fused_wgrad:
-            dW = conv_wgrad(x, dz, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, cfg.name, ctx.in_affine)
+        if dW is None:
+            dW = conv_wgrad(x, dz, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, cfg.name, ctx.in_affine, plan)
         dx = None
         if ctx.needs_input_grad[0]:
-            if cfg.nchw_in:
+            if plan.dgrad is None:
                 raise _lib.HipExtensionError('input gradient of an NCHW-input convolution is not implemented')
             fuse, h = None, cfg.in_holder
-            if (FUSE_BN_BWD_REDUCE and ctx.in_affine is not None and h is not None and x.shape[3] % 4 == 0
-                    and not _winograd_ok(cfg.k, cfg.stride, cfg.pad, N, False)):
+            if plan.dgrad_bn_fuse and ctx.in_affine is not None and h is not None:
                 bred = zero_pool.take((STATS_COPIES, x.shape[3], 2), torch.float64, x.device)
                 fuse = (x, ctx.in_affine[0], ctx.in_affine[1], h['mean'], h['invstd'], ctx.in_affine[2], bred)
-            info = {}
-            dx = conv_dgrad(dz, weight, tuple(x.shape), cfg.k, cfg.stride, cfg.pad, cfg.name, fuse, info)
+            dx = conv_dgrad(dz, weight, tuple(x.shape), cfg.k, cfg.stride, cfg.pad, cfg.name, fuse, plan)
             if fuse is not None:
-                h['premasked'] = bool(info.get('premasked', False))
+                h['premasked'] = plan.dgrad_premasks
                 h['red'] = _empty((x.shape[3], 2), x, torch.float64)
                 call('cy_bn_red_fold', _ptr(bred), STATS_COPIES, 1.0, _ptr(h['red']), None, None, x.shape[3], st)
         return dx, dW, dbias, dgamma, dbeta, None, None, None
@@ -873,7 +879,7 @@ class _ConvBlockBF16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, cfg):
         st = _stream()
-        if getattr(cfg, 'in_f32', False):
+        if cfg.in_f32:
             # the producer is an fp32 kernel (the first block): round its activation to bf16 HERE, so that autograd sees an
             # fp32 input and takes the fp32 gradient this block's input-gradient kernel writes (a separate cast Function made
             # the engine convert that gradient to bf16 and back: two 3 GB passes at 608 x 608)
@@ -891,30 +897,23 @@ class _ConvBlockBF16(torch.autograd.Function):
             stats = zero_pool.take((STATS_COPIES, N, 2), torch.float64, x.device)
             z = conv_forward_bf16(x, weight, bias, cfg.k, cfg.stride, cfg.pad, stats, cfg.name)
             P = z.numel() // N
-            dist, world = _sync_world()
-            if dist is not None:
-                dist.all_reduce(stats)
-            call('cy_bn_finalize', _ptr(stats), P * world, _ptr(gamma), _ptr(beta), _ptr(bn.running_mean), _ptr(bn.running_var),
-                 float(bn.momentum), float(bn.eps), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), N,
-                 _ptr(bn.num_batches_tracked), st)
-            _bump_param_epoch()
+            _bn_finalize(stats, P, gamma, beta, bn, scale, shift, mean, invstd, N, st)
         else:
             if FOLD_EVAL_BN and 0.0 <= float(cfg.slope) <= 1.0:     # eval mode: ONE launch, BatchNorm folded into weights / bias
                 Wf, bf = fold_eval_bn(weight, bias, gamma, beta, bn)
                 ctx.bn_train = False
                 ctx.save_for_backward()
-                return conv_forward_bf16(x, Wf, bf, cfg.k, cfg.stride, cfg.pad, None, cfg.name, lrelu=float(cfg.slope),
-                                         out_f32=bool(getattr(cfg, 'out_f32', False)))
+                return conv_forward_bf16(x, Wf, bf, cfg.k, cfg.stride, cfg.pad, None, cfg.name, lrelu=float(cfg.slope), out_f32=cfg.out_f32)
             z = conv_forward_bf16(x, weight, bias, cfg.k, cfg.stride, cfg.pad, None, cfg.name)
             P = z.numel() // N
             call('cy_bn_eval_scale_shift', _ptr(gamma), _ptr(beta), _ptr(bn.running_mean), _ptr(bn.running_var), float(bn.eps),
                  _ptr(scale), _ptr(shift), N, st)
         ctx.bn_train, ctx.P = bool(bn.training), P
-        out_f32 = bool(getattr(cfg, 'out_f32', False))
+        out_f32 = cfg.out_f32
         out = torch.empty(z.shape, dtype=torch.float32 if out_f32 else torch.bfloat16, device=z.device)
         call('cy_affine_act_bf16', _ptr(z), _ptr(out), _ptr(scale), _ptr(shift), float(cfg.slope), P, N, 1 if out_f32 else 0, st)
         ctx.save_for_backward(x, weight, z, scale, shift, mean, invstd)
-        h = getattr(cfg, 'out_holder', None)
+        h = cfg.out_holder
         if h is not None:
             # what the CONSUMER block's input-gradient epilogue needs for this block's BatchNorm-backward sums (bf16 output only)
             h.clear()
@@ -933,7 +932,7 @@ class _ConvBlockBF16(torch.autograd.Function):
         da_f32 = da.dtype == torch.float32
         da = _f32(da, 'grad') if da_f32 else _bf(da, 'grad')
         slope = float(cfg.slope)
-        ho = getattr(cfg, 'out_holder', None)
+        ho = cfg.out_holder
         if ho is not None and ho.get('red') is not None and not da_f32:
             red = ho['red']                    # summed by the consumer block's input-gradient epilogues, which also stored da premasked
             ho['red'] = None
@@ -965,8 +964,7 @@ class _ConvBlockBF16(torch.autograd.Function):
             dW = conv_wgrad_bf16(x, dz, cfg.k, cfg.stride, cfg.pad, cfg.name)
         dx = None
         if ctx.needs_input_grad[0]:
-            in_f32 = bool(getattr(cfg, 'in_f32', False))
-            hi = getattr(cfg, 'in_holder', None)
+            in_f32, hi = cfg.in_f32, cfg.in_holder
             fuse = None
             if (FUSE_BN_BWD_REDUCE_BF16 and hi is not None and hi.get('z') is not None and not in_f32
                     and tuple(hi['z'].shape) == tuple(x.shape)):

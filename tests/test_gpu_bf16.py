@@ -98,7 +98,8 @@ def test_first_block_of_the_bf16_path(B, H, W, cout):
         keys = set(k.split('/')[0] for k in ops.timer.events)
     finally:
         ops.timer.enabled = False
-    onepass = B * H * W >= ops.CONV1_MOMENTS_MIN_PIXELS
+    plan = ops.conv_plan((B, 3, H, W), cout, 3, 1, 1, True)
+    onepass = plan.conv1_moments and plan.conv1_onepass
     assert ('conv1_bn_bwd_onepass' in keys) == onepass and ('conv1_bn_bwd_wgrad' in keys) == (not onepass), keys
     assert rel_l2(out.float().permute(0, 3, 1, 2), a) < 1e-2
     assert rel_l2(hc.weight.grad, conv.weight.grad) < 2e-2

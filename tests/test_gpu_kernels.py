@@ -433,10 +433,12 @@ def test_conv_dgrad_epilogue_bn_backward_sums(case, monkeypatch):
     sc, sh = (rnd((Cin,), 114, 0.3) + 1.0).to(dev()), rnd((Cin,), 115, 0.5).to(dev())
     mu, isd = rnd((Cin,), 116, 0.2).to(dev()), (rnd((Cin,), 117, 0.1).abs() + 0.8).to(dev())
     red = torch.zeros((ops.STATS_COPIES, Cin, 2), dtype=torch.float64, device=dev())
-    info = {}
-    dx = ops.conv_dgrad(dz, w, (B, Hi, Hi, Cin), k, stride, pad, 'c', (z, sc, sh, mu, isd, 0.1, red), info)
+    plan = ops.conv_plan((B, Hi, Hi, Cin), Cout, k, stride, pad)
+    assert plan.dgrad_bn_fuse and plan.dgrad_premasks == (k == 4 and Cin % 64 == 0)
+    assert plan.dgrad == ('conv_gemm_dgrad' if not plan.dgrad_premasks else 'conv_wino42_dgrad' if len(case) == 8 else 'conv_wino2_dgrad')
+    dx = ops.conv_dgrad(dz, w, (B, Hi, Hi, Cin), k, stride, pad, 'c', (z, sc, sh, mu, isd, 0.1, red))
     dx0 = ops.conv_dgrad(dz, w, (B, Hi, Hi, Cin), k, stride, pad)
-    if info.get('premasked'):
+    if plan.dgrad_premasks:
         # the stride-2 Winograd kernel stores d = dx * lrelu'(y) when it sums (include/capsyolo_hip.h): the producer block's
         # backward then runs with slope 1
         assert k == 4 and Cin % 64 == 0
@@ -1243,7 +1245,7 @@ def test_round3_winograd_kernels_repeat_bit_for_bit(monkeypatch):
 
     def bn_dgrad():
         red = torch.zeros((ops.STATS_COPIES, 128, 2), dtype=torch.float64, device=dev())
-        return ops.conv_dgrad(dz4, w4, (B, H, H, 128), 4, 2, 1, 'c', (z, sc, sh, mu, isd, 0.1, red), {})
+        return ops.conv_dgrad(dz4, w4, (B, H, H, 128), 4, 2, 1, 'c', (z, sc, sh, mu, isd, 0.1, red))
     cases = {
         'F(4x4,3x3) forward': lambda: ops.conv_forward(x, w3, None, 3, 1, 1),
         'F(4x4,3x3) input gradient': lambda: ops.conv_dgrad(dz3, w3, (B, H, H, 128), 3, 1, 1),

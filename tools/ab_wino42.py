@@ -51,10 +51,10 @@ for name, H, Cin, Cout in (('conv_3', 416, 256, 64), ('conv_4', 208, 64, 128), (
         ops.USE_WINOGRAD4_S2_DGRAD = f42
         red = torch.zeros(ops.STATS_COPIES, Cin, 2, dtype=torch.float64, device=dev)
         dx = ops.conv_dgrad(dz, w, (B, H, H, Cin), 4, 2, 1)
-        dxb = ops.conv_dgrad(dz, w, (B, H, H, Cin), 4, 2, 1, 'c', (zin, sc, sh, mu, isd, 0.1, red), {})
+        dxb = ops.conv_dgrad(dz, w, (B, H, H, Cin), 4, 2, 1, 'c', (zin, sc, sh, mu, isd, 0.1, red))
         redc = red.sum(0).clone()
         t = med(lambda: ops.conv_dgrad(dz, w, (B, H, H, Cin), 4, 2, 1))
-        tb = med(lambda: ops.conv_dgrad(dz, w, (B, H, H, Cin), 4, 2, 1, 'c', (zin, sc, sh, mu, isd, 0.1, red), {}))
+        tb = med(lambda: ops.conv_dgrad(dz, w, (B, H, H, Cin), 4, 2, 1, 'c', (zin, sc, sh, mu, isd, 0.1, red)))
         res[f42] = (dx, dxb, redc, t, tb)
     d0, db0, r0, t0, tb0 = res[False]; d1, db1, r1, t1, tb1 = res[True]
     print('%s input gradient: F(2x2,2x2) %.3f ms, F(4x4,2x2) %.3f ms (%.0f TFLOP/s direct-equivalent) | with the BatchNorm sums %.3f -> %.3f ms | rel L2 diff %.2e / %.2e, sums %.2e'

@@ -79,7 +79,7 @@ for (Cin, H, Cout, k, s) in ((128, 208, 256, 3, 1), (256, 208, 64, 4, 2), (64, 1
         rep(tag + 'fp32 F(4x4,2x2) fwd, input affine', lambda: ops.conv_forward(x, w, None, k, s, 1, False, None, False, 'c', (sc, sh, 0.1)))
         rep(tag + 'fp32 F(4x4,2x2) dgrad', lambda: ops.conv_dgrad(dz, w, (B, H, H, Cin), k, s, 1))
         # (the sums themselves are double atomics: the stored premasked gradient is what must repeat)
-        rep(tag + 'fp32 F(4x4,2x2) dgrad + BatchNorm sums (dx)', lambda: ops.conv_dgrad(dz, w, (B, H, H, Cin), k, s, 1, 'c', (zz, sc, sh, mu, isd, 0.1, red), {}))
+        rep(tag + 'fp32 F(4x4,2x2) dgrad + BatchNorm sums (dx)', lambda: ops.conv_dgrad(dz, w, (B, H, H, Cin), k, s, 1, 'c', (zz, sc, sh, mu, isd, 0.1, red)))
         ops.WINOGRAD4_S2_MIN_PIXELS = old
 print('check_determinism:', 'ok' if bad == 0 else 'FAILED')
 sys.exit(0 if bad == 0 else 1)

@@ -60,7 +60,7 @@ for it in range(n):
 
         def dg():
             r = reds[k2[0]]; k2[0] += 1
-            return ops.conv_dgrad(dz, w, (B, H, W, Cin), 4, 2, 1, 'c', (z, sc, sh, mu, isd, 0.1, r), {})
+            return ops.conv_dgrad(dz, w, (B, H, W, Cin), 4, 2, 1, 'c', (z, sc, sh, mu, isd, 0.1, r))
         d1, d0 = both(dg, ['USE_WINOGRAD4_S2_DGRAD'])
         e = (rel(y1, y0), rel(st[0].sum(0), st[1].sum(0)), rel(d1, d0), rel(reds[0].sum(0), reds[1].sum(0)))
         ok = e[0] < 5e-5 and e[1] < 1e-4 and e[2] < 5e-5 and e[3] < 2e-4
