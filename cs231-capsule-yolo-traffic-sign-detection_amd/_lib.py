@@ -121,6 +121,10 @@ _SIGS = {
     'cy_yolo_head_bwd': [_P, _P, _P, _L, _I, _I, _P],
     'cy_yolo_decode_boxes': [_P, _P, C.c_double, C.c_double, _I, _I, _I, _I, _F, _P, _P, _P, _P, _I, _P],
     'cy_detect_confusion': [_P, _P, _I, _P, _P, _I, _I, C.c_double, _I, _P, _P],
+    'cy_crop_resize_u8': [_P, _P, _P, _I, _L, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P],
+    'cy_combine_scores': [_P, _P, _P, _P, _I, _P, C.c_double, _I, _I, _I, _I, _P, _P, _P, _P],
+    'cy_yolo_decode_boxes_conf': [_P, _P, C.c_double, C.c_double, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P],
+    'cy_confusion_sweep': [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P],
     'cy_pick_capsule': [_P, _P, _P, _I, _I, _I, _I, _P],
     'cy_zero_bytes': [_P, _L, _P],
     'cy_conv_bf16_pack_weights': [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],

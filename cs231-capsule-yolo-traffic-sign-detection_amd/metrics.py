@@ -1,9 +1,10 @@
-"""Detection metrics of the reference on the device: metrics.detect_acc / detect_and_recog_acc / detect_AP
-(metrics.py:193-282).
+"""Detection metrics of the reference on the device: metrics.detect_acc / detect_and_recog_acc / detect_AP /
+detect_and_recog_mAP (metrics.py:193-339).
 
 The reference decodes both arrays to boxes with numpy and matches them with two nested Python loops per image
 (metrics.py:136-147) every `eval_every` epochs; here the decoding (`cy_yolo_decode_boxes`) and the IoU matching
-(`cy_detect_confusion`, one block per image) stay on the GPU and only TP / FP / FN come back.
+(`cy_detect_confusion`, one block per image) stay on the GPU and only TP / FP / FN come back.  `confusion_sweep` does the whole
+confidence x IoU threshold sweep of the AP metrics with one decode per array and one launch (`cy_confusion_sweep`).
 """
 import numpy as np
 import torch
@@ -106,3 +107,73 @@ def detect_AP(y, y_hat, params, show=False, save=False, save_dir=None):
         for i, iou_th in enumerate(iou_ths):
             prec[i, k], rec[i, k] = precision_and_recall(*_confusion_of_boxes(gt, pr, yt, ht, params, iou_th))
     return np.mean(np.array([average_precision(prec[i], rec[i]) for i in range(10)]))
+
+
+def _as_device_f32(a):
+    return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).to(device='cuda', dtype=torch.float32).contiguous()
+
+
+def confusion_sweep(y, y_hat, params, conf_ths, iou_ths, per_class=True):
+    """(TP, FP, FN) of metrics.single_img_confusion summed over the images for EVERY confidence threshold, class and IoU
+    threshold: int64 numpy [K][C or 1][T][3] (per_class=False: boxes are matched per image whatever their class, as in
+    detect_AP).  The reference decodes both arrays again for every confidence threshold (metrics.py:298-302); a pair's IoU does
+    not depend on it, so both are decoded once at min(conf_ths) with their confidences, sorted by image * C + class, and one
+    launch counts everything: a box is hit at (th, iou_t) iff min(its confidence, best partner confidence at iou_t) > th."""
+    C = int(params.n_classes)
+    if per_class and C <= 0:
+        raise ValueError('confusion_sweep(per_class=True) needs a classifying head (n_classes > 0)')
+    conf_ths = np.ascontiguousarray(np.asarray(conf_ths, dtype=np.float64).reshape(-1))
+    iou_ths = np.ascontiguousarray(np.asarray(iou_ths, dtype=np.float64).reshape(-1))
+    K, T = len(conf_ths), len(iou_ths)
+    if K < 1 or T < 1:
+        raise ValueError('confusion_sweep needs at least one confidence and one IoU threshold')
+    lo = np.float32(conf_ths.min())
+    if float(lo) > conf_ths.min():          # the decode compares in float: never start above the lowest threshold
+        lo = np.nextafter(lo, np.float32(-np.inf))
+    yt, ht = _as_device_f32(y), _as_device_f32(y_hat)
+    Cn = C if per_class else 1
+    sets = []
+    for arr in (yt, ht):
+        n, idx, xy, cls, conf = utils.decode_boxes_device(arr, params, None, float(lo), with_conf=True)
+        if n and per_class:
+            key, order = torch.sort(idx.long() * C + cls.long(), stable=True)
+            idx, xy, conf = key.to(torch.int32).contiguous(), xy[order].contiguous(), conf[order].contiguous()
+        sets.append((n, idx, xy, conf))
+    batch, g = int(yt.shape[0]), int(yt.shape[1])
+    nb_max = max((int(yt.shape[3]) - C) // 5, (int(ht.shape[3]) - C) // 5)
+    (n1, gk, gxy, gcf), (n2, pk, pxy, pcf) = sets
+    ths = torch.from_numpy(np.concatenate([conf_ths, iou_ths])).cuda()
+    out = torch.zeros(K * Cn * T * 3 + 1, dtype=torch.int32, device='cuda')          # the table, then the error word
+    call('cy_confusion_sweep', gk.data_ptr() if n1 else None, gxy.data_ptr() if n1 else None, gcf.data_ptr() if n1 else None, n1,
+         pk.data_ptr() if n2 else None, pxy.data_ptr() if n2 else None, pcf.data_ptr() if n2 else None, n2,
+         batch * Cn, Cn, ths.data_ptr(), K, ths.data_ptr() + 8 * K, T, g * g * nb_max,
+         out.data_ptr(), out.data_ptr() + 4 * (K * Cn * T * 3), torch.cuda.current_stream().cuda_stream)
+    host = out.cpu().numpy()
+    if host[-1] >= 1 << 20:
+        raise RuntimeError('confusion_sweep: a group holds more than %d boxes' % (g * g * nb_max))
+    if host[-1]:
+        raise AssertionError('malformed box (x1 > x2 or y1 > y2) in %d case(s)' % host[-1])
+    return host[:-1].astype(np.int64).reshape(K, Cn, T, 3)
+
+
+def _ap_table(counts):
+    """[C][T] 11-point average precision over the K confidence thresholds of a count table [K][C][T][3]."""
+    K, Cn, T, _ = counts.shape
+    table = np.zeros((Cn, T))
+    for c in range(Cn):
+        for t in range(T):
+            pr = [precision_and_recall(*[int(v) for v in counts[k, c, t]]) for k in range(K)]
+            table[c, t] = average_precision(np.array([p for p, _ in pr]), np.array([r for _, r in pr]))
+    return table
+
+
+def detect_and_recog_mAP(y, y_hat, params, show=False, save=False, save_dir=None):
+    """metrics.py:284-339 (plots are out of scope): the mean, over the classes present in y and the 10 IoU thresholds, of the
+    11-point AP over 100 confidence thresholds, boxes matched per image and class.  Sets params.n_classes = 43 like the
+    reference (metrics.py:285)."""
+    params.n_classes = 43
+    counts = confusion_sweep(y, y_hat, params, np.linspace(0, 1, 100), np.linspace(0.5, 0.95, 10))
+    avg_ps = _ap_table(counts)
+    y_np = y.detach().cpu().numpy() if torch.is_tensor(y) else np.asarray(y)
+    classes = np.sign(y_np[:, :, :, 5:].reshape(-1, 43).sum(axis=0))
+    return np.mean(avg_ps[classes > 0])

@@ -1,11 +1,17 @@
-"""Eval-mode forward wrappers with the reference's names (predict_fns.py:60-73 and the forward part of
-10-58).  Box decoding / drawing / cropping (cv2 post-processing, predict_fns.py:44-58) is out of scope."""
+"""Prediction with the reference's names (predict_fns.py:10-82): the eval forwards, and the two-stage chain detector ->
+box crops -> classifier -> combined y_hat with every step between the two forwards on the device (csrc/predict.hip).
+
+Resizing follows cv2.resize's INTER_LINEAR half-pixel convention (source coordinate (o + 0.5) * n_in / n_out - 0.5, neighbours
+clamped into the image or crop), interpolated in fp32.  cv2's 11-bit fixed-point rounding of the weights is NOT reproduced (cv2
+is not a dependency, so the difference could not be measured; it is expected to stay within one grey level).  Drawing boxes
+and writing JPEGs (plot.draw_boxes_vec's images) is out of scope: where the reference returns the drawn images, None is returned."""
 import os
 
 import numpy as np
 import torch
 
 from . import utils
+from ._lib import call
 
 
 def _restore(model, model_dir, params, restore_file):
@@ -41,3 +47,116 @@ def dark_forward(x, model, model_dir, params, restore_file, batch_size=32):
     """predict_fns.py:38-43: eval forward of the detector on already-resized NHWC images -> y_hat numpy (batched like class_pred)."""
     _restore(model, model_dir, params, restore_file)
     return _eval_forward_batched(x, model, params, batch_size)
+
+
+class PackedImages(object):
+    """A list of HWC uint8 images of different sizes as ONE device buffer (what `cy_crop_resize_u8` reads)."""
+
+    def __init__(self, images, device='cuda'):
+        arrs = []
+        for k, im in enumerate(images):
+            a = np.asarray(im)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise ValueError('image %d: expected a uint8 array [h, w, 3], got %s %s' % (k, a.dtype, a.shape))
+            arrs.append(np.ascontiguousarray(a))
+        if not arrs:
+            raise ValueError('no images')
+        self.n = len(arrs)
+        self.hw = np.array([a.shape[0:2] for a in arrs], dtype=np.int64)
+        sizes = np.array([a.size for a in arrs], dtype=np.int64)
+        self.nbytes = int(sizes.sum())
+        self.buf = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrs])).to(device)
+        self.off = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)).to(device)
+        self.hw32 = torch.from_numpy(self.hw.astype(np.int32)).to(device)
+
+    def crop_resize(self, box_img, rect, oh, ow, shift=0.0, scale=1.0, to_nchw=False):
+        """float32 device tensor [n, oh, ow, 3] ([n, 3, oh, ow] with to_nchw): (resized crop + shift) * scale."""
+        box_img = np.ascontiguousarray(np.asarray(box_img, dtype=np.int32).reshape(-1))
+        rect = np.ascontiguousarray(np.asarray(rect, dtype=np.int32).reshape(-1, 4))
+        n = len(box_img)
+        if len(rect) != n:
+            raise ValueError('%d image indices for %d rectangles' % (n, len(rect)))
+        dev = self.buf.device
+        out = torch.empty((n, 3, oh, ow) if to_nchw else (n, oh, ow, 3), dtype=torch.float32, device=dev)
+        if n == 0:
+            return out
+        args = torch.from_numpy(np.concatenate([rect.reshape(-1), box_img, [0]]).astype(np.int32)).to(dev)   # rect, index, error word
+        call('cy_crop_resize_u8', self.buf.data_ptr(), self.off.data_ptr(), self.hw32.data_ptr(), self.n, self.nbytes,
+             args.data_ptr() + 16 * n, args.data_ptr(), n, int(oh), int(ow), float(shift), float(scale), int(bool(to_nchw)),
+             out.data_ptr(), args.data_ptr() + 20 * n, torch.cuda.current_stream().cuda_stream)
+        bad = int(args[-1].item())
+        if bad:
+            raise ValueError('%d rectangle(s) are empty or reach outside their image' % bad)
+        return out
+
+    def resize(self, side, to_nchw=True):
+        rect = np.stack([np.zeros(self.n, np.int64), self.hw[:, 0], np.zeros(self.n, np.int64), self.hw[:, 1]], axis=1)
+        return self.crop_resize(np.arange(self.n), rect, side, side, 0.0, 1.0, to_nchw)
+
+
+def resize_images_device(images, side):
+    """predict_fns.py:38, `cv2.resize(image, (side, side))` of every image of a list of HWC uint8 arrays of different sizes, on the
+    device in one launch: float32 tensor [n, 3, side, side] with the raw 0..255 scale the reference feeds the detector."""
+    return PackedImages(images).resize(int(side), to_nchw=True)
+
+
+def _detect_and_crop(images, model, params, conf_th, batch_size, crop_side, shift, scale, to_nchw):
+    """Chunks of `batch_size` images: upload -> resize -> eval forward -> decode with the images' own sizes -> rectangles ->
+    crops, all but the rectangle rule (a few integers per box, in double on the host) on the device.
+    Returns (y_hat device [B,g,g,D], crops device, image_indices int64 numpy, boxes_xy float64 numpy)."""
+    n = len(images)
+    bs = max(int(batch_size) if batch_size else n, 1)
+    y_hats, crops, idxs, xys = [], [], [], []
+    model.eval()
+    with torch.no_grad():
+        for lo in range(0, n, bs):
+            packed = PackedImages(images[lo:lo + bs], params.device)
+            y_hat = model(packed.resize(int(params.darknet_input), to_nchw=True)).data
+            nbox, idx, xy, _ = utils.decode_boxes_device(y_hat, params, packed.hw, conf_th)
+            idx_np, xy_np = idx.cpu().numpy().astype(np.int64), xy.cpu().numpy()
+            try:
+                rect = utils.crop_rectangles(xy_np, idx_np, packed.hw)
+            except ValueError as e:
+                raise ValueError('images %d..%d: %s' % (lo, lo + packed.n - 1, e))
+            crops.append(packed.crop_resize(idx_np, rect, crop_side, crop_side, shift, scale, to_nchw))
+            y_hats.append(y_hat)
+            idxs.append(idx_np + lo)
+            xys.append(xy_np)
+    return torch.cat(y_hats, 0), torch.cat(crops, 0), np.concatenate(idxs), np.concatenate(xys, 0)
+
+
+def dark_pred(images, model, model_dir, params, restore_file, is_end=True, conf_th=0.5, y=None, batch_size=32):
+    """predict_fns.py:10-58.  images: list of HWC uint8 arrays of different sizes.  is_end=True: (y_hat, None) -- the reference
+    returns the images with the boxes drawn, which is out of scope (`y` only adds the ground-truth boxes to that drawing and is
+    ignored).  is_end=False: (y_hat, crops float32 numpy [n_boxes, ci, ci, 3] on the raw 0..255 scale like the reference,
+    image_indices [n_boxes], boxes_xy [n_boxes, 4] in pixels of the original images)."""
+    _restore(model, model_dir, params, restore_file)
+    ci = int(params.capsule_input)
+    y_hat, crops, idx, xy = _detect_and_crop(images, model, params, conf_th, batch_size, ci, 0.0, 1.0, False)
+    if is_end:
+        return y_hat.cpu().numpy(), None
+    return y_hat.cpu().numpy(), crops.cpu().numpy(), idx, xy
+
+
+def dark_class_pred(images, dark_model, dark_model_dir, dark_params, class_model, class_model_dir, class_params, restore_file,
+                    batch_size=32, conf_th=0.5):
+    """predict_fns.py:75-82: detector -> crop of every box -> classifier -> utils.combine_y_hat.  Returns (y_hat float64 numpy
+    [B, g, g, D + n_classes], None); the second value is the reference's drawn images (out of scope).  The crops are produced
+    already centred ((v - 128) / 128, utils.center_rgb) in the classifier's NCHW layout and never leave the device.  No box over
+    conf_th (new, optional; the reference's dark_pred default 0.5) is a valid outcome: the class part stays zero."""
+    _restore(dark_model, dark_model_dir, dark_params, restore_file)
+    _restore(class_model, class_model_dir, class_params, restore_file)
+    ci = int(dark_params.capsule_input)
+    dark_y_hat, crops, idx, xy = _detect_and_crop(images, dark_model, dark_params, conf_th, batch_size, ci, -128.0, 1.0 / 128.0, True)
+    n = int(crops.shape[0])
+    n_classes = int(class_params.n_classes)
+    class_model.eval()
+    bs = max(int(batch_size) if batch_size else n, 1)
+    scores = []
+    with torch.no_grad():
+        for lo in range(0, n, bs):
+            scores.append(class_model(crops[lo:lo + bs]).data.reshape(-1, n_classes))
+    class_y_hat = torch.cat(scores, 0) if scores else torch.zeros((0, n_classes), dtype=torch.float32, device=dark_y_hat.device)
+    image_hw = np.array([np.asarray(im).shape[0:2] for im in images])
+    y_hat = utils.combine_y_hat_device(image_hw, dark_y_hat, class_y_hat, idx, xy, dark_params)
+    return y_hat.cpu().numpy().astype(np.float64), None

@@ -32,3 +32,15 @@ def gtsdb_labels(n, g, n_classes, seed=1234, first=0):
             if n_classes > 0:
                 y[i, r, col, 5 + int(rng.integers(0, n_classes))] = 1.0
     return y
+
+
+def raw_images(n, seed=1234, first=0, min_side=48, max_side=160):
+    """A list of n uint8 HWC images of DIFFERENT sizes (min_side .. max_side per side), the shape of what predict mode reads
+    from the raw GTSDB folder (main.py:305-306): a smooth gradient plus noise.  Image i depends only on (seed, first + i)."""
+    out = []
+    for i in range(n):
+        rng = np.random.default_rng([seed, 13, first + i])
+        h, w = (int(v) for v in rng.integers(min_side, max_side + 1, 2))
+        ramp = np.add.outer(np.linspace(0, 96, h), np.linspace(0, 96, w))[:, :, None]
+        out.append(np.clip(ramp + rng.integers(0, 64, (h, w, 3)), 0, 255).astype(np.uint8))
+    return out

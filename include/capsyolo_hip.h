@@ -462,6 +462,40 @@ int cy_yolo_decode_boxes(const float* y, const long long* image_hw, double img_h
  * gets +2^20 per image with more than max_per_image boxes.  The caller zeroes out4. */
 int cy_detect_confusion(const int* gt_idx, const double* gt_xy, int n_gt, const int* pr_idx, const double* pr_xy, int n_pr,
                         int n_images, double iou_th, int max_per_image, int* out4, void* stream);
+/* ------------------------------------------------------------------ two-stage prediction (csrc/predict.hip)
+ * predict_fns.dark_class_pred (predict_fns.py:75-82) and metrics.detect_and_recog_mAP (metrics.py:284-339) on the device.
+ *
+ * Crop + bilinear resize + affine of many boxes in one launch: cv2.resize of whole images (predict_fns.py:38) and of box
+ * crops (plot.py:22, predict_fns.py:57).  imgs: packed uint8 HWC images of different sizes (imgs_bytes in all), image k at
+ * byte img_off[k] with img_hw[k] = (height, width).  Output b is the half-open rectangle rect[b] = (y0, y1, x0, x1) of image
+ * box_img[b], resized as a stand-alone image to OH x OW with the half-pixel convention of INTER_LINEAR
+ * (s = (o + 0.5) n_in / n_out - 0.5, neighbours clamped into the crop), interpolated in fp32 and written as
+ * (v + shift) * scale to out[n][OH][OW][3], or [n][3][OH][OW] with to_nchw.  cv2's 11-bit fixed-point weights are not
+ * reproduced.  A box whose image index or rectangle is out of range is zero-filled and counted in *err (caller-zeroed). */
+int cy_crop_resize_u8(const unsigned char* imgs, const long long* img_off, const int* img_hw, int n_images, long long imgs_bytes,
+                      const int* box_img, const int* rect, int n, int OH, int OW, float shift, float scale, int to_nchw,
+                      float* out, int* err, void* stream);
+/* utils.combine_y_hat (utils.py:336-351): y_hat[B][g][g][D + C] = the detector's output dark[B][g][g][D] followed by the class
+ * scores[n][C] of the box whose centre lies in the cell (zeros where there is none).  The cell is computed in double in the
+ * reference's order (utils.py:198-230) from box_xy[n][4] (pixels of the original image, image_hw[B][2] int64) and the
+ * detector's input side; of several boxes in one cell the highest index wins (winner[B g g]: caller-zeroed scratch).
+ * A box whose image index, row or column is out of range is counted in *err (caller-zeroed) and ignored. */
+int cy_combine_scores(const float* dark, const float* scores, const int* box_img, const double* box_xy, int n,
+                      const long long* image_hw, double side, int B, int g, int D, int C, int* winner, float* y_hat, int* err,
+                      void* stream);
+/* cy_yolo_decode_boxes that also returns conf[n], the stored confidence of every box */
+int cy_yolo_decode_boxes_conf(const float* y, const long long* image_hw, double img_h, double img_w, int B, int g, int nb, int C,
+                              float conf_th, int* count, int* image_idx, double* xy, int* cls, float* conf, int max_boxes,
+                              void* stream);
+/* metrics.single_img_confusion for K confidence thresholds x T IoU thresholds in one launch (the sweep of detect_AP and
+ * detect_and_recog_mAP).  gt / pr: boxes decoded ONCE at the lowest confidence threshold, with their confidences, sorted by
+ * the group key (image, or image * C + class) ascending; one block per group.  A box counts at threshold th iff
+ * (double)conf > th, and is hit iff additionally a partner with IoU > iou_t and (double)conf > th exists.  Adds, for every
+ * k and t, (TP, FP, FN) to out[k][group % C][t][0..2] (int32, caller-zeroed; C = 1 for the class-agnostic table).
+ * *err (caller-zeroed) counts malformed boxes and gets +2^20 per group with more than max_per_group boxes. */
+int cy_confusion_sweep(const int* gt_key, const double* gt_xy, const float* gt_conf, int n_gt, const int* pr_key,
+                       const double* pr_xy, const float* pr_conf, int n_pr, int n_groups, int C, const double* conf_ths, int K,
+                       const double* iou_ths, int T, int max_per_group, int* out, int* err, void* stream);
 /* torch.gather of the labelled capsule (models.py:122): backward=0: out[B][D] = caps[b][y[b]][:];
  * backward=1: caps is d(out) [B][D], out = d(caps) [B][C][D] (zero off the labelled capsule) */
 int cy_pick_capsule(const float* caps, const long long* y, float* out, int B, int C, int D, int backward, void* stream);

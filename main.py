@@ -12,6 +12,9 @@ keys, same registry shape ``name -> (ModelCls, loss_fn, predict_fn, metric)`` (m
   --fix_ckpt_dir    save checkpoints into model_dir, where --restore looks for them
   params.json keys ``n_iter`` (routing iterations, default 3), ``sync_bn`` (data parallel only)
   --model darkcapsule2 | darkcapsule3   the reference's unwired variants with their losses (models.py:271-337, 403-463)
+``--mode predict --model darknet_d|darknet_r --combine cnn|capsule --restore last|best`` runs the two-stage chain
+(predict_fns.dark_class_pred) and writes detect_and_recog_mAP / detect_and_recog_acc to combine-<name>_metric_output.txt
+(main.py:329-356); drawing the boxes and the detect-only / class-only predict branches are not wired (see predict()).
 Data-parallel: launch with ``python -m torch.distributed.run --nproc-per-node N main.py ...``; every rank takes
 its equal shard of each global batch, gradients are averaged with one RCCL all-reduce per step, epoch losses are
 averaged over the ranks before the LR scheduler sees them, metrics run on the gathered predictions, rank 0 writes.
@@ -35,7 +38,7 @@ from capsyolo_amd.loss_fns import (capsule_loss, cnn_loss, dark_loss, darkcapsul
                                    darkcapsule_loss)
 from capsyolo_amd.models import CapsuleNet, ConvNet, DarkCapsuleNet, DarkCapsuleNet2, DarkCapsuleNet3, DarkNet  # noqa: E402
 from capsyolo_amd.optim import Adam  # noqa: E402
-from capsyolo_amd.predict_fns import class_pred, dark_forward  # noqa: E402
+from capsyolo_amd.predict_fns import class_pred, dark_class_pred, dark_forward  # noqa: E402
 
 parser = argparse.ArgumentParser()
 parser.add_argument('--model', default='cnn', help=' | '.join(config.model_names))
@@ -46,7 +49,7 @@ parser.add_argument('--lr', type=float, default=1e-3, help='learning rate')
 parser.add_argument('--dropout', type=float, default=-1, help='dropout rate')
 parser.add_argument('--train_frac', type=float, default=1, help='fraction of train data')
 parser.add_argument('--restore', default=None, help="last | best")
-parser.add_argument('--combine', default=None, help="darknet_r | darknet_d")
+parser.add_argument('--combine', default=None, help="cnn | capsule: the classifier behind --model darknet_d|darknet_r in predict mode")
 parser.add_argument('--recon', help='if use reconstruction loss', action='store_false')
 parser.add_argument('--recon_coef', default=5e-4, help='reconstruction coefficient')
 parser.add_argument('--eval_every', default=1, type=int, help='evaluate metric every # epochs')
@@ -74,6 +77,9 @@ model_loss_predict = {
     'darkcapsule2': (DarkCapsuleNet2, darkcapsule2_loss, None, None),
     'darkcapsule3': (DarkCapsuleNet3, darkcapsule3_loss, None, None),
 }
+# what predict mode reports for detector + classifier (main.py:342-346): name -> metric(y, y_hat, params), in this order
+combine_metrics = {'detect_and_recog_mAP': metrics.detect_and_recog_mAP,          # sets params.n_classes = 43 (metrics.py:285)
+                   'detect_and_recog_acc': metrics.detect_and_recog_acc}
 
 
 def _batches(x, y, batch_size):
@@ -313,6 +319,40 @@ def synthetic_data(args, params):
     return x_tr, y_tr, x_ev, y_ev
 
 
+def predict(args, model, model_dir, data_dir, params):
+    """main.py:293-356, the combined branch: `--model darknet_d|darknet_r --combine cnn|capsule --restore last|best` runs
+    dark_class_pred and writes detect_and_recog_mAP / detect_and_recog_acc to <model_dir>/combine-<name>_metric_output.txt.
+    The images are a list of raw HWC uint8 arrays: `--synthetic N` draws them (with labels) from synth, otherwise they come from
+    data_dir/test_images.npy (an object array) next to data_dir/test.p.  The classifier's directory is config.model_dir[--combine]
+    or, with --model_dir, its sibling <model_dir>/../<name>.  Nothing is drawn and no cv2 is needed."""
+    if args.restore is None:
+        raise SystemExit('Must give restore file last/best')                           # main.py:294-296
+    if args.model not in ('darknet_d', 'darknet_r') or args.combine not in ('cnn', 'capsule'):
+        raise SystemExit('predict mode runs the combined chain only: --model darknet_d|darknet_r --combine cnn|capsule; the '
+                         'eval-mode forwards of the other branches are capsyolo_amd.predict_fns.class_pred / dark_pred')
+    class_model_dir = config.model_dir[args.combine] if args.model_dir is None else \
+        os.path.join(os.path.dirname(os.path.abspath(model_dir)), args.combine)
+    class_args = argparse.Namespace(**dict(vars(args), model=args.combine))
+    class_params = load_params(class_model_dir, class_args)
+    class_model = model_loss_predict[args.combine][0](class_params).to(device=class_params.device)
+    if args.synthetic:
+        x = synth.raw_images(args.synthetic)
+        y = synth.gtsdb_labels(args.synthetic, params.n_grid, 43)
+    else:
+        import pickle
+        with open(data_dir + config.te_d, 'rb') as f:
+            _, y = pickle.load(f)
+        x = list(np.load(data_dir + '/test_images.npy', allow_pickle=True))
+    y_hat, _ = dark_class_pred(x, model, model_dir, params, class_model, class_model_dir, class_params, args.restore,
+                               batch_size=params.batch_size)
+    metric_out = {name: fn(y, y_hat, params) for name, fn in combine_metrics.items()}
+    with open(os.path.join(model_dir, 'combine-{}_metric_output.txt'.format(args.combine)), 'w') as text_file:
+        for k, v in metric_out.items():
+            text_file.write("{}:{}, ".format(k, v))
+            print("{}:{}, ".format(k, v))
+    return metric_out
+
+
 def main(argv=None):
     args = parser.parse_args(argv)
     if args.model not in config.model_names:
@@ -360,8 +400,7 @@ def main(argv=None):
             data = utils.load_data(data_dir, False, npy=args.npy)
         return train_and_evaluate(model, optimizer, loss_fn, metric, params, data, model_dir, restore_file=args.restore)
     if args.mode == 'predict':
-        raise SystemExit('predict mode needs the raw GTSDB images and cv2 post-processing (out of scope, SURVEY section 2); '
-                         'the eval-mode forward is capsyolo_amd.predict_fns.class_pred / dark_forward')
+        return predict(args, model, model_dir, data_dir, params)
 
 
 if __name__ == '__main__':
