@@ -173,6 +173,7 @@ _RET = {
     'cy_routing_general_fwd_ws_floats': (_L, [C.POINTER(RoutingFwd)]),
     'cy_routing_specialised': (_I, [C.POINTER(RoutingFwd)]),
     'cy_conv_gemm_bf16_plan': (_I, [C.POINTER(ConvGemm), _I, _I, C.POINTER(C.c_int)]),
+    'cy_routing_plan': (_I, [C.POINTER(RoutingFwd), _I, _I, C.POINTER(_L), _I]),
 }
 EXPORTS = sorted(list(_SIGS) + list(_RET))
 ABI_VERSION = 5     # what the signatures above were written against (include/capsyolo_hip.h, csrc/error.cpp)

@@ -56,6 +56,44 @@ int cyi_mfma_launch(const cyi_rows_args_t* a, int nch, int Dout, hipStream_t s);
 
 int cyi_caps_bwd_launch(const cy_routing_bwd_t* a, const float* cdb, hipStream_t s);   // routing_caps.hip: du and dW (cdb: saved couplings or NULL)
 
+// ---- the routing plan: everything the host decides about one routing call (routing.hip cyi_routing_plan, pure host arithmetic).
+// The launchers of routing.hip and routing_general.hip take their launch numbers and every workspace pointer from it, the
+// _ws_floats queries return its `total`, cy_routing_plan exports it.  DESIGN section 4 has the region tables per path.
+enum { CYI_ROUTE_C1, CYI_ROUTE_ROWS_FUSED, CYI_ROUTE_ROWS_PHASED, CYI_ROUTE_GENERAL, CYI_ROUTE_MFMA_FUSED, CYI_ROUTE_MFMA_PHASED };
+enum { CYI_WS_DS_ALL, CYI_WS_V, CYI_WS_SA, CYI_WS_SLABS, CYI_WS_TAIL, CYI_WS_W, CYI_WS_CDB, CYI_WS_DUH, CYI_WS_DWS, CYI_WS_N };
+enum { CYI_RG_MAX_DIN = 16, CYI_RG_MAX_DOUT = 64, CYI_RG_MAX_C = 256 };     // the envelope of the general kernels
+typedef struct cyi_routing_plan_t {
+  int path;                    // CYI_ROUTE_*
+  cyi_rows_plan_t rows;        // rows / mfma paths: the plan of routing_rows.hip
+  struct cyi_rg_plan_t {       // general path: the plan of routing_general.hip (filled by cyi_general_plan)
+    int DP, CW, Cp, nrb;
+    int nch, ic;               // forward / dV passes: chunks of input capsules
+    int ich, nich, ipb;        // du_hat pass: input capsules per staged chunk, number of chunks, per block
+    int rs, rps;               // dW contraction: row splits, rows per split
+    long long plane, wp;       // R*C*DP, floats of the packed W
+  } rg;
+  int row_blocks, nch, ic;     // what the pass launches use: blocks along the rows (c1: persistent blocks), chunks of input capsules, capsules per chunk
+  int cdb;                     // fused rows backward: the row part saves c^t, db^t for routing_caps.hip
+  // workspace regions in floats, in the order they lie in (len 0: the call has no such region).  V is the forward's running sum or
+  // the backward's V_all; TAIL: the 4 floats routing_caps.hip may read past ds_all / V_all (it reads whole 16-byte pieces).
+  int nreg, order[CYI_WS_N];
+  long long off[CYI_WS_N], len[CYI_WS_N], total;
+} cyi_routing_plan_t;
+// appends a region at the end of the workspace (align: on a 16-byte boundary)
+static inline void cyi_ws_add(cyi_routing_plan_t* p, int id, long long len, int align) {
+  p->off[id] = align ? (p->total + 3) & ~3ll : p->total;
+  p->len[id] = len;
+  p->order[p->nreg++] = id;
+  p->total = p->off[id] + len;
+}
+static inline float* cyi_ws_at(float* ws, const cyi_routing_plan_t* p, int id) { return p->len[id] ? ws + p->off[id] : nullptr; }
+// 0, or CY_EINVAL with the message (prefixed by fn) for a shape no path takes.  force_general: the general kernels also where the specialised ones apply.
+int cyi_routing_plan(const char* fn, int R, int N, int C, int Din, int Dout, int n_iter, int g, int B, int backward, int force_general,
+                     cyi_routing_plan_t* p);
+void cyi_general_plan(int R, int N, int C, int Din, int Dout, int n_iter, int backward, cyi_routing_plan_t* p);   // routing_general.hip: p->rg, launch numbers, regions
+int cyi_general_fwd(const cy_routing_fwd_t* a, const cyi_routing_plan_t* p, hipStream_t s);
+int cyi_general_bwd(const cy_routing_bwd_t* a, const cyi_routing_plan_t* p, hipStream_t s);
+
 #ifdef __HIPCC__
 // offset (in floats) of the 8-vector of input capsule i of capsule row `row`: contiguous rows [R][N][8], or (g != 0)
 // the DarkCapsuleNet cell gather (models.py:393-398) read in place from the NHWC feature map [B][4g][4g][256]

@@ -435,218 +435,238 @@ inline int c1_blocks() {                   // CY_C1_BLOCKS: developer knob (512 
   static int v = [] { const char* e = getenv("CY_C1_BLOCKS"); const int k = e ? atoi(e) : 0; return (k >= 64 && k <= 1024) ? k : C1_BLOCKS_DEFAULT; }();
   return v;
 }
-#define C1_BLOCKS c1_blocks()
-bool fast_c1(int N, int C, int Din, int Dout) { return C == 1 && N * Din == 4096 && Dout == 5; }
 
 cyi_rows_args_t rows_args(const float* u, const float* Wp, int R, int N, int C, int n_iter, int g, int B) {
   cyi_rows_args_t r{};
   r.u = u; r.Wp = Wp; r.R = R; r.N = N; r.C = C; r.n_iter = n_iter; r.g = g; r.B = B;
   return r;
 }
-inline long long align4(long long n) { return (n + 3) & ~3ll; }
 
-// CY_ROUTING_MFMA=1: the forward of C > 1 heads on routing_mfma.hip (u_hat on v_mfma_f32_16x16x4_f32) instead of the vector kernel
-// of routing_rows.hip.  OFF by default: measured slower (round 3, tools/ab_routing_mfma.py: DarkCapsuleNet3 head 5.67 ms against
-// 3.78 ms, CapsuleNet head 0.178 against 0.130 ms) -- with u_hat on the matrix cores the step is bound by what stays on the vector
-// pipe next to them (logits, softmax, weighted sums, accumulator moves: 464 vector instructions per input capsule and wave against 36
-// MFMAs) and the 16-row tiles need two rounds on 256 CUs; DESIGN section 4 has the census and what it would take.
-inline bool mfma_enabled() {
-  const char* e = getenv("CY_ROUTING_MFMA");
-  return e && e[0] == '1';
-}
-inline long long fwd_wp_floats(int N, int C, int Dout) {          // the larger of the two packed W images
-  const long long a = cyi_rows_wp_floats(N, C, Dout), b = cyi_mfma_ok(C, Dout) ? cyi_mfma_wp_floats(N, C, Dout) : 0;
-  return a > b ? a : b;
-}
-// chunks of input capsules per row tile of the MFMA kernel's phased plan (few rows): about one block per CU, never more chunks
-// than the vector plan has (the workspace holds p.nch slabs)
-inline void mfma_chunks(int R, int N, const cyi_rows_plan_t& p, int* nch, int* ic) {
-  const int row_tiles = (R + 15) / 16;
-  int n = 256 / row_tiles;
-  if (n > p.nch) n = p.nch;
-  if (n > (N + 1) / 2) n = (N + 1) / 2;
-  if (n < 1) n = 1;
-  *ic = (N + n - 1) / n;
-  *nch = (N + *ic - 1) / *ic;
-}
-
-// workspace of the forward: [packed W image][phased plans: V_t, partial-sum slabs]
 template <int DOUT>
-int launch_fwd(const cy_routing_fwd_t* a, hipStream_t s) {
-  cyi_rows_plan_t p;
-  cyi_rows_plan(a->R, a->N, a->C, DOUT, 0, &p);
+int launch_fwd(const cy_routing_fwd_t* a, const cyi_routing_plan_t& p, hipStream_t s) {
   if (a->ws == nullptr) return cy_set_error(CY_EINVAL, "cy_routing_fwd: this shape needs the workspace (ws) of cy_routing_fwd_ws_floats()");
-  float* Wp = a->ws;
-  const bool mfma = mfma_enabled() && cyi_mfma_ok(a->C, DOUT);
+  float* Wp = cyi_ws_at(a->ws, &p, CYI_WS_W);
+  const bool mfma = p.path == CYI_ROUTE_MFMA_FUSED || p.path == CYI_ROUTE_MFMA_PHASED;
   int rc = mfma ? cyi_mfma_pack_w(a->W, Wp, a->N, a->C, DOUT, s) : cyi_rows_pack_w(a->W, Wp, a->N, a->C, DOUT, s);
   if (rc) return rc;
   cyi_rows_args_t r = rows_args(a->u, Wp, a->R, a->N, a->C, a->n_iter, a->gather_g, a->gather_B);
-  r.s_hist = a->s_hist; r.v_out = a->v_out;
-  if (!p.phased) {
-    r.fused = 1; r.ic = a->N;
-    return mfma ? cyi_mfma_launch(&r, 1, DOUT, s) : cyi_rows_launch(0, &r, &p, DOUT, s);
+  r.s_hist = a->s_hist; r.v_out = a->v_out; r.ic = p.ic;
+  if (p.path == CYI_ROUTE_ROWS_FUSED || p.path == CYI_ROUTE_MFMA_FUSED) {
+    r.fused = 1;
+    return mfma ? cyi_mfma_launch(&r, 1, DOUT, s) : cyi_rows_launch(0, &r, &p.rows, DOUT, s);
   }
   const long long plane = (long long)a->R * a->C * DOUT;
-  float* V = a->ws + fwd_wp_floats(a->N, a->C, DOUT);
-  float* slab = V + align4(plane);
-  int nch = p.nch, ic = p.ic;
-  if (mfma) mfma_chunks(a->R, a->N, p, &nch, &ic);
+  float* V = cyi_ws_at(a->ws, &p, CYI_WS_V);
+  float* slab = cyi_ws_at(a->ws, &p, CYI_WS_SLABS);
   for (int it = 0; it < a->n_iter; ++it) {
-    r.fused = 0; r.it = it; r.ic = ic; r.V = it > 0 ? V : nullptr; r.slab = slab;
-    rc = mfma ? cyi_mfma_launch(&r, nch, DOUT, s) : cyi_rows_launch(0, &r, &p, DOUT, s);
+    r.fused = 0; r.it = it; r.V = it > 0 ? V : nullptr; r.slab = slab;
+    rc = mfma ? cyi_mfma_launch(&r, p.nch, DOUT, s) : cyi_rows_launch(0, &r, &p.rows, DOUT, s);
     if (rc) return rc;
     constexpr int OPB = (64 / DOUT) * DOUT;
-    slab_fin_kernel<DOUT, false><<<(unsigned)cy_ceil_div(plane, OPB), 1024, 0, s>>>(slab, nch, plane, a->s_hist + (long long)it * plane, V, a->v_out,
+    slab_fin_kernel<DOUT, false><<<(unsigned)cy_ceil_div(plane, OPB), 1024, 0, s>>>(slab, p.nch, plane, a->s_hist + (long long)it * plane, V, a->v_out,
                                                                                      nullptr, nullptr, nullptr, a->C, it, it == a->n_iter - 1,
                                                                                      a->gather_g, a->gather_B);
   }
   return 0;
 }
-// workspace of the backward: [ds_all][V_all] (read by routing_caps.hip) [phased plans: SA, A_t, slabs] [+4] [packed W image]
-inline long long bwd_ws_head(const cy_routing_bwd_t* a, const cyi_rows_plan_t& p) {
-  const long long plane = (long long)a->R * a->C * a->Dout;
-  return align4(2ll * a->n_iter * plane + (p.phased ? (2ll + p.nch) * plane : 0) + 4);   // + 4: routing_caps.hip reads whole 16-byte pieces
-}
 template <int DOUT>
-int launch_bwd(const cy_routing_bwd_t* a, hipStream_t s) {
-  cyi_rows_plan_t p;
-  cyi_rows_plan(a->R, a->N, a->C, DOUT, 1, &p);
+int launch_bwd(const cy_routing_bwd_t* a, const cyi_routing_plan_t& p, hipStream_t s) {
   const long long plane = (long long)a->R * a->C * DOUT;
-  float* Wp = a->ws + bwd_ws_head(a, p);
+  float* Wp = cyi_ws_at(a->ws, &p, CYI_WS_W);
   int rc = cyi_rows_pack_w(a->W, Wp, a->N, a->C, DOUT, s);
   if (rc) return rc;
   cyi_rows_args_t r = rows_args(a->u, Wp, a->R, a->N, a->C, a->n_iter, a->gather_g, a->gather_B);
-  float* ds_all = a->ws;
-  float* V_all = a->ws + (long long)a->n_iter * plane;
-  float* cdb = nullptr;                             // fused plans (many rows): c^t, db^t of every (t >= 1, row, i, j), behind the W image
-  if (!p.phased && a->n_iter > 1 && DOUT <= 21) cdb = Wp + cyi_rows_wp_floats(a->N, a->C, DOUT);   // (Dout = 48: dW alone overflows the registers)
-  if (!p.phased) {
-    r.fused = 1; r.ic = a->N; r.s_hist = const_cast<float*>(a->s_hist); r.dv = a->dv; r.ds_all = ds_all; r.V_all = V_all;
+  float* ds_all = cyi_ws_at(a->ws, &p, CYI_WS_DS_ALL);
+  float* V_all = cyi_ws_at(a->ws, &p, CYI_WS_V);
+  float* cdb = cyi_ws_at(a->ws, &p, CYI_WS_CDB);     // fused plans (many rows): c^t, db^t of every (t >= 1, row, i, j); NULL when not saved
+  r.ic = p.ic;
+  if (p.path == CYI_ROUTE_ROWS_FUSED) {
+    r.fused = 1; r.s_hist = const_cast<float*>(a->s_hist); r.dv = a->dv; r.ds_all = ds_all; r.V_all = V_all;
     r.cdb = cdb;
-    rc = cyi_rows_launch(1, &r, &p, DOUT, s);
+    rc = cyi_rows_launch(1, &r, &p.rows, DOUT, s);
     if (rc) return rc;
   } else {
-    float* SA = a->ws + 2ll * a->n_iter * plane;
-    float* At = SA + plane;
-    float* slab = At + plane;
+    float* SA = cyi_ws_at(a->ws, &p, CYI_WS_SA);
+    float* slab = cyi_ws_at(a->ws, &p, CYI_WS_SLABS);
     const int fin_blocks = (int)cy_ceil_div((long long)a->R * a->C, 128);
     routing_bwd_prep_kernel<DOUT><<<fin_blocks, 128, 0, s>>>(a->s_hist, a->dv, ds_all, V_all, SA, a->R, a->C, a->n_iter,
                                                              a->gather_g, a->gather_B);
     for (int t = a->n_iter - 1; t >= 1; --t) {
-      r.fused = 0; r.it = t; r.ic = p.ic; r.V = V_all + (long long)t * plane; r.ds = ds_all + (long long)t * plane; r.slab = slab;
-      rc = cyi_rows_launch(1, &r, &p, DOUT, s);
+      r.fused = 0; r.it = t; r.V = V_all + (long long)t * plane; r.ds = ds_all + (long long)t * plane; r.slab = slab;
+      rc = cyi_rows_launch(1, &r, &p.rows, DOUT, s);
       if (rc) return rc;
       constexpr int OPB = (64 / DOUT) * DOUT;
       slab_fin_kernel<DOUT, true><<<(unsigned)cy_ceil_div(plane, OPB), 1024, 0, s>>>(slab, p.nch, plane, nullptr, nullptr, nullptr,
                                                                                       a->s_hist + (long long)(t - 1) * plane,
                                                                                       ds_all + (long long)(t - 1) * plane, SA, a->C, t, 0, 0, 1);
-      (void)At;
     }
   }
   return cyi_caps_bwd_launch(a, cdb, s);
 }
 
-// what today's kernels take: the C == 1 stream, or Din = 8, Dout in {5, 16, 21, 48}, C <= 64
-bool specialised_shape(int N, int C, int Din, int Dout) {
-  return fast_c1(N, C, Din, Dout) || (Din == 8 && (Dout == 5 || Dout == 16 || Dout == 21 || Dout == 48) && C <= 64);
-}
-bool gather_ok(int R, int N, int Din, int g, int B) { return g == 0 || (N == 512 && Din == 8 && B > 0 && R == g * g * B); }
+}  // namespace
 
-int check_shape(const char* fn, int R, int N, int C, int Din, int Dout, int n_iter, int g, int B) {
-  if (R <= 0 || N <= 0 || C <= 0 || n_iter <= 0) return cy_set_error(CY_EINVAL, "%s: non-positive dimension", fn);
-  if (!gather_ok(R, N, Din, g, B))
-    return cy_set_error(CY_EINVAL, "%s: cell gather needs N=512, Din=8, R=g*g*B (got N=%d Din=%d R=%d g=%d B=%d)", fn, N,
-                        Din, R, g, B);
+// Which path takes the call, with which launch numbers, and where every buffer lies in the workspace.
+//  * c1: C == 1 with N * Din == 4096, Dout == 5, the stream kernels;  * rows_fused / rows_phased: Din == 8, Dout in {5, 16, 21, 48},
+//    C <= 64 on routing_rows.hip (+ routing_caps.hip backward), phased when the rows alone cannot fill the chip;  * mfma_*: the same
+//    forward on routing_mfma.hip, opt-in;  * general: every other shape of the envelope, or any shape of it with force_general.
+int cyi_routing_plan(const char* fn, int R, int N, int C, int Din, int Dout, int n_iter, int g, int B, int backward, int force_general,
+                     cyi_routing_plan_t* p) {
+  if (R <= 0 || N <= 0 || C <= 0 || Din <= 0 || Dout <= 0 || n_iter <= 0) return cy_set_error(CY_EINVAL, "%s: non-positive dimension", fn);
+  if (g != 0 && (N != 512 || Din != 8 || B <= 0 || R != g * g * B))
+    return cy_set_error(CY_EINVAL, "%s: cell gather needs N=512, Din=8, R=g*g*B (got N=%d Din=%d R=%d g=%d B=%d)", fn, N, Din, R, g, B);
+  *p = cyi_routing_plan_t{};
+  const bool c1 = C == 1 && N * Din == 4096 && Dout == 5;
+  const bool rows = Din == 8 && (Dout == 5 || Dout == 16 || Dout == 21 || Dout == 48) && C <= 64;
+  if (force_general || !(c1 || rows)) {
+    if (Din > CYI_RG_MAX_DIN || Dout > CYI_RG_MAX_DOUT || C > CYI_RG_MAX_C)
+      return cy_set_error(CY_EINVAL, "%s: capsule shape C=%d Din=%d Dout=%d outside the routing envelope (Din 1..16, Dout 1..64, C 1..256)",
+                          fn, C, Din, Dout);
+    p->path = CYI_ROUTE_GENERAL;
+    cyi_general_plan(R, N, C, Din, Dout, n_iter, backward, p);
+    return 0;
+  }
+  if (c1) {      // forward: no workspace; backward: one dW slab per persistent block
+    p->path = CYI_ROUTE_C1;
+    p->row_blocks = R < c1_blocks() ? R : c1_blocks();
+    if (!backward) while ((R + p->row_blocks - 1) / p->row_blocks + 1 > C1_MAXROWS) p->row_blocks *= 2;   // keep rows per block within the slot table
+    p->nch = 1; p->ic = N;
+    if (backward) cyi_ws_add(p, CYI_WS_SLABS, (long long)c1_blocks() * 4096 * 5, 0);
+    return 0;
+  }
+  cyi_rows_plan(R, N, C, Dout, backward, &p->rows);
+  const bool phased = p->rows.phased;
+  const long long plane = (long long)R * C * Dout, wp = cyi_rows_wp_floats(N, C, Dout);
+  p->path = phased ? CYI_ROUTE_ROWS_PHASED : CYI_ROUTE_ROWS_FUSED;
+  p->row_blocks = p->rows.row_blocks; p->nch = p->rows.nch; p->ic = p->rows.ic;
+  if (backward) {
+    cyi_ws_add(p, CYI_WS_DS_ALL, n_iter * plane, 0);      // routing_caps.hip reads ds_all at ws + 0 and V_all at ws + n_iter * plane
+    cyi_ws_add(p, CYI_WS_V, n_iter * plane, 0);
+    if (phased) {
+      cyi_ws_add(p, CYI_WS_SA, plane, 0);
+      cyi_ws_add(p, CYI_WS_SLABS, p->nch * plane, 0);
+    }
+    cyi_ws_add(p, CYI_WS_TAIL, 4, 0);
+    cyi_ws_add(p, CYI_WS_W, wp, 1);
+    p->cdb = !phased && n_iter > 1 && Dout <= 21;         // (Dout = 48: dW alone overflows the registers)
+    if (p->cdb) cyi_ws_add(p, CYI_WS_CDB, 2ll * (n_iter - 1) * R * N * C, 0);
+    return 0;
+  }
+  // CY_ROUTING_MFMA=1: the forward of C > 1 heads on routing_mfma.hip (u_hat on v_mfma_f32_16x16x4_f32) instead of the vector kernel
+  // of routing_rows.hip.  OFF by default: measured slower (round 3, tools/ab_routing_mfma.py: DarkCapsuleNet3 head 5.67 ms against
+  // 3.78 ms, CapsuleNet head 0.178 against 0.130 ms) -- with u_hat on the matrix cores the step is bound by what stays on the vector
+  // pipe next to them (logits, softmax, weighted sums, accumulator moves: 464 vector instructions per input capsule and wave against 36
+  // MFMAs) and the 16-row tiles need two rounds on 256 CUs; DESIGN section 4 has the census and what it would take.
+  const char* e = getenv("CY_ROUTING_MFMA");
+  const long long wpm = cyi_mfma_ok(C, Dout) ? cyi_mfma_wp_floats(N, C, Dout) : 0;
+  if (e && e[0] == '1' && cyi_mfma_ok(C, Dout)) {
+    p->path = phased ? CYI_ROUTE_MFMA_PHASED : CYI_ROUTE_MFMA_FUSED;
+    p->row_blocks = (R + 15) / 16;
+    if (phased) {      // chunks per 16-row tile: about one block per CU, never more chunks than the vector plan has (the workspace holds rows.nch slabs)
+      int n = 256 / p->row_blocks;
+      if (n > p->rows.nch) n = p->rows.nch;
+      if (n > (N + 1) / 2) n = (N + 1) / 2;
+      if (n < 1) n = 1;
+      p->ic = (N + n - 1) / n;
+      p->nch = (N + p->ic - 1) / p->ic;
+    }
+  }
+  cyi_ws_add(p, CYI_WS_W, wp > wpm ? wp : wpm, 1);       // the larger of the two packed W images wherever the MFMA kernel could take the shape
+  if (phased) {
+    cyi_ws_add(p, CYI_WS_V, plane, 1);
+    cyi_ws_add(p, CYI_WS_SLABS, p->rows.nch * plane, 1);
+  }
   return 0;
 }
 
-}  // namespace
+#define CY_PLAN_OF(fn, a, backward, p) \
+  cyi_routing_plan(fn, (a)->R, (a)->N, (a)->C, (a)->Din, (a)->Dout, (a)->n_iter, (a)->gather_g, (a)->gather_B, backward, 0, p)
 
 extern "C" int cy_routing_fwd(const cy_routing_fwd_t* a, void* stream) {
   CY_REQUIRE(a && a->u && a->W && a->v_out && a->s_hist, "cy_routing_fwd: null pointer");
-  int rc = check_shape("cy_routing_fwd", a->R, a->N, a->C, a->Din, a->Dout, a->n_iter, a->gather_g, a->gather_B);
+  cyi_routing_plan_t p;
+  int rc = CY_PLAN_OF("cy_routing_fwd", a, 0, &p);
   if (rc) return rc;
-  if (!specialised_shape(a->N, a->C, a->Din, a->Dout)) return cy_routing_general_fwd(a, stream);
   hipStream_t s = (hipStream_t)stream;
-  if (fast_c1(a->N, a->C, a->Din, a->Dout)) {
-    int blocks = a->R < C1_BLOCKS ? a->R : C1_BLOCKS;
-    while ((a->R + blocks - 1) / blocks + 1 > C1_MAXROWS) blocks *= 2;   // keep rows per block within the slot table
+  if (p.path == CYI_ROUTE_GENERAL) return cyi_general_fwd(a, &p, s);
+  if (p.path == CYI_ROUTE_C1) {
     float* s_last = a->s_hist + (long long)(a->n_iter - 1) * a->R * 5;
     if (a->gather_g)
-      caps1_fwd_kernel<5, true><<<blocks, C1_THREADS, 0, s>>>(a->u, a->W, a->v_out, s_last, a->R, a->gather_g, a->gather_B);
+      caps1_fwd_kernel<5, true><<<p.row_blocks, C1_THREADS, 0, s>>>(a->u, a->W, a->v_out, s_last, a->R, a->gather_g, a->gather_B);
     else
-      caps1_fwd_kernel<5, false><<<blocks, C1_THREADS, 0, s>>>(a->u, a->W, a->v_out, s_last, a->R, 0, 1);
-  } else if (a->Dout == 5) rc = launch_fwd<5>(a, s);
-  else if (a->Dout == 16) rc = launch_fwd<16>(a, s);
-  else if (a->Dout == 21) rc = launch_fwd<21>(a, s);
-  else rc = launch_fwd<48>(a, s);
+      caps1_fwd_kernel<5, false><<<p.row_blocks, C1_THREADS, 0, s>>>(a->u, a->W, a->v_out, s_last, a->R, 0, 1);
+  } else if (a->Dout == 5) rc = launch_fwd<5>(a, p, s);
+  else if (a->Dout == 16) rc = launch_fwd<16>(a, p, s);
+  else if (a->Dout == 21) rc = launch_fwd<21>(a, p, s);
+  else rc = launch_fwd<48>(a, p, s);
   if (rc) return rc;
   CY_LAUNCH_CHECK("cy_routing_fwd");
   return 0;
 }
 
 extern "C" int cy_routing_specialised(const cy_routing_fwd_t* a) {
-  return a && a->R > 0 && a->N > 0 && a->C > 0 && a->n_iter > 0 && gather_ok(a->R, a->N, a->Din, a->gather_g, a->gather_B) &&
-         specialised_shape(a->N, a->C, a->Din, a->Dout);
+  cyi_routing_plan_t p;
+  return a && CY_PLAN_OF("cy_routing_specialised", a, 0, &p) == 0 && p.path != CYI_ROUTE_GENERAL;
 }
 
-// other shapes: the general kernels' workspace (0 outside their envelope: cy_routing_fwd then reports the shape)
+// 0 for a shape no path takes: cy_routing_fwd / cy_routing_bwd then report it
 extern "C" long long cy_routing_fwd_ws_floats(const cy_routing_fwd_t* a) {
-  if (!a || fast_c1(a->N, a->C, a->Din, a->Dout)) return 0;
-  if (!specialised_shape(a->N, a->C, a->Din, a->Dout)) {
-    const long long n = cy_routing_general_fwd_ws_floats(a);
-    return n > 0 ? n : 0;
-  }
-  cyi_rows_plan_t p;
-  cyi_rows_plan(a->R, a->N, a->C, a->Dout, 0, &p);
-  const long long plane = (long long)a->R * a->C * a->Dout;
-  return fwd_wp_floats(a->N, a->C, a->Dout) + (p.phased ? align4(plane) + p.nch * plane : 0);
+  cyi_routing_plan_t p;
+  return a && CY_PLAN_OF("cy_routing_fwd_ws_floats", a, 0, &p) == 0 ? p.total : 0;
+}
+extern "C" long long cy_routing_bwd_ws_floats(const cy_routing_bwd_t* a) {
+  cyi_routing_plan_t p;
+  return a && CY_PLAN_OF("cy_routing_bwd_ws_floats", a, 1, &p) == 0 ? p.total : 0;
 }
 
-extern "C" long long cy_routing_bwd_ws_floats(const cy_routing_bwd_t* a) {
-  if (!a) return 0;
-  if (fast_c1(a->N, a->C, a->Din, a->Dout)) return (long long)C1_BLOCKS * 4096 * 5;
-  if (!specialised_shape(a->N, a->C, a->Din, a->Dout)) {
-    const long long n = cy_routing_general_bwd_ws_floats(a);
-    return n > 0 ? n : 0;
+// out = {path, row_blocks, nch, ic, cdb, total, number of regions, then (region id, offset, length) per region in workspace order}
+extern "C" int cy_routing_plan(const cy_routing_fwd_t* a, int backward, int force_general, long long* out, int n) {
+  CY_REQUIRE(a && out, "cy_routing_plan: null pointer");
+  cyi_routing_plan_t p;
+  int rc = cyi_routing_plan("cy_routing_plan", a->R, a->N, a->C, a->Din, a->Dout, a->n_iter, a->gather_g, a->gather_B, backward, force_general, &p);
+  if (rc) return rc;
+  CY_REQUIRE(n >= 7 + 3 * p.nreg, "cy_routing_plan: out holds %d values, the plan has %d", n, 7 + 3 * p.nreg);
+  const long long headv[7] = {p.path, p.row_blocks, p.nch, p.ic, p.cdb, p.total, p.nreg};
+  for (int k = 0; k < 7; ++k) out[k] = headv[k];
+  for (int k = 0; k < p.nreg; ++k) {
+    const int id = p.order[k];
+    out[7 + 3 * k] = id; out[8 + 3 * k] = p.off[id]; out[9 + 3 * k] = p.len[id];
   }
-  cyi_rows_plan_t p;
-  cyi_rows_plan(a->R, a->N, a->C, a->Dout, 1, &p);
-  const long long cdb = (!p.phased && a->n_iter > 1 && a->Dout <= 21) ? 2ll * (a->n_iter - 1) * a->R * a->N * a->C : 0;
-  return bwd_ws_head(a, p) + cyi_rows_wp_floats(a->N, a->C, a->Dout) + cdb;
+  return 0;
 }
 
 extern "C" int cy_routing_bwd(const cy_routing_bwd_t* a, void* stream) {
   CY_REQUIRE(a && a->u && a->W && a->s_hist && a->dv && a->du && a->dW && a->ws, "cy_routing_bwd: null pointer");
-  int rc = check_shape("cy_routing_bwd", a->R, a->N, a->C, a->Din, a->Dout, a->n_iter, a->gather_g, a->gather_B);
+  cyi_routing_plan_t p;
+  int rc = CY_PLAN_OF("cy_routing_bwd", a, 1, &p);
   if (rc) return rc;
-  if (!specialised_shape(a->N, a->C, a->Din, a->Dout)) return cy_routing_general_bwd(a, stream);
   hipStream_t s = (hipStream_t)stream;
-  if (fast_c1(a->N, a->C, a->Din, a->Dout)) {
-    const int blocks = a->R < C1_BLOCKS ? a->R : C1_BLOCKS;
+  if (p.path == CYI_ROUTE_GENERAL) return cyi_general_bwd(a, &p, s);
+  if (p.path == CYI_ROUTE_C1) {
     const size_t lds = (size_t)4096 * 5 * 4;
     const float* s_last = a->s_hist + (long long)(a->n_iter - 1) * a->R * 5;
+    float* slabs = cyi_ws_at(a->ws, &p, CYI_WS_SLABS);
     if (a->gather_g) {
       rc = cy_allow_lds(caps1_bwd_kernel<5, true>, lds);
       if (rc) return rc;
-      caps1_bwd_kernel<5, true><<<blocks, C1B_THREADS, lds, s>>>(a->u, a->W, s_last, a->dv, a->du, a->ws, a->R, a->gather_g, a->gather_B);
+      caps1_bwd_kernel<5, true><<<p.row_blocks, C1B_THREADS, lds, s>>>(a->u, a->W, s_last, a->dv, a->du, slabs, a->R, a->gather_g, a->gather_B);
     } else {
       rc = cy_allow_lds(caps1_bwd_kernel<5, false>, lds);
       if (rc) return rc;
-      caps1_bwd_kernel<5, false><<<blocks, C1B_THREADS, lds, s>>>(a->u, a->W, s_last, a->dv, a->du, a->ws, a->R, 0, 1);
+      caps1_bwd_kernel<5, false><<<p.row_blocks, C1B_THREADS, lds, s>>>(a->u, a->W, s_last, a->dv, a->du, slabs, a->R, 0, 1);
     }
     CY_LAUNCH_CHECK("cy_routing_bwd(c1)");
     const long long n = 4096ll * 5;
-    slab_sum_kernel<<<(unsigned)cy_ceil_div(n, 64), 1024, 0, s>>>(a->ws, a->dW, blocks, n);
+    slab_sum_kernel<<<(unsigned)cy_ceil_div(n, 64), 1024, 0, s>>>(slabs, a->dW, p.row_blocks, n);
     CY_LAUNCH_CHECK("cy_routing_bwd(c1 reduce)");
     return 0;
   }
   hipError_t e = hipMemsetAsync(a->dW, 0, (size_t)a->N * a->C * a->Din * a->Dout * 4, s);
   if (e != hipSuccess) return cy_set_error((int)e, "cy_routing_bwd: memset: %s", hipGetErrorString(e));
-  if (a->Dout == 5) rc = launch_bwd<5>(a, s);
-  else if (a->Dout == 16) rc = launch_bwd<16>(a, s);
-  else if (a->Dout == 21) rc = launch_bwd<21>(a, s);
-  else rc = launch_bwd<48>(a, s);
+  if (a->Dout == 5) rc = launch_bwd<5>(a, p, s);
+  else if (a->Dout == 16) rc = launch_bwd<16>(a, p, s);
+  else if (a->Dout == 21) rc = launch_bwd<21>(a, p, s);
+  else rc = launch_bwd<48>(a, p, s);
   if (rc) return rc;
   CY_LAUNCH_CHECK("cy_routing_bwd");
   return 0;

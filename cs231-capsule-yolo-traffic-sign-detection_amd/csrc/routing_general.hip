@@ -27,7 +27,7 @@ namespace {
 
 constexpr int RG_THREADS = 256;
 constexpr long long RG_DUH_BUDGET = 64ll << 20;     // floats of the du_hat staging buffer per chunk of input capsules
-constexpr int RG_MAX_DIN = 16, RG_MAX_DOUT = 64, RG_MAX_C = 256;
+constexpr int RG_MAX_DIN = CYI_RG_MAX_DIN;
 
 inline int rg_cw(int C) { return C <= 64 ? 1 : C <= 128 ? 2 : 4; }
 inline int rg_dp(int Dout) {
@@ -430,69 +430,7 @@ __global__ void rg_split_sum_kernel(const float* __restrict__ slabs, float* __re
 }
 
 // ------------------------------------------------------------------------------------------------ host plan
-struct rg_plan {
-  int DP, CW, Cp, nrb;
-  int nch, ic;               // forward / dV passes: chunks of input capsules
-  int ich, nich, ipb;        // du_hat pass: input capsules per staged chunk, number of chunks, per block
-  int rs, rps;               // dW contraction: row splits, rows per split
-  long long plane, wp;       // R*C*DP, floats of the packed W
-};
-
-rg_plan make_plan(int R, int N, int C, int Din, int Dout) {
-  rg_plan p;
-  p.DP = rg_dp(Dout);
-  p.CW = rg_cw(C);
-  p.Cp = 64 * p.CW;
-  p.nrb = (int)cy_ceil_div(R, 4 / p.CW);
-  p.plane = (long long)R * C * p.DP;
-  p.wp = (long long)N * Din * p.DP * p.Cp;
-  // about 4 blocks per CU, chunks of at least 4 input capsules
-  long long n = cy_ceil_div(1024, p.nrb);
-  const long long nmax = cy_ceil_div(N, 4);
-  if (n > nmax) n = nmax;
-  if (n < 1) n = 1;
-  p.ic = (int)cy_ceil_div(N, n);
-  p.nch = (int)cy_ceil_div(N, p.ic);
-  long long ich = RG_DUH_BUDGET / p.plane;
-  if (ich > N) ich = N;
-  if (ich < 1) ich = 1;
-  p.ich = (int)ich;
-  p.nich = (int)cy_ceil_div(N, p.ich);
-  long long ipb = cy_ceil_div((long long)p.nrb * p.ich, 1024);
-  if (ipb > p.ich) ipb = p.ich;
-  p.ipb = (int)ipb;
-  const long long xb = cy_ceil_div((long long)p.ich * C * Dout, RG_THREADS);
-  long long rs = cy_ceil_div(2048, xb);
-  const long long rsmax = cy_ceil_div(R, 8);
-  if (rs > rsmax) rs = rsmax;
-  if (rs < 1) rs = 1;
-  p.rps = (int)cy_ceil_div(R, rs);
-  p.rs = (int)cy_ceil_div(R, p.rps);
-  return p;
-}
-
-// forward workspace: [Wp][V][slabs]
-long long fwd_ws(const rg_plan& p) { return rg_align4(p.wp) + rg_align4(p.plane) + (long long)p.nch * p.plane; }
-// backward workspace: [Wp][V_all][ds_all][SA][slabs][du_hat][dW split slabs]
-long long bwd_dwslab(const rg_plan& p, int C, int Din, int Dout) {
-  return p.rs > 1 ? (long long)p.rs * p.ich * C * Din * Dout : 0;
-}
-long long bwd_ws(const rg_plan& p, int T, int R, int C, int Din, int Dout) {
-  return rg_align4(p.wp) + 2ll * T * p.plane + p.plane + (long long)p.nch * p.plane + (long long)R * p.ich * C * p.DP +
-         bwd_dwslab(p, C, Din, Dout);
-}
-
-int check_general(const char* fn, int R, int N, int C, int Din, int Dout, int n_iter, int g, int B) {
-  if (R <= 0 || N <= 0 || C <= 0 || Din <= 0 || Dout <= 0 || n_iter <= 0)
-    return cy_set_error(CY_EINVAL, "%s: non-positive dimension", fn);
-  if (g != 0 && (N != 512 || Din != 8 || B <= 0 || R != g * g * B))
-    return cy_set_error(CY_EINVAL, "%s: cell gather needs N=512, Din=8, R=g*g*B (got N=%d Din=%d R=%d g=%d B=%d)", fn, N,
-                        Din, R, g, B);
-  if (Din > RG_MAX_DIN || Dout > RG_MAX_DOUT || C > RG_MAX_C)
-    return cy_set_error(CY_EINVAL, "%s: capsule shape C=%d Din=%d Dout=%d outside the routing envelope (Din 1..16, Dout 1..64, C 1..256)",
-                        fn, C, Din, Dout);
-  return 0;
-}
+typedef cyi_routing_plan_t::cyi_rg_plan_t rg_plan;
 
 rg_args base_args(const float* u, const float* Wp, int R, int N, int C, int Din, int Dout, int g, int B, const rg_plan& p) {
   rg_args r{};
@@ -508,10 +446,11 @@ int pack(const float* W, float* Wp, int N, int C, int Din, int Dout, const rg_pl
 }
 
 template <int DP>
-int fwd_dp(const cy_routing_fwd_t* a, const rg_plan& p, hipStream_t s) {
-  float* Wp = a->ws;
-  float* V = Wp + rg_align4(p.wp);
-  float* slab = V + rg_align4(p.plane);
+int fwd_dp(const cy_routing_fwd_t* a, const cyi_routing_plan_t& P, hipStream_t s) {
+  const rg_plan& p = P.rg;
+  float* Wp = cyi_ws_at(a->ws, &P, CYI_WS_W);
+  float* V = cyi_ws_at(a->ws, &P, CYI_WS_V);
+  float* slab = cyi_ws_at(a->ws, &P, CYI_WS_SLABS);
   int rc = pack(a->W, Wp, a->N, a->C, a->Din, a->Dout, p, s);
   if (rc) return rc;
   rg_args r = base_args(a->u, Wp, a->R, a->N, a->C, a->Din, a->Dout, a->gather_g, a->gather_B, p);
@@ -530,15 +469,16 @@ int fwd_dp(const cy_routing_fwd_t* a, const rg_plan& p, hipStream_t s) {
 }
 
 template <int DP>
-int bwd_dp(const cy_routing_bwd_t* a, const rg_plan& p, hipStream_t s) {
+int bwd_dp(const cy_routing_bwd_t* a, const cyi_routing_plan_t& P, hipStream_t s) {
+  const rg_plan& p = P.rg;
   const int T = a->n_iter, R = a->R, C = a->C;
-  float* Wp = a->ws;
-  float* V_all = Wp + rg_align4(p.wp);
-  float* ds_all = V_all + (long long)T * p.plane;
-  float* SA = ds_all + (long long)T * p.plane;
-  float* slab = SA + p.plane;
-  float* duh = slab + (long long)p.nch * p.plane;
-  float* dws = duh + (long long)R * p.ich * C * p.DP;
+  float* Wp = cyi_ws_at(a->ws, &P, CYI_WS_W);
+  float* V_all = cyi_ws_at(a->ws, &P, CYI_WS_V);
+  float* ds_all = cyi_ws_at(a->ws, &P, CYI_WS_DS_ALL);
+  float* SA = cyi_ws_at(a->ws, &P, CYI_WS_SA);
+  float* slab = cyi_ws_at(a->ws, &P, CYI_WS_SLABS);
+  float* duh = cyi_ws_at(a->ws, &P, CYI_WS_DUH);
+  float* dws = cyi_ws_at(a->ws, &P, CYI_WS_DWS);          // NULL without row splits (p.rs == 1)
   int rc = pack(a->W, Wp, a->N, C, a->Din, a->Dout, p, s);
   if (rc) return rc;
   const unsigned fb = (unsigned)cy_ceil_div((long long)R * C, 128);
@@ -578,51 +518,88 @@ int bwd_dp(const cy_routing_bwd_t* a, const rg_plan& p, hipStream_t s) {
 
 }  // namespace
 
-extern "C" long long cy_routing_general_fwd_ws_floats(const cy_routing_fwd_t* a) {
-  if (!a) return -1;
-  if (check_general("cy_routing_general_fwd_ws_floats", a->R, a->N, a->C, a->Din, a->Dout, a->n_iter, a->gather_g, a->gather_B))
-    return -1;
-  return fwd_ws(make_plan(a->R, a->N, a->C, a->Din, a->Dout));
+// the general kernels' part of the routing plan: launch numbers and workspace regions (tables: DESIGN section 4g)
+void cyi_general_plan(int R, int N, int C, int Din, int Dout, int n_iter, int backward, cyi_routing_plan_t* P) {
+  rg_plan& p = P->rg;
+  p.DP = rg_dp(Dout);
+  p.CW = rg_cw(C);
+  p.Cp = 64 * p.CW;
+  p.nrb = (int)cy_ceil_div(R, 4 / p.CW);
+  p.plane = (long long)R * C * p.DP;
+  p.wp = (long long)N * Din * p.DP * p.Cp;
+  // about 4 blocks per CU, chunks of at least 4 input capsules
+  long long n = cy_ceil_div(1024, p.nrb);
+  const long long nmax = cy_ceil_div(N, 4);
+  if (n > nmax) n = nmax;
+  if (n < 1) n = 1;
+  p.ic = (int)cy_ceil_div(N, n);
+  p.nch = (int)cy_ceil_div(N, p.ic);
+  long long ich = RG_DUH_BUDGET / p.plane;
+  if (ich > N) ich = N;
+  if (ich < 1) ich = 1;
+  p.ich = (int)ich;
+  p.nich = (int)cy_ceil_div(N, p.ich);
+  long long ipb = cy_ceil_div((long long)p.nrb * p.ich, 1024);
+  if (ipb > p.ich) ipb = p.ich;
+  p.ipb = (int)ipb;
+  const long long xb = cy_ceil_div((long long)p.ich * C * Dout, RG_THREADS);
+  long long rs = cy_ceil_div(2048, xb);
+  const long long rsmax = cy_ceil_div(R, 8);
+  if (rs > rsmax) rs = rsmax;
+  if (rs < 1) rs = 1;
+  p.rps = (int)cy_ceil_div(R, rs);
+  p.rs = (int)cy_ceil_div(R, p.rps);
+  P->row_blocks = p.nrb; P->nch = p.nch; P->ic = p.ic;
+  cyi_ws_add(P, CYI_WS_W, p.wp, 1);
+  cyi_ws_add(P, CYI_WS_V, (backward ? n_iter : 1) * p.plane, 1);
+  if (backward) {
+    cyi_ws_add(P, CYI_WS_DS_ALL, n_iter * p.plane, 1);
+    cyi_ws_add(P, CYI_WS_SA, p.plane, 1);
+  }
+  cyi_ws_add(P, CYI_WS_SLABS, p.nch * p.plane, 1);
+  if (backward) {
+    cyi_ws_add(P, CYI_WS_DUH, (long long)R * p.ich * C * p.DP, 1);
+    if (p.rs > 1) cyi_ws_add(P, CYI_WS_DWS, (long long)p.rs * p.ich * C * Din * Dout, 1);
+  }
 }
 
+#define RG_DISPATCH(fn, a, p, s)                \
+  switch ((p)->rg.DP) {                         \
+    case 4: return fn<4>(a, *(p), s);           \
+    case 8: return fn<8>(a, *(p), s);           \
+    case 16: return fn<16>(a, *(p), s);         \
+    case 24: return fn<24>(a, *(p), s);         \
+    case 32: return fn<32>(a, *(p), s);         \
+    case 48: return fn<48>(a, *(p), s);         \
+    default: return fn<64>(a, *(p), s);         \
+  }
+int cyi_general_fwd(const cy_routing_fwd_t* a, const cyi_routing_plan_t* p, hipStream_t s) {
+  CY_REQUIRE(a->ws, "cy_routing_general_fwd: needs the workspace (ws) of cy_routing_general_fwd_ws_floats()");
+  RG_DISPATCH(fwd_dp, a, p, s)
+}
+int cyi_general_bwd(const cy_routing_bwd_t* a, const cyi_routing_plan_t* p, hipStream_t s) { RG_DISPATCH(bwd_dp, a, p, s) }
+
+#define RG_PLAN_OF(fn, a, backward, p) \
+  cyi_routing_plan(fn, (a)->R, (a)->N, (a)->C, (a)->Din, (a)->Dout, (a)->n_iter, (a)->gather_g, (a)->gather_B, backward, 1, p)
+
+extern "C" long long cy_routing_general_fwd_ws_floats(const cy_routing_fwd_t* a) {
+  cyi_routing_plan_t p;
+  return a && RG_PLAN_OF("cy_routing_general_fwd_ws_floats", a, 0, &p) == 0 ? p.total : -1;
+}
 extern "C" long long cy_routing_general_bwd_ws_floats(const cy_routing_bwd_t* a) {
-  if (!a) return -1;
-  if (check_general("cy_routing_general_bwd_ws_floats", a->R, a->N, a->C, a->Din, a->Dout, a->n_iter, a->gather_g, a->gather_B))
-    return -1;
-  return bwd_ws(make_plan(a->R, a->N, a->C, a->Din, a->Dout), a->n_iter, a->R, a->C, a->Din, a->Dout);
+  cyi_routing_plan_t p;
+  return a && RG_PLAN_OF("cy_routing_general_bwd_ws_floats", a, 1, &p) == 0 ? p.total : -1;
 }
 
 extern "C" int cy_routing_general_fwd(const cy_routing_fwd_t* a, void* stream) {
   CY_REQUIRE(a && a->u && a->W && a->v_out && a->s_hist, "cy_routing_general_fwd: null pointer");
-  int rc = check_general("cy_routing_general_fwd", a->R, a->N, a->C, a->Din, a->Dout, a->n_iter, a->gather_g, a->gather_B);
-  if (rc) return rc;
-  CY_REQUIRE(a->ws, "cy_routing_general_fwd: needs the workspace (ws) of cy_routing_general_fwd_ws_floats()");
-  const rg_plan p = make_plan(a->R, a->N, a->C, a->Din, a->Dout);
-  hipStream_t s = (hipStream_t)stream;
-  switch (p.DP) {
-    case 4: return fwd_dp<4>(a, p, s);
-    case 8: return fwd_dp<8>(a, p, s);
-    case 16: return fwd_dp<16>(a, p, s);
-    case 24: return fwd_dp<24>(a, p, s);
-    case 32: return fwd_dp<32>(a, p, s);
-    case 48: return fwd_dp<48>(a, p, s);
-    default: return fwd_dp<64>(a, p, s);
-  }
+  cyi_routing_plan_t p;
+  const int rc = RG_PLAN_OF("cy_routing_general_fwd", a, 0, &p);
+  return rc ? rc : cyi_general_fwd(a, &p, (hipStream_t)stream);
 }
-
 extern "C" int cy_routing_general_bwd(const cy_routing_bwd_t* a, void* stream) {
   CY_REQUIRE(a && a->u && a->W && a->s_hist && a->dv && a->du && a->dW && a->ws, "cy_routing_general_bwd: null pointer");
-  int rc = check_general("cy_routing_general_bwd", a->R, a->N, a->C, a->Din, a->Dout, a->n_iter, a->gather_g, a->gather_B);
-  if (rc) return rc;
-  const rg_plan p = make_plan(a->R, a->N, a->C, a->Din, a->Dout);
-  hipStream_t s = (hipStream_t)stream;
-  switch (p.DP) {
-    case 4: return bwd_dp<4>(a, p, s);
-    case 8: return bwd_dp<8>(a, p, s);
-    case 16: return bwd_dp<16>(a, p, s);
-    case 24: return bwd_dp<24>(a, p, s);
-    case 32: return bwd_dp<32>(a, p, s);
-    case 48: return bwd_dp<48>(a, p, s);
-    default: return bwd_dp<64>(a, p, s);
-  }
+  cyi_routing_plan_t p;
+  const int rc = RG_PLAN_OF("cy_routing_general_bwd", a, 1, &p);
+  return rc ? rc : cyi_general_bwd(a, &p, (hipStream_t)stream);
 }

@@ -995,19 +995,32 @@ ROUTING_FORCE_GENERAL = False   # every routing shape on the general kernels (ro
 #                                 take: A/B runs and cross-checks.  Read at each call, so a forward and its backward may take different paths.
 
 
-def _routing_entry(a):
-    """'cy_routing_fwd' where the specialised kernels take the shape, else the general kernels' entry point."""
-    if ROUTING_FORCE_GENERAL or not query('cy_routing_specialised', C.byref(a)):
-        return 'cy_routing_general_fwd'
-    return 'cy_routing_fwd'
+ROUTING_PATHS = ('c1', 'rows_fused', 'rows_phased', 'general', 'mfma_fused', 'mfma_phased')     # CYI_ROUTE_* of csrc/common.h
+ROUTING_REGIONS = ('ds_all', 'V', 'SA', 'slabs', 'tail', 'W', 'cdb', 'du_hat', 'dW_splits')      # CYI_WS_*
 
 
-def _routing_ws(name, a):
-    n = query(name, C.byref(a))
-    if n < 0:          # outside the general kernels' envelope: the library's message says which
+def routing_plan(R, N, Cc, Din, Dout, n_iter, gather_g=0, gather_B=0, backward=False, force_general=None):
+    """What the library decides about one routing call (cy_routing_plan, host arithmetic): the path, the launch numbers, and the
+    workspace regions [(name, offset, length)] in floats in the order they lie in, `total` being the end of the last one."""
+    a = RoutingFwd(R=R, N=N, C=Cc, Din=Din, Dout=Dout, n_iter=n_iter, gather_g=gather_g, gather_B=gather_B)
+    out = (C.c_longlong * (7 + 3 * len(ROUTING_REGIONS)))()
+    force = ROUTING_FORCE_GENERAL if force_general is None else force_general
+    rc = query('cy_routing_plan', C.byref(a), int(backward), int(force), out, len(out))
+    if rc:          # no path takes the shape: the library's message says why
         msg = _lib.load().capsyolo_last_error()
-        raise _lib.HipExtensionError('%s failed: %s' % (name, msg.decode() if msg else '?'))
-    return n
+        raise _lib.HipExtensionError('cy_routing_plan failed (code %d): %s' % (rc, msg.decode() if msg else '?'))
+    names = [n + '_all' if backward and n == 'V' else n for n in ROUTING_REGIONS]
+    return {'path': ROUTING_PATHS[out[0]], 'row_blocks': out[1], 'nch': out[2], 'ic': out[3], 'cdb': bool(out[4]), 'total': out[5],
+            'regions': [(names[out[7 + 3 * k]], out[8 + 3 * k], out[9 + 3 * k]) for k in range(out[6])]}
+
+
+def _routing_call(kind, a, like):
+    """One plan query: the entry point of the plan's path, on a workspace of the plan's total."""
+    p = routing_plan(a.R, a.N, a.C, a.Din, a.Dout, a.n_iter, a.gather_g, a.gather_B, backward=kind == 'bwd')
+    ws = _empty((p['total'],), like) if p['total'] else None
+    a.ws = ws.data_ptr() if p['total'] else None
+    with timer.range('routing_' + kind):
+        call(('cy_routing_general_' if p['path'] == 'general' else 'cy_routing_') + kind, C.byref(a), _stream())
 
 
 class _Routing(torch.autograd.Function):
@@ -1023,15 +1036,8 @@ class _Routing(torch.autograd.Function):
             out_shape = (R, Cc, Dout)
         v = _empty(out_shape, u)
         s_hist = _empty((n_iter, R, Cc, Dout), u)
-        a = RoutingFwd(u=u.data_ptr(), W=W.data_ptr(), v_out=v.data_ptr(), s_hist=s_hist.data_ptr(), R=R, N=N, C=Cc,
-                       Din=Din, Dout=Dout, n_iter=n_iter, gather_g=gather_g, gather_B=gather_B, ws=None)
-        fn = _routing_entry(a)
-        nws = _routing_ws(fn + '_ws_floats', a)
-        if nws:
-            ws = _empty((nws,), u)
-            a.ws = ws.data_ptr()
-        with timer.range('routing_fwd'):
-            call(fn, C.byref(a), _stream())
+        _routing_call('fwd', RoutingFwd(u=u.data_ptr(), W=W.data_ptr(), v_out=v.data_ptr(), s_hist=s_hist.data_ptr(), R=R, N=N, C=Cc,
+                                        Din=Din, Dout=Dout, n_iter=n_iter, gather_g=gather_g, gather_B=gather_B, ws=None), u)
         ctx.save_for_backward(u, W, s_hist)
         ctx.dims = (R, N, Cc, Din, Dout, n_iter, gather_g, gather_B)
         return v
@@ -1042,15 +1048,9 @@ class _Routing(torch.autograd.Function):
         R, N, Cc, Din, Dout, n_iter, g, gB = ctx.dims
         dv = _f32(dv, 'grad')
         du, dW = torch.empty_like(u), torch.empty_like(W)
-        a = RoutingBwd(u=u.data_ptr(), W=W.data_ptr(), s_hist=s_hist.data_ptr(), dv=dv.data_ptr(), du=du.data_ptr(),
-                       dW=dW.data_ptr(), ws=None, R=R, N=N, C=Cc, Din=Din, Dout=Dout, n_iter=n_iter, gather_g=g,
-                       gather_B=gB)
-        fwd = RoutingFwd(R=R, N=N, C=Cc, Din=Din, Dout=Dout, n_iter=n_iter, gather_g=g, gather_B=gB)
-        fn = _routing_entry(fwd).replace('_fwd', '_bwd')
-        ws = _empty((_routing_ws(fn + '_ws_floats', a),), u)
-        a.ws = ws.data_ptr()
-        with timer.range('routing_bwd'):
-            call(fn, C.byref(a), _stream())
+        _routing_call('bwd', RoutingBwd(u=u.data_ptr(), W=W.data_ptr(), s_hist=s_hist.data_ptr(), dv=dv.data_ptr(), du=du.data_ptr(),
+                                        dW=dW.data_ptr(), ws=None, R=R, N=N, C=Cc, Din=Din, Dout=Dout, n_iter=n_iter, gather_g=g,
+                                        gather_B=gB), u)
         return du, dW, None, None, None
 
 

@@ -385,6 +385,14 @@ long long cy_routing_general_fwd_ws_floats(const cy_routing_fwd_t* a);
 int cy_routing_general_fwd(const cy_routing_fwd_t* a, void* stream);
 long long cy_routing_general_bwd_ws_floats(const cy_routing_bwd_t* a);
 int cy_routing_general_bwd(const cy_routing_bwd_t* a, void* stream);
+/* The plan of one routing call, without a GPU (host arithmetic; only the shape fields of `a` are read): which kernels take it, with
+ * which launch numbers, and where every buffer lies in the workspace.  backward: the plan of cy_routing_bwd instead of cy_routing_fwd;
+ * force_general: the plan of the cy_routing_general_ entry points.  out[0..6] = {path (0 c1, 1 rows_fused, 2 rows_phased, 3 general,
+ * 4 mfma_fused, 5 mfma_phased), blocks along the rows, chunks of input capsules, input capsules per chunk, couplings saved for the
+ * du / dW kernel (0 / 1), workspace floats (what the _ws_floats query of the path returns), number of regions}, then per region in
+ * workspace order {id (0 ds_all, 1 V / V_all, 2 SA, 3 slabs, 4 tail, 5 W, 6 cdb, 7 du_hat, 8 dW_splits), offset, length} in floats;
+ * n: the values out can hold (34 always suffice).  Returns 0, or CY_EINVAL with capsyolo_last_error() set for a shape no path takes. */
+int cy_routing_plan(const cy_routing_fwd_t* a, int backward, int force_general, long long* out, int n);
 
 /* squash over the last dim (models.py:64-67), rows of D floats; and its backward */
 int cy_squash_fwd(const float* s, float* v, long long rows, int D, void* stream);

@@ -186,3 +186,81 @@ def test_outside_the_envelope_is_an_error(shape):
     u, W = rnd((R, N, Din), 1).to(dev()), rnd((1, N, Cc, Din, Dout), 2).to(dev())
     with pytest.raises(_lib.HipExtensionError, match='envelope'):
         ops.routing(u, W, n_iter)
+
+
+# ------------------------------------------------------------------------------------------------ the workspace stays inside the plan's total
+GUARD, PATTERN = 1024, 0x5A5A5A5A        # floats before and after the workspace (a multiple of 4: the slice keeps its 16-byte alignment)
+
+
+def guarded_ws(total):
+    buf = torch.full((GUARD + total + GUARD,), PATTERN, dtype=torch.int32, device=dev())
+    return buf, buf.view(torch.float32)[GUARD:GUARD + total]
+
+
+def guards_untouched(buf, total):
+    return bool((buf[:GUARD] == PATTERN).all()) and bool((buf[GUARD + total:] == PATTERN).all())
+
+
+def guard_case(shape, g=0, B=0, want_path=None):
+    """cy_routing_fwd / _bwd (or the general entry points, as the plan says) called directly on a workspace of exactly the plan's
+    total floats cut out of a larger tensor: the 1024 floats on either side keep their bit pattern, and the results are those of
+    ops.routing on the same inputs."""
+    from capsyolo_amd import _lib, ops
+    R, N, Cc, Din, Dout, n_iter = shape
+    if g:
+        u, out_shape = rnd((B, 4 * g, 4 * g, 256), 51, 0.7).to(dev()), (B, g, g, Cc, Dout)
+    else:
+        u, out_shape = rnd((R, N, Din), 51, 0.8).to(dev()), (R, Cc, Dout)
+    W, G = rnd((1, N, Cc, Din, Dout), 52, 0.15).to(dev()), rnd(out_shape, 53).to(dev())
+    ur, Wr = u.clone().requires_grad_(True), W.clone().requires_grad_(True)
+    vr = ops.routing(ur, Wr, n_iter, g, B)
+    (vr * G).sum().backward()
+
+    pf, pb = ops.routing_plan(*shape, g, B), ops.routing_plan(*shape, g, B, backward=True)
+    if want_path:
+        assert pf['path'] == want_path, pf
+    entry = 'cy_routing_general_' if pf['path'] == 'general' else 'cy_routing_'
+    v, s_hist = torch.empty(out_shape, device=dev()), torch.empty((n_iter, R, Cc, Dout), device=dev())
+    buf, ws = guarded_ws(pf['total'])
+    a = _lib.RoutingFwd(u=u.data_ptr(), W=W.data_ptr(), v_out=v.data_ptr(), s_hist=s_hist.data_ptr(), R=R, N=N, C=Cc, Din=Din, Dout=Dout,
+                        n_iter=n_iter, gather_g=g, gather_B=B, ws=ws.data_ptr() if pf['total'] else None)
+    _lib.call(entry + 'fwd', ctypes.byref(a), ops._stream())
+    torch.cuda.synchronize()
+    assert guards_untouched(buf, pf['total']), ('forward', shape, pf)
+    assert torch.equal(v, vr.detach())
+
+    du, dW = torch.empty_like(u), torch.empty_like(W)
+    buf, ws = guarded_ws(pb['total'])
+    a = _lib.RoutingBwd(u=u.data_ptr(), W=W.data_ptr(), s_hist=s_hist.data_ptr(), dv=G.data_ptr(), du=du.data_ptr(), dW=dW.data_ptr(),
+                        ws=ws.data_ptr(), R=R, N=N, C=Cc, Din=Din, Dout=Dout, n_iter=n_iter, gather_g=g, gather_B=B)
+    _lib.call(entry + 'bwd', ctypes.byref(a), ops._stream())
+    torch.cuda.synchronize()
+    assert guards_untouched(buf, pb['total']), ('backward', shape, pb)
+    assert torch.equal(du, ur.grad)
+    if pb['path'] in ('c1', 'general'):
+        assert torch.equal(dW, Wr.grad)
+    else:
+        # routing_caps.hip adds its row chunks into dW with float atomics: the same partial sums in another order.  Reordering a
+        # sum of K <= 256 fp32 terms moves it by at most K * 2^-24 * sum |terms|; 1e-5 of the largest |dW| is 168 * 2^-24 of it.
+        close(dW, Wr.grad, 0, 1e-5 * float(Wr.grad.abs().max()))
+    return pf, pb
+
+
+@pytest.mark.parametrize('shape,g,B,path', [
+    ((130, 512, 1, 8, 5, 3), 0, 0, 'c1'), ((1100, 12, 5, 8, 16, 3), 0, 0, 'rows_fused'), ((37, 70, 43, 8, 16, 3), 0, 0, 'rows_phased'),
+    ((6, 40, 49, 8, 48, 2), 0, 0, 'rows_phased'), ((45, 512, 1, 8, 5, 3), 3, 5, 'c1'), ((9, 20, 7, 4, 64, 7), 0, 0, 'general'),
+    ((1200, 3, 130, 4, 3, 3), 0, 0, 'general')])
+def test_workspace_stays_inside_the_plan_total(shape, g, B, path):
+    guard_case(shape, g, B, path)
+
+
+def test_workspace_stays_inside_the_plan_total_on_the_mfma_forward():
+    """The same check in a fresh process that has CY_ROUTING_MFMA=1 from its start."""
+    import os
+    import subprocess
+    import sys
+    from helpers import REPO
+    code = ('import sys; sys.path[:0] = [%r, %r]\nimport test_gpu_routing_general as t\n'
+            't.guard_case((37, 70, 43, 8, 16, 3), want_path="mfma_phased")\nprint("guards ok")\n' % (REPO, os.path.join(REPO, 'tests')))
+    r = subprocess.run([sys.executable, '-c', code], env=dict(os.environ, CY_ROUTING_MFMA='1'), capture_output=True, text=True)
+    assert r.returncode == 0 and 'guards ok' in r.stdout, r.stdout + r.stderr

@@ -74,5 +74,5 @@ def test_envelope_message_names_the_envelope():
 
 def test_new_entry_points_are_bound():
     for n in ('cy_routing_general_fwd', 'cy_routing_general_bwd', 'cy_routing_general_fwd_ws_floats',
-              'cy_routing_general_bwd_ws_floats', 'cy_routing_specialised'):
+              'cy_routing_general_bwd_ws_floats', 'cy_routing_specialised', 'cy_routing_plan'):
         assert n in _lib.EXPORTS and hasattr(_lib.load(), n)
