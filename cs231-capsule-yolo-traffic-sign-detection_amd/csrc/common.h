@@ -33,6 +33,43 @@ static inline int cy_allow_lds(K kernel, size_t bytes) {
   return 0;
 }
 
+// CU count of the current device, or 0 when it cannot be had (no device, no driver: the workspace-size queries run there too).
+// What 0 means is the caller's policy: an error, an assumed 256, or no split.  err (optional): the failing call's code.
+static inline int cyi_cu_count(hipError_t* err = nullptr) {
+  int dev = 0, ncu = 0;
+  hipError_t he = hipGetDevice(&dev);
+  if (he == hipSuccess) he = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  if (err) *err = he;
+  return he == hipSuccess && ncu > 0 ? ncu : 0;
+}
+// persistent grid: one block per CU, at most one per tile
+static inline int cyi_persistent_blocks(const char* who, long long tiles, long long* blocks) {
+  hipError_t he;
+  const int ncu = cyi_cu_count(&he);
+  if (ncu == 0) return cy_set_error((int)he, "%s: cannot query the CU count: %s", who, hipGetErrorString(he));
+  *blocks = tiles < ncu ? tiles : ncu;
+  return 0;
+}
+#ifdef __HIPCC__
+// opts the kernel it is about to launch (and no other instantiation) in to `lds` bytes of dynamic LDS, launches it, returns the code
+template <typename... P, typename... A>
+static inline int cyi_launch_lds(const char* who, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args) {
+  if (int rc = cy_allow_lds(kernel, lds)) return rc;
+  kernel<<<grid, block, lds, s>>>(args...);
+  CY_LAUNCH_CHECK(who);
+  return 0;
+}
+#endif
+
+// A developer knob whose nonzero value compiles kernels that compute wrong results (timing experiments) must not reach a production
+// library through a plain -D: each such knob's definition site invokes this, and only a build that says -DCY_DEV_BUILD may set it.
+#ifdef CY_DEV_BUILD
+#define CY_WRONG_RESULT_KNOB(knob) static_assert(true, "")
+#else
+#define CY_WRONG_RESULT_KNOB(knob) \
+  static_assert((knob) == 0, #knob " is set: its kernels compute wrong results; a build that wants that says -DCY_DEV_BUILD")
+#endif
+
 // ---- internal interface of routing_rows.hip (the row-stationary routing pass for C > 1), used by routing.hip
 typedef struct {
   const float* u; const float* Wp;                       // Wp: W repacked by cyi_rows_pack_w (the LDS image layout)

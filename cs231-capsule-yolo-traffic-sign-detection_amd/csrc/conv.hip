@@ -12,7 +12,7 @@
 //   * lane (i = lane&31, h = lane>>5) fetches 4 MFMA steps of its operand with ONE ds_read_b128
 //     at [kq = 2*kg + h][row i]: step t multiplies k = 8kg+t (h=0) and 8kg+4+t (h=1).
 // Both operands use the same k permutation, so the sum over k is unchanged.
-#include "common.h"
+#include "prims.h"
 
 namespace {
 
@@ -29,10 +29,6 @@ struct GemmGeom {
   int S, kt_per, tiles;
   float* ws;
 };
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
 
 // ------------------------------------------------------------------------------------------------
 template <int NTW, bool VEC>
@@ -212,7 +208,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(cy_conv_gemm_t a, Gem
 #pragma unroll
           for (int ni = 0; ni < NTW; ++ni) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc[mi][ni] = mfma32(fa[cb][mi][e], fb[cb][ni][e], acc[mi][ni]);
+            for (int e = 0; e < 4; ++e) acc[mi][ni] = cyk::mfma32(fa[cb][mi][e], fb[cb][ni][e], acc[mi][ni]);
           }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -639,7 +635,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(cy_conv_wgrad_t a, i
 #pragma unroll
         for (int ni = 0; ni < NT; ++ni) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) acc[mi][ni] = mfma32(fa[cb][mi][e], fb[cb][ni][e], acc[mi][ni]);
+          for (int e = 0; e < 4; ++e) acc[mi][ni] = cyk::mfma32(fa[cb][mi][e], fb[cb][ni][e], acc[mi][ni]);
         }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -809,9 +805,8 @@ GemmPlan plan_gemm(const cy_conv_gemm_t* a, const GemmGeom& g) {
   p.S = 1; p.kt_per = g.KT;
   // ... and, still far below two blocks per CU with a long reduction, S blocks per tile on a share of the K tiles each (>= 8 per
   // share; not with the fused statistics epilogues, which need the finished sums)
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-    ncu = 256;
+  int ncu = cyi_cu_count();
+  if (ncu == 0) ncu = 256;
   if (a->stats == nullptr && a->bn_red == nullptr && p.tiles * 4 <= 3ll * ncu && g.KT >= 32) {
     long long S = (2ll * ncu) / p.tiles;
     if (S > g.KT / 8) S = g.KT / 8;

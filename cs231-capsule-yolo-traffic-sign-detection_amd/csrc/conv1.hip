@@ -28,8 +28,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 struct Conv1Args {
   const float* X; const float* W; const float* bias; float* Y; double* stats;
   const float* scale; const float* shift; float slope;   // forward only, optional: Y = lrelu((conv + bias) * scale + shift)
@@ -797,13 +795,7 @@ __global__ __launch_bounds__(256) void conv1_bn_bwd_finish_kernel(const float* _
 }
 
 static int conv1_blocks(long long ntiles, long long* blocks, const char* who) {
-  int dev = 0, ncu = 0;
-  hipError_t he = hipGetDevice(&dev);
-  if (he == hipSuccess) he = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  if (he != hipSuccess || ncu <= 0) return cy_set_error((int)he, "%s: cannot query the CU count: %s", who, hipGetErrorString(he));
-  *blocks = (ntiles + 3) / 4;
-  if (*blocks > ncu) *blocks = ncu;         // persistent: one wave per SIMD
-  return 0;
+  return cyi_persistent_blocks(who, (ntiles + 3) / 4, blocks);   // persistent: one wave per SIMD
 }
 
 }  // namespace

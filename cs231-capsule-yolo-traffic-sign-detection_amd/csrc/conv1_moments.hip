@@ -189,13 +189,7 @@ __global__ __launch_bounds__(256) void conv1_moments_stats_kernel(const double* 
 }
 
 int moments_blocks(long long rows, long long* blocks, const char* who) {
-  int dev = 0, ncu = 0;
-  hipError_t he = hipGetDevice(&dev);
-  if (he == hipSuccess) he = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  if (he != hipSuccess || ncu <= 0) return cy_set_error((int)he, "%s: cannot query the CU count: %s", who, hipGetErrorString(he));
-  *blocks = (rows + 3) / 4;
-  if (*blocks > ncu) *blocks = ncu;
-  return 0;
+  return cyi_persistent_blocks(who, (rows + 3) / 4, blocks);
 }
 
 }  // namespace

@@ -19,7 +19,7 @@
 // Measured per tile at conv_2 (CY_BF16_PROF=1, cycles of wave 0): 18 K steps x 3.8k (MFMA time of the SIMD's two waves: 2.0k;
 // ~1.0k of barrier skew between them, ~0.1k waiting for the DMA) + 9.4k of epilogue; the register-staged one-tile-per-block
 // first version had 4.0k per step and ~27k of fixed cost per tile (launch, first-step latency, 16 bias round trips).
-#include "common.h"
+#include "prims.h"
 // Output tiles are stored nontemporal: the 0.7 - 5.7 GB of a layer's output otherwise keep evicting the input rows that the 9 (16)
 // taps of the implicit GEMM re-read through L2 (conv_2 forward at 416 x 416: 3.78 -> 3.51 ms; the other shapes unchanged).
 #ifndef CY_BF_NT
@@ -49,6 +49,17 @@ __device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((unsigned)
 
 constexpr int BK = 64;
 constexpr int ROWB = 128;                           // bytes of an LDS row: 64 bf16, NOT padded (LDS-DMA writes 1 KiB = 8 whole rows)
+
+// developer knobs for timing experiments (results are wrong when set).  CY_BF_DBG: 1 no A pieces, 2 no B pieces of a K step;
+// CY_BF_NOSTAGGER: the blocks of an XCD start together
+#ifndef CY_BF_DBG
+#define CY_BF_DBG 0
+#endif
+#ifndef CY_BF_NOSTAGGER
+#define CY_BF_NOSTAGGER 0
+#endif
+CY_WRONG_RESULT_KNOB(CY_BF_DBG);
+CY_WRONG_RESULT_KNOB(CY_BF_NOSTAGGER);
 
 // 16 zero bytes that the LDS-DMA lanes of padding pixels / rows past M read instead of the image
 __device__ __attribute__((aligned(16))) unsigned conv_bf16_zero16[4];
@@ -148,10 +159,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8) ? 1 : 2) void conv_bf1
   asm volatile("" : "+s"(zaddr));
   const u16* zsrc = (const u16*)(uintptr_t)zaddr;
   auto piece = [&](int buf, int j) {
-#ifdef CY_BF_DBG
-    if ((CY_BF_DBG & 1) && j < NA) return;           // timing knock-outs (results are wrong): 1 no A pieces, 2 no B pieces
+    if ((CY_BF_DBG & 1) && j < NA) return;
     if ((CY_BF_DBG & 2) && j >= NA) return;
-#endif
     unsigned char* Ab = smem_raw + buf * BUF_BYTES + wave * 8 * ROWB;      // this wave's 1 KiB piece of round 0
     if (j < NA) {
       const int iy = iy0[j] + tap_a * a.dstep, ix = ix0[j] + tap_b * a.dstep;
@@ -194,9 +203,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8) ? 1 : 2) void conv_bf1
   // the K loops.  The blocks of an XCD therefore start an eighth of a tile apart (one sleep of ~0.2 us per K step and phase).
   if (gridDim.x >= 64) {
     const int phase = (blockIdx.x >> 3) & 7;
-#ifndef CY_BF_NOSTAGGER
-    for (int i = 0; i < phase * (KT + 6); ++i) __builtin_amdgcn_s_sleep(8);
-#endif
+    if (!CY_BF_NOSTAGGER)
+      for (int i = 0; i < phase * (KT + 6); ++i) __builtin_amdgcn_s_sleep(8);
   }
   int cur = 0, slot = 0;
   // Consecutive tiles are consecutive pixel segments: the rows a 3 x 3 tap reads above and below a tile are the rows of the next
@@ -939,29 +947,11 @@ struct WgArgs {
 #ifndef CY_WG_DBG
 #define CY_WG_DBG 0
 #endif
-#ifndef CY_WG_ST_AUX
-#define CY_WG_ST_AUX ""              // cache policy of the fused variant's dz store (" nt": swept)
-#endif
+CY_WRONG_RESULT_KNOB(CY_WG_DBG);
 #ifndef CY_WG_RING
 #define CY_WG_RING 3               // B fragments in flight ahead of their MFMAs (swept 2 / 3 / 4)
 #endif
-typedef int wg_i32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ wg_i32x4 wg_desc(const void* p, unsigned bytes) {
-  const unsigned long long b = (unsigned long long)(uintptr_t)p;
-  return wg_i32x4{(int)(unsigned)b, (int)(unsigned)((b >> 32) & 0xffffu), (int)bytes, 0x00020000};
-}
-// loads hipcc does not count (see wgrad_bf16_kernel); waited for by hand
-__device__ __forceinline__ void wg_load(u32x4_t& dst, wg_i32x4 desc, unsigned voff, unsigned soff) {
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(dst) : "v"(voff), "s"(desc), "s"(soff));
-}
-
-// (the s_nop: a vector-memory store of more than 64 bits reads its data registers a cycle behind its issue, and a vector instruction
-// that overwrites them right away needs a wait state in between -- hipcc pads it for its own stores and cannot for an asm statement:
-// without it the first dword of now and then a stored piece was the NEXT item's LDS address, computed into the same register)
-__device__ __forceinline__ void wg_store(const u32x4_t& src, wg_i32x4 desc, unsigned voff, unsigned soff) {
-  asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" CY_WG_ST_AUX "\n\ts_nop 1" : : "v"(src), "v"(voff), "s"(desc), "s"(soff) : "memory");
-}
-
+// (the loads of X and dz are cyk::bufload: hipcc does not count them, see wgrad_bf16_kernel; they are waited for by hand)
 __device__ __forceinline__ bf16x8 tr_frag(const u16* p0, const u16* p1) {
   const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p0);
   const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p1);
@@ -1057,7 +1047,7 @@ __global__ __launch_bounds__(64 * NW, 1) void wgrad_bf16_kernel(WgArgs a) {
   long long left = c_hi - c_lo;                     // real chunks not yet requested
   const bool writer = BNF && (tile % a.ntiles_ci) == 0;          // the input-channel tiles of a dz tile all form it; the first one writes it
   unsigned dzbad[NSET] = {};                        // BNF: items of the staged chunk that lie outside the image (their dz is zero, not kc)
-  wg_i32x4 ozd[NSET]; unsigned ozs[NSET] = {};
+  cyk::i32x4 ozd[NSET]; unsigned ozs[NSET] = {};
   (void)writer;
   auto load_chunk = [&](auto set_c) {
     constexpr int S = decltype(set_c)::value;
@@ -1066,10 +1056,10 @@ __global__ __launch_bounds__(64 * NW, 1) void wgrad_bf16_kernel(WgArgs a) {
     const bool real = left > 0;
     --left;
     const int ox0 = cw * PW;
-    const wg_i32x4 dzd = wg_desc(a.dZ + (long long)b * a.Ho * a.Wo * a.Cout, real ? zimg_b : 0u);
-    wg_i32x4 zzd = dzd;
-    if constexpr (BNF) zzd = wg_desc(a.Z + (long long)b * a.Ho * a.Wo * a.Cout, real ? zimg_b : 0u);
-    const wg_i32x4 xd = wg_desc((const char*)(a.X + (long long)b * a.Hi * a.Wi * a.Cin) - xshift, real ? ximg_b + xshift : 0u);
+    const cyk::i32x4 dzd = cyk::bufdesc(a.dZ + (long long)b * a.Ho * a.Wo * a.Cout, real ? zimg_b : 0u);
+    cyk::i32x4 zzd = dzd;
+    if constexpr (BNF) zzd = cyk::bufdesc(a.Z + (long long)b * a.Ho * a.Wo * a.Cout, real ? zimg_b : 0u);
+    const cyk::i32x4 xd = cyk::bufdesc((const char*)(a.X + (long long)b * a.Hi * a.Wi * a.Cin) - xshift, real ? ximg_b + xshift : 0u);
     const unsigned zso = (unsigned)__builtin_amdgcn_readfirstlane(((oy * a.Wo + ox0) * a.Cout) * 2);
     const unsigned xso = (unsigned)__builtin_amdgcn_readfirstlane(((oy * STRIDE * a.Wi + ox0 * STRIDE) * a.Cin) * 2);
     // first pixel / output row / patch column / patch row beyond the image (row limits from bit 8 on, as in dzpx / xjj: one compare
@@ -1079,7 +1069,7 @@ __global__ __launch_bounds__(64 * NW, 1) void wgrad_bf16_kernel(WgArgs a) {
 #pragma unroll
     for (int i = 0; i < NDZ; ++i) {
       const bool bad = (CY_WG_DBG & 2) || (dzpx[i] & 255) >= zlim || (dzpx[i] >> 8) >= zrlim;
-      wg_load(rdz[S][i], dzd, bad ? 0x80000000u : dzv[i], zso);
+      cyk::bufload(rdz[S][i], dzd, bad ? 0x80000000u : dzv[i], zso);
       if constexpr (BNF && !(CY_WG_DBG & 4)) {
         const unsigned m0v = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)(zlds + (S * NDZ + i) * NTHR * 16) + wave * 1024);
         unsigned keep;                              // (M0 is compiler-reserved: saved and restored inside the statement that uses it)
@@ -1089,22 +1079,22 @@ __global__ __launch_bounds__(64 * NW, 1) void wgrad_bf16_kernel(WgArgs a) {
       if constexpr (BNF) dzbad[S] = (dzbad[S] & ~(1u << i)) | ((bad ? 1u : 0u) << i);
     }
     if constexpr (BNF) {                            // where this chunk's dz goes (stored when the set is); a phantom chunk or a block that shares the tile: nowhere
-      ozd[S] = wg_desc(a.dZout + (long long)b * a.Ho * a.Wo * a.Cout, (real && writer) ? zimg_b : 0u);
+      ozd[S] = cyk::bufdesc(a.dZout + (long long)b * a.Ho * a.Wo * a.Cout, (real && writer) ? zimg_b : 0u);
       ozs[S] = zso;
     }
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
       const bool bad = (CY_WG_DBG & 2) || (((unsigned)xjj[i] >> 16) & bt) != 0u || (xjj[i] & 255) >= xlim || ((xjj[i] >> 8) & 255) >= xrlim;
-      wg_load(rx[S][i], xd, bad ? 0x80000000u : xv[i], xso);
+      cyk::bufload(rx[S][i], xd, bad ? 0x80000000u : xv[i], xso);
     }
   };
   auto wait_set = [&](auto set_c, auto n_c) {       // all but the n youngest vector-memory operations have landed; ties the set's registers
     constexpr int S = decltype(set_c)::value, N = decltype(n_c)::value;
 #pragma unroll
-    for (int i = 0; i < NDZ; ++i) { u32x4_t& r = rdz[S][i]; asm volatile("s_waitcnt vmcnt(%1)" : "+v"(r) : "n"(N)); }
+    for (int i = 0; i < NDZ; ++i) cyk::vmwait<N>(rdz[S][i]);
     asm volatile("" ::: "memory");                  // (BNF: the z DMAs of the set have landed with its loads: they are older than its x loads)
 #pragma unroll
-    for (int i = 0; i < NX; ++i) { u32x4_t& r = rx[S][i]; asm volatile("s_waitcnt vmcnt(%1)" : "+v"(r) : "n"(N)); }
+    for (int i = 0; i < NX; ++i) cyk::vmwait<N>(rx[S][i]);
   };
   auto store_chunk = [&](auto set_c, int buf) {
     constexpr int S = decltype(set_c)::value;
@@ -1122,7 +1112,7 @@ __global__ __launch_bounds__(64 * NW, 1) void wgrad_bf16_kernel(WgArgs a) {
         u32x4_t ov = pack8(o);
         if ((dzbad[S] >> i) & 1u) ov = u32x4_t{0u, 0u, 0u, 0u};       // outside the image: no pixel, no contribution
         if (c < DZ_CH) *(u32x4_t*)(dzimg + buf * DZ_IMG + px * DZB + q * 16) = ov;
-        wg_store(ov, ozd[S], ((CY_WG_DBG & 8) || ((dzbad[S] >> i) & 1u)) ? 0x80000000u : dzv[i], ozs[S]);
+        cyk::bufstore(ov, ozd[S], ((CY_WG_DBG & 8) || ((dzbad[S] >> i) & 1u)) ? 0x80000000u : dzv[i], ozs[S]);
       } else {
         if (c < DZ_CH) *(u32x4_t*)(dzimg + buf * DZ_IMG + px * DZB + q * 16) = rdz[S][i];
       }

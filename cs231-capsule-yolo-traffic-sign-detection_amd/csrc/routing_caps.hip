@@ -22,6 +22,7 @@ namespace {
 #ifndef CY_B2_DBG
 #define CY_B2_DBG 0
 #endif
+CY_WRONG_RESULT_KNOB(CY_B2_DBG);
 
 // SAVED: the row part (routing_rows.hip, fused plans) left c^t and db^t of every (t >= 1, row, i, j) in `cdb`
 // ([t - 1][row][i][2][C]): this kernel then recomputes neither u_hat (a pass over W_i) nor the logits and the softmax (two

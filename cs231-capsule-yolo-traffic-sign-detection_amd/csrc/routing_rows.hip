@@ -42,6 +42,7 @@ namespace {
 #ifndef CY_ROWS_DBG
 #define CY_ROWS_DBG 0
 #endif
+CY_WRONG_RESULT_KNOB(CY_ROWS_DBG);
 constexpr int DBG = CY_ROWS_DBG;
 
 __device__ __forceinline__ float row16_max(float v) {

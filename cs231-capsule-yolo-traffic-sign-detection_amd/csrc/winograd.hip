@@ -14,7 +14,7 @@
 //   are copied to LDS; each wave then issues 16 positions x 4 MFMAs.  The transform of chunk c+1 and the
 //   global loads of chunk c+2 are issued between the MFMAs of chunk c (three-stage software pipeline, two
 //   barriers per chunk).
-#include "common.h"
+#include "prims.h"
 
 // Nontemporal stores of the (streamed once, 5.7 GB) output keep it from pushing the transformed weights, which every tile
 // re-reads, out of the XCD's 4 MB L2: conv_2 forward fetches 4.9 instead of 8.5 GB -- and runs 13.62 instead of 13.28 ms (the
@@ -31,6 +31,7 @@
 
 
 namespace {
+using namespace cyk;
 
 constexpr int WT = 64;                      // tiles per block (8 x 8)
 constexpr int WN = 64;                      // output channels per block
@@ -56,40 +57,6 @@ struct WinoArgs {
   long long yslab;
 };
 
-__device__ __forceinline__ f32x16 mfma_zero() {
-  f32x16 c;
-  asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %1, 0" : "=a"(c) : "v"(0.f));
-  return c;
-}
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
-// two fp32 adds in one VALU instruction (the compiler splits most float2 adds into two v_add_f32)
-__device__ __forceinline__ f32x2 pk_add(f32x2 x, f32x2 y) {
-  f32x2 r;
-  asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
-  return r;
-}
-__device__ __forceinline__ f32x2 pk_fma(f32x2 x, f32x2 y, f32x2 z) {
-  f32x2 r;
-  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(z));
-  return r;
-}
-__device__ __forceinline__ f32x2 pk_sub(f32x2 x, f32x2 y) {
-  f32x2 r;
-  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(x), "v"(y));
-  return r;
-}
-
-// One accumulator element, read where the statement stands.  Plain `acc[xi][r]` lets the compiler copy ALL 16
-// accumulator vectors AGPR -> VGPR in front of the output transform (256 VGPRs: everything else is spilled).
-__device__ __forceinline__ float acc_elem(float a_elem) {
-  float x;
-  asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x) : "a"(a_elem));
-  return x;
-}
-
 // A fragment read the compiler does not track: with LDS-DMA instructions in the loop hipcc answers every tracked ds_read
 // result with `s_waitcnt lgkmcnt(0)` at its first use (tools/check_lds_waits.py showed it in front of every second
 // position), which throws the counted waits of the schedule away.  The slot's explicit wait is tied to these registers.
@@ -101,9 +68,6 @@ template <int BYTE_OFF> __device__ __forceinline__ void lds_read128(f32x4& dst, 
 template <int OFF0, int OFF1> __device__ __forceinline__ void lds_read2_b64(f32x4& dst, const float* p) {
   const unsigned a_ = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const float*)p;
   asm volatile("ds_read2_b64 %0, %1 offset0:%2 offset1:%3" : "=v"(dst) : "v"(a_), "n"(OFF0), "n"(OFF1));
-}
-__device__ __forceinline__ void mfma32_inplace(f32x16& c, float a, float b) {
-  asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
 }
 template <int N> __device__ __forceinline__ void lgkm_wait(f32x4& x, f32x4& y) {
   asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(x), "+v"(y) : "n"(N));
@@ -148,6 +112,7 @@ constexpr int WS_BAR = 54;                  // barrier; the fragments of the nex
 #ifndef CY_WINO_DBG
 #define CY_WINO_DBG 0
 #endif
+CY_WRONG_RESULT_KNOB(CY_WINO_DBG);
 constexpr int WDBG = CY_WINO_DBG;
 constexpr int wino_side_kind_all(int s);
 constexpr int wino_side_kind(int s) {
@@ -315,25 +280,25 @@ __global__ __launch_bounds__(256, 1) void wino_conv_kernel(WinoArgs a) {
     f32x2 t0[4];
 #pragma unroll
     for (int cc = 0; cc < 4; ++cc)
-      t0[cc] = R == 0 ? pk_sub(xv[0][cc], xv[2][cc]) : R == 1 ? pk_add(xv[1][cc], xv[2][cc])
-             : R == 2 ? pk_sub(xv[2][cc], xv[1][cc]) : pk_sub(xv[1][cc], xv[3][cc]);
-    *(f32x2*)(vb + (R * 4 + 0) * 2 * SLAB) = pk_sub(t0[0], t0[2]);
-    *(f32x2*)(vb + (R * 4 + 1) * 2 * SLAB) = pk_add(t0[1], t0[2]);
-    *(f32x2*)(vb + (R * 4 + 2) * 2 * SLAB) = pk_sub(t0[2], t0[1]);
-    *(f32x2*)(vb + (R * 4 + 3) * 2 * SLAB) = pk_sub(t0[1], t0[3]);
+      t0[cc] = R == 0 ? asm_pk_sub(xv[0][cc], xv[2][cc]) : R == 1 ? asm_pk_add(xv[1][cc], xv[2][cc])
+             : R == 2 ? asm_pk_sub(xv[2][cc], xv[1][cc]) : asm_pk_sub(xv[1][cc], xv[3][cc]);
+    *(f32x2*)(vb + (R * 4 + 0) * 2 * SLAB) = asm_pk_sub(t0[0], t0[2]);
+    *(f32x2*)(vb + (R * 4 + 1) * 2 * SLAB) = asm_pk_add(t0[1], t0[2]);
+    *(f32x2*)(vb + (R * 4 + 2) * 2 * SLAB) = asm_pk_sub(t0[2], t0[1]);
+    *(f32x2*)(vb + (R * 4 + 3) * 2 * SLAB) = asm_pk_sub(t0[1], t0[3]);
   };
   f32x2 t0h[4];                             // the row's column differences, computed by the first half, used by both
   auto Vhalf = [&](float* vb, int R, int jp) {   // columns 2 jp, 2 jp + 1 of row R
     if (jp == 0) {
 #pragma unroll
       for (int cc = 0; cc < 4; ++cc)
-        t0h[cc] = R == 0 ? pk_sub(XQ(0, cc), XQ(2, cc)) : R == 1 ? pk_add(XQ(1, cc), XQ(2, cc))
-                : R == 2 ? pk_sub(XQ(2, cc), XQ(1, cc)) : pk_sub(XQ(1, cc), XQ(3, cc));
-      *(f32x2*)(vb + (R * 4 + 0) * 2 * SLAB) = pk_sub(t0h[0], t0h[2]);
-      *(f32x2*)(vb + (R * 4 + 1) * 2 * SLAB) = pk_add(t0h[1], t0h[2]);
+        t0h[cc] = R == 0 ? asm_pk_sub(XQ(0, cc), XQ(2, cc)) : R == 1 ? asm_pk_add(XQ(1, cc), XQ(2, cc))
+                : R == 2 ? asm_pk_sub(XQ(2, cc), XQ(1, cc)) : asm_pk_sub(XQ(1, cc), XQ(3, cc));
+      *(f32x2*)(vb + (R * 4 + 0) * 2 * SLAB) = asm_pk_sub(t0h[0], t0h[2]);
+      *(f32x2*)(vb + (R * 4 + 1) * 2 * SLAB) = asm_pk_add(t0h[1], t0h[2]);
     } else {
-      *(f32x2*)(vb + (R * 4 + 2) * 2 * SLAB) = pk_sub(t0h[2], t0h[1]);
-      *(f32x2*)(vb + (R * 4 + 3) * 2 * SLAB) = pk_sub(t0h[1], t0h[3]);
+      *(f32x2*)(vb + (R * 4 + 2) * 2 * SLAB) = asm_pk_sub(t0h[2], t0h[1]);
+      *(f32x2*)(vb + (R * 4 + 3) * 2 * SLAB) = asm_pk_sub(t0h[1], t0h[3]);
     }
   };
   auto T = [&](int c) {                     // raw patch -> V (this thread's tile, 2 channels)
@@ -417,7 +382,7 @@ __global__ __launch_bounds__(256, 1) void wino_conv_kernel(WinoArgs a) {
       constexpr int sidx = (SIDX);                                                                  \
       constexpr int xi = wino_xi(sidx), e = wino_e(sidx);                                           \
       if (e == 0) lgkm_wait<wino_younger(xi)>(fa_[xi & 3], fb_[xi & 3]);                            \
-      mfma32_inplace(acc[xi], fa_[xi & 3][e], fb_[xi & 3][e]);   /* volatile asm: stays in front of the slot's reads */ \
+      mfma32_a(acc[xi], fa_[xi & 3][e], fb_[xi & 3][e]);   /* volatile asm: stays in front of the slot's reads */ \
       constexpr int fp = wino_frag_pos(sidx);                                                       \
       if (fp >= 0) {                                                                                \
         constexpr int fq = fp >= 0 ? fp : 0;                                                        \
@@ -518,7 +483,7 @@ __global__ __launch_bounds__(256, 1) void wino_conv_kernel(WinoArgs a) {
     // the accumulators of the next tile: 16 MFMAs with zero operands (0 * 0 + 0) instead of 256 v_accvgpr_write; they
     // run in the matrix pipe while the stores below are issued
 #pragma unroll
-    for (int xi = 0; xi < 16; ++xi) acc[xi] = mfma_zero();
+    for (int xi = 0; xi < 16; ++xi) acc[xi] = mfma32_zero();
     __builtin_amdgcn_sched_barrier(0);
     {
       const int c4 = lane & 7;
@@ -701,17 +666,6 @@ constexpr int wg_younger(int xi) {
   return n > 14 ? 14 : n;
 }
 
-// (dword[O0 * 64], dword[O1 * 64]) from LDS byte address `addr` as ONE aligned register pair.  Plain C++ loads
-// are paired up by the compiler as it likes (adjacent columns) and then shuffled with v_mov + an immediate wait;
-// the transform below needs (column c, column c + 2).  The compiler does not count this read: the consumer slot
-// waits with an explicit s_waitcnt.
-template <int O0, int O1>
-__device__ __forceinline__ f32x2 lds_pair_st64(unsigned addr) {
-  f32x2 r;
-  asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(r) : "v"(addr), "n"(O0), "n"(O1));
-  return r;
-}
-
 // BNF: 0 = plain, 1 = BatchNorm + LeakyReLU backward pass 2 on the way in, 2 = the same for a premasked gradient (no y, no select)
 template <int BNF>
 __global__ __launch_bounds__(256, 1) void wino_wgrad_kernel(WinoWgradArgs a) {
@@ -787,10 +741,10 @@ __global__ __launch_bounds__(256, 1) void wino_wgrad_kernel(WinoWgradArgs a) {
       const f32x2 z = f32x2{zz[q][2 * h], zz[q][2 * h + 1]}, g = f32x2{gz[q][2 * h], gz[q][2 * h + 1]};
       f32x2 sel = k_sc[h];
       if constexpr (BNF == 1) {
-        const f32x2 y = pk_fma(z, k_sc[h], k_sh[h]);
+        const f32x2 y = asm_pk_fma(z, k_sc[h], k_sh[h]);
         sel = f32x2{y[0] > 0.f ? k_sc[h][0] : k_scs[h][0], y[1] > 0.f ? k_sc[h][1] : k_scs[h][1]};
       }
-      const f32x2 o = pk_fma(g, sel, pk_fma(pk_add(z, k_nmu[h]), k_b[h], k_c[h]));
+      const f32x2 o = asm_pk_fma(g, sel, asm_pk_fma(asm_pk_add(z, k_nmu[h]), k_b[h], k_c[h]));
       gd[q][2 * h] = o[0]; gd[q][2 * h + 1] = o[1];
     }
   };
@@ -883,37 +837,37 @@ __global__ __launch_bounds__(256, 1) void wino_wgrad_kernel(WinoWgradArgs a) {
     f32x2 t0[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c)
-      t0[c] = R == 0 ? pk_sub(xv[0][c], xv[2][c]) : R == 1 ? pk_add(xv[1][c], xv[2][c])
-            : R == 2 ? pk_sub(xv[2][c], xv[1][c]) : pk_sub(xv[3][c], xv[1][c]);
-    *(f32x2*)(vb + (R * 4 + 0) * 2 * SLAB) = pk_sub(t0[0], t0[2]);
-    *(f32x2*)(vb + (R * 4 + 1) * 2 * SLAB) = pk_add(t0[1], t0[2]);
-    *(f32x2*)(vb + (R * 4 + 2) * 2 * SLAB) = pk_sub(t0[2], t0[1]);
-    *(f32x2*)(vb + (R * 4 + 3) * 2 * SLAB) = pk_sub(t0[3], t0[1]);
+      t0[c] = R == 0 ? asm_pk_sub(xv[0][c], xv[2][c]) : R == 1 ? asm_pk_add(xv[1][c], xv[2][c])
+            : R == 2 ? asm_pk_sub(xv[2][c], xv[1][c]) : asm_pk_sub(xv[3][c], xv[1][c]);
+    *(f32x2*)(vb + (R * 4 + 0) * 2 * SLAB) = asm_pk_sub(t0[0], t0[2]);
+    *(f32x2*)(vb + (R * 4 + 1) * 2 * SLAB) = asm_pk_add(t0[1], t0[2]);
+    *(f32x2*)(vb + (R * 4 + 2) * 2 * SLAB) = asm_pk_sub(t0[2], t0[1]);
+    *(f32x2*)(vb + (R * 4 + 3) * 2 * SLAB) = asm_pk_sub(t0[3], t0[1]);
   };
   auto Vhalf = [&](float* vb, int R, int jp) {   // columns 2 jp, 2 jp + 1 of row R
     f32x2 t0[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c)
-      t0[c] = R == 0 ? pk_sub(xv[0][c], xv[2][c]) : R == 1 ? pk_add(xv[1][c], xv[2][c])
-            : R == 2 ? pk_sub(xv[2][c], xv[1][c]) : pk_sub(xv[3][c], xv[1][c]);
+      t0[c] = R == 0 ? asm_pk_sub(xv[0][c], xv[2][c]) : R == 1 ? asm_pk_add(xv[1][c], xv[2][c])
+            : R == 2 ? asm_pk_sub(xv[2][c], xv[1][c]) : asm_pk_sub(xv[3][c], xv[1][c]);
     if (jp == 0) {
-      *(f32x2*)(vb + (R * 4 + 0) * 2 * SLAB) = pk_sub(t0[0], t0[2]);
-      *(f32x2*)(vb + (R * 4 + 1) * 2 * SLAB) = pk_add(t0[1], t0[2]);
+      *(f32x2*)(vb + (R * 4 + 0) * 2 * SLAB) = asm_pk_sub(t0[0], t0[2]);
+      *(f32x2*)(vb + (R * 4 + 1) * 2 * SLAB) = asm_pk_add(t0[1], t0[2]);
     } else {
-      *(f32x2*)(vb + (R * 4 + 2) * 2 * SLAB) = pk_sub(t0[2], t0[1]);
-      *(f32x2*)(vb + (R * 4 + 3) * 2 * SLAB) = pk_sub(t0[3], t0[1]);
+      *(f32x2*)(vb + (R * 4 + 2) * 2 * SLAB) = asm_pk_sub(t0[2], t0[1]);
+      *(f32x2*)(vb + (R * 4 + 3) * 2 * SLAB) = asm_pk_sub(t0[3], t0[1]);
     }
   };
   auto Zhalf = [&](float* zb, int R, int jp) {
     f32x2 t0[2];
 #pragma unroll
     for (int c = 0; c < 2; ++c)
-      t0[c] = R == 0 ? zv[0][c] : R == 1 ? pk_add(zv[0][c], zv[1][c]) : R == 2 ? pk_sub(zv[0][c], zv[1][c]) : zv[1][c];
+      t0[c] = R == 0 ? zv[0][c] : R == 1 ? asm_pk_add(zv[0][c], zv[1][c]) : R == 2 ? asm_pk_sub(zv[0][c], zv[1][c]) : zv[1][c];
     if (jp == 0) {
       *(f32x2*)(zb + (R * 4 + 0) * 2 * SLAB) = t0[0];
-      *(f32x2*)(zb + (R * 4 + 1) * 2 * SLAB) = pk_add(t0[0], t0[1]);
+      *(f32x2*)(zb + (R * 4 + 1) * 2 * SLAB) = asm_pk_add(t0[0], t0[1]);
     } else {
-      *(f32x2*)(zb + (R * 4 + 2) * 2 * SLAB) = pk_sub(t0[0], t0[1]);
+      *(f32x2*)(zb + (R * 4 + 2) * 2 * SLAB) = asm_pk_sub(t0[0], t0[1]);
       *(f32x2*)(zb + (R * 4 + 3) * 2 * SLAB) = t0[1];
     }
   };
@@ -921,10 +875,10 @@ __global__ __launch_bounds__(256, 1) void wino_wgrad_kernel(WinoWgradArgs a) {
     f32x2 t0[2];
 #pragma unroll
     for (int c = 0; c < 2; ++c)
-      t0[c] = R == 0 ? zv[0][c] : R == 1 ? pk_add(zv[0][c], zv[1][c]) : R == 2 ? pk_sub(zv[0][c], zv[1][c]) : zv[1][c];
+      t0[c] = R == 0 ? zv[0][c] : R == 1 ? asm_pk_add(zv[0][c], zv[1][c]) : R == 2 ? asm_pk_sub(zv[0][c], zv[1][c]) : zv[1][c];
     *(f32x2*)(zb + (R * 4 + 0) * 2 * SLAB) = t0[0];
-    *(f32x2*)(zb + (R * 4 + 1) * 2 * SLAB) = pk_add(t0[0], t0[1]);
-    *(f32x2*)(zb + (R * 4 + 2) * 2 * SLAB) = pk_sub(t0[0], t0[1]);
+    *(f32x2*)(zb + (R * 4 + 1) * 2 * SLAB) = asm_pk_add(t0[0], t0[1]);
+    *(f32x2*)(zb + (R * 4 + 2) * 2 * SLAB) = asm_pk_sub(t0[0], t0[1]);
     *(f32x2*)(zb + (R * 4 + 3) * 2 * SLAB) = t0[1];
   };
 
@@ -1165,8 +1119,8 @@ __global__ void wino_split_sum_kernel(const float* __restrict__ ws, float* __res
 // shares of the reduction for a launch without an epilogue (input gradients): at most 4, at least 16 chunks of 8 channels each
 int wino_shares(int B, int H, int W, int Cin, int Cout, int plain) {
   if (!plain || Cout % 4 != 0) return 1;
-  int dev = 0, ncu = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) return 1;
+  const int ncu = cyi_cu_count();
+  if (ncu == 0) return 1;
   const long long tiles = (long long)B * ((H + 15) / 16) * ((W + 15) / 16) * ((Cout + 63) / 64);
   long long S = ncu / (tiles > 0 ? tiles : 1);
   if (S > 4) S = 4;
@@ -1215,22 +1169,16 @@ extern "C" int cy_conv3x3_winograd_ws(const float* X, const float* U, float* Y, 
     }
   }
   a.ntiles = (int)tiles;
-  int dev = 0, ncu = 0;
-  hipError_t he = hipGetDevice(&dev);
-  if (he == hipSuccess) he = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  if (he != hipSuccess || ncu <= 0) return cy_set_error((int)he, "cy_conv3x3_winograd: cannot query the CU count: %s", hipGetErrorString(he));
-  const long long blocks = tiles < ncu ? tiles : ncu;   // persistent: one block per CU (155 KB of LDS, 512 registers per lane)
+  long long blocks = 0;                                 // persistent: one block per CU (155 KB of LDS, 512 registers per lane)
+  if (int rc = cyi_persistent_blocks("cy_conv3x3_winograd", tiles, &blocks)) return rc;
   const size_t lds = (size_t)(4 * VU_BUF + 2 * RAW_BUF) * 4;
-  int rc = cy_allow_lds(wino_conv_kernel<1>, lds);
+  const char* who = "cy_conv3x3_winograd";
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if (a.stats != nullptr) rc = cyi_launch_lds(who, wino_conv_kernel<1>, (unsigned)blocks, 256, lds, st, a);
+  else if (out_slope == 1.f) rc = cyi_launch_lds(who, wino_conv_kernel<0>, dim3((unsigned)blocks, (unsigned)S), 256, lds, st, a);
+  else rc = cyi_launch_lds(who, wino_conv_kernel<2>, (unsigned)blocks, 256, lds, st, a);
   if (rc) return rc;
-  rc = cy_allow_lds(wino_conv_kernel<0>, lds);
-  if (rc) return rc;
-  rc = cy_allow_lds(wino_conv_kernel<2>, lds);
-  if (rc) return rc;
-  if (a.stats != nullptr) wino_conv_kernel<1><<<(unsigned)blocks, 256, lds, (hipStream_t)stream>>>(a);
-  else if (out_slope != 1.f) wino_conv_kernel<2><<<(unsigned)blocks, 256, lds, (hipStream_t)stream>>>(a);
-  else wino_conv_kernel<0><<<dim3((unsigned)blocks, (unsigned)S), 256, lds, (hipStream_t)stream>>>(a);
-  CY_LAUNCH_CHECK("cy_conv3x3_winograd");
   if (S > 1) {
     const long long n4 = a.yslab / 4;
     wino_split_sum_kernel<<<(unsigned)cy_ceil_div(n4, 256), 256, 0, (hipStream_t)stream>>>(ws, Y, S, n4);
@@ -1266,16 +1214,11 @@ static int wino_wgrad_launch(WinoWgradArgs a, bool bnf, float* dW, float* ws, co
   CY_REQUIRE(gtot < (1ll << 31), "%s: too many tile groups", who);
   const long long blocks = (long long)a.nrange * (Cin / 64) * (Cout / 64);
   const size_t lds = (size_t)(4 * VU_BUF + RAWW_BUF) * 4;
-  int rc = cy_allow_lds(wino_wgrad_kernel<0>, lds);
+  int rc;
+  if (!bnf) rc = cyi_launch_lds(who, wino_wgrad_kernel<0>, (unsigned)blocks, 256, lds, s, a);
+  else if (!a.premasked) rc = cyi_launch_lds(who, wino_wgrad_kernel<1>, (unsigned)blocks, 256, lds, s, a);
+  else rc = cyi_launch_lds(who, wino_wgrad_kernel<2>, (unsigned)blocks, 256, lds, s, a);
   if (rc) return rc;
-  rc = cy_allow_lds(wino_wgrad_kernel<1>, lds);
-  if (rc) return rc;
-  rc = cy_allow_lds(wino_wgrad_kernel<2>, lds);
-  if (rc) return rc;
-  if (bnf && a.premasked) wino_wgrad_kernel<2><<<(unsigned)blocks, 256, lds, s>>>(a);
-  else if (bnf) wino_wgrad_kernel<1><<<(unsigned)blocks, 256, lds, s>>>(a);
-  else wino_wgrad_kernel<0><<<(unsigned)blocks, 256, lds, s>>>(a);
-  CY_LAUNCH_CHECK(who);
   const long long n = (long long)Cin * Cout;
   wino_wgrad_finish_kernel<<<(unsigned)cy_ceil_div(n, 256), 256, 0, s>>>(ws, dW, a.nrange, Cin, Cout);
   CY_LAUNCH_CHECK(who);

@@ -22,15 +22,17 @@
 // the current tile's last chunks).  The loop's global loads (input patch, B-operand ring of F4_NBR position pairs) are inline asm
 // with hand-counted `s_waitcnt vmcnt(N)` (hipcc's own bookkeeping drew vmcnt(0) at the loop header); tools/check_vmcnt.py replays them.
 #include <type_traits>
-#include "common.h"
+#include "prims.h"
 
 namespace {
+using namespace cyk;
 
 // developer knob for timing experiments (results are wrong when set): drop 1 the input transform's arithmetic and V stores,
 // 2 the patch loads / stores, 4 the B-operand loads, 8 the accumulator drain, 16 the transform's patch reads
 #ifndef CY_F4_DBG
 #define CY_F4_DBG 0
 #endif
+CY_WRONG_RESULT_KNOB(CY_F4_DBG);
 constexpr int F4DBG = CY_F4_DBG;
 
 constexpr int F4_PC = 34;                       // patch columns: 8 tiles x 4 + 2
@@ -61,49 +63,21 @@ struct Wino4Args {
   float out_slope;                              // EPI == 2: Y = lrelu(conv + bias) (eval forward, BatchNorm folded into U / bias)
 };
 
-__device__ __forceinline__ void mfma16_a(f32x4& c, float a, float b) {
-  asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma16_v(f32x4& c, float a, float b) {
-  asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
-// packed fp32 arithmetic as plain vector expressions: hipcc selects v_pk_fma_f32 / v_pk_add_f32 for them on gfx950 (with inline
-// constants and neg modifiers), and -- unlike inline-asm statements -- needs no s_nop pad between two dependent ones
-__device__ __forceinline__ f32x2 pkfma(f32x2 x, f32x2 y, f32x2 z) { return __builtin_elementwise_fma(x, y, z); }    // x * y + z
-__device__ __forceinline__ f32x2 pkfnma(f32x2 x, f32x2 y, f32x2 z) { return __builtin_elementwise_fma(-x, y, z); }  // z - x * y
-__device__ __forceinline__ f32x2 pkadd(f32x2 x, f32x2 y) { return x + y; }
-__device__ __forceinline__ f32x2 pksub(f32x2 x, f32x2 y) { return x - y; }
-// The B-operand ring is loaded and waited for by hand: tracked by hipcc, the loop header of the chunk loop waited vmcnt(0)
-// (the join of the loop's back edge with its entry), i.e. for the B loads issued in the chunk's last slots.  The counted
-// wait in front of a pair's first MFMA is the EXACT number of vector-memory operations the schedule issues between the
-// pair's load and that MFMA (f4_younger_b: with a flat vmcnt(4) the in-order counter made pair 2 wait for the patch loads
-// issued a few slots earlier, i.e. for HBM latency: the first third of a chunk took 2.3x its MFMA time); output stores of a
-// drain in between only add younger operations.
+// The B-operand ring is loaded and waited for by hand (cyk::gload / vmwait): tracked by hipcc, the loop header of the chunk loop
+// waited vmcnt(0), i.e. for the B loads issued in the chunk's last slots.  The counted wait in front of a pair's first MFMA is the
+// EXACT number of vector-memory operations the schedule issues between the pair's load and that MFMA (f4_younger_b: with a flat
+// vmcnt(4) the in-order counter made pair 2 wait for the patch loads issued a few slots earlier, i.e. for HBM latency: the first
+// third of a chunk took 2.3x its MFMA time); output stores of a drain in between only add younger operations.
 template <int OFF> __device__ __forceinline__ void bload(f32x4& dst, const char* base, unsigned voff) {
   if constexpr (CY_F4_DBG & 4) dst = f32x4{1.f, 1.f, 1.f, 1.f};
-  else asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(base), "n"(OFF));
+  else gload<OFF>(dst, base, voff);
 }
-template <int N> __device__ __forceinline__ void vmwait(f32x4& x) { asm volatile("s_waitcnt vmcnt(%1)" : "+v"(x) : "n"(N)); }
-// ... and so are the patch loads (a tracked load pending at the loop header draws the same vmcnt(0), which would then also
-// wait for the youngest ring loads).  A patch item is stored to LDS one chunk after its load; its wait counts the operations
-// younger than the load in the FIRST chunk of a block (f4_younger_r: 4 - q patch loads + the 6 ring loads of the prologue +
-// what the chunk has issued by then), fewer than in any later chunk.
+// ... and so are the patch loads (cyk::bufload; a tracked load pending at the loop header draws the same vmcnt(0), which would
+// then also wait for the youngest ring loads).  A patch item is stored to LDS one chunk after its load; its wait counts the
+// operations younger than the load in the FIRST chunk of a block (f4_younger_r: 4 - q patch loads + the 6 ring loads of the
+// prologue + what the chunk has issued by then), fewer than in any later chunk.
 // The patch is read through a buffer descriptor of ONE image (base = the image, num_records = its bytes): a padding item
-// gets an offset beyond the image and the hardware's range check returns zeros -- no select, no zero page, no masks; the
-// chunk's channel offset travels as the instruction's scalar offset (no vector add per chunk).
-typedef int i32x4_ __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void rload(f32x4& dst, i32x4_ desc, unsigned voff, unsigned soff) {
-#ifndef CY_F4_RLOAD_AUX
-#define CY_F4_RLOAD_AUX ""
-#endif
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" CY_F4_RLOAD_AUX : "=v"(dst) : "v"(voff), "s"(desc), "s"(soff));
-}
-__device__ __forceinline__ void rwait0(f32x4& x) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(x)); }
-__device__ __forceinline__ float acc_elem4(float a_elem) {    // one accumulator element, read where the statement stands
-  float x;
-  asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x) : "a"(a_elem));
-  return x;
-}
+// gets an offset beyond the image; the chunk's channel offset travels as the instruction's scalar offset.
 
 // ---- compile-time schedule of one chunk: 144 slots; slot s issues the MFMA of position s >> 2, tile half s & 1, k-step
 // (s >> 1) & 1 (consecutive MFMAs alternate between the position's two accumulators).  The A fragment of position p + 2 (both
@@ -161,7 +135,7 @@ constexpr int f4_younger_b(int q) {
   return q >= F4_NBR ? f4_vm_between(f4_slot_of(1, q - F4_NBR) + 1, 8 * q)
                      : f4_vm_between(f4_slot_of(1, q + 18 - F4_NBR) + 1, 144) + f4_vm_between(0, 8 * q);
 }
-// operations younger than the load of patch item q when S_raw(q) stores it, first chunk of a block (see rload)
+// operations younger than the load of patch item q when S_raw(q) stores it, first chunk of a block (see bufload)
 constexpr int f4_younger_r(int q) { return (F4_NQ - 1 - q) + F4_NBR + f4_vm_between(0, f4_slot_of(3, q)); }
 
 // EPI: 0 plain (input gradient), 1 BatchNorm statistics (training forward), 2 LeakyReLU (eval forward, BatchNorm folded)
@@ -200,12 +174,11 @@ __global__ __launch_bounds__(256, 1) void wino4_conv_kernel(Wino4Args a) {
   const bool rlast_ok = pix0 + 128 * (F4_NQ - 1) < F4_NPIX;
   const int roff4 = roff0 + 512 * (rlast_ok ? F4_NQ - 1 : F4_NQ - 2);
   unsigned goff[F4_NQ];                         // byte offset of the item's pixel, channel quad, from the image base; padding: 2^31
-  i32x4_ xdesc = {0, 0, 0, 0};                  // uniform: buffer descriptor of the patch cursor's image
+  i32x4 xdesc = {0, 0, 0, 0};                   // uniform: buffer descriptor of the patch cursor's image
   const int img_bytes = a.H * a.W * a.Cin * 4;
   auto set_raw_tile = [&](int k) {
     const TilePos p = tile_pos(k);
-    const unsigned long long xb = (unsigned long long)(uintptr_t)(a.X + (long long)p.b * a.H * a.W * a.Cin);
-    xdesc = i32x4_{(int)(unsigned)xb, (int)(unsigned)((xb >> 32) & 0xffffu), img_bytes, 0x00020000};
+    xdesc = bufdesc(a.X + (long long)p.b * a.H * a.W * a.Cin, img_bytes);
 #pragma unroll
     for (int q = 0; q < F4_NQ; ++q) {
       const int pix = pix0 + 128 * ((q < F4_NQ - 1 || rlast_ok) ? q : q - 1);
@@ -222,7 +195,7 @@ __global__ __launch_bounds__(256, 1) void wino4_conv_kernel(Wino4Args a) {
   };
   int kr = 0, cr = 0;                           // patch cursor
   f32x4 graw[F4_NQ];
-  auto Graw1 = [&](int q, int c, f32x4& dst) { rload(dst, xdesc, goff[q], (unsigned)c * 32u); };
+  auto Graw1 = [&](int q, int c, f32x4& dst) { bufload(dst, xdesc, goff[q], (unsigned)c * 32u); };
   auto Sraw1 = [&](float* rb, int q, const f32x4& src) { *(f32x4*)(rb + (q < F4_NQ - 1 ? roff0 + 512 * q : roff4)) = src; };
 
   // ---- B operand stream: U[nb][chunk][wave][pair 18][lane][4]
@@ -316,7 +289,7 @@ __global__ __launch_bounds__(256, 1) void wino4_conv_kernel(Wino4Args a) {
 #pragma unroll
     for (int q = 0; q < F4_NQ; ++q) Graw1(q, 0, graw[q]);
 #pragma unroll
-    for (int q = 0; q < F4_NQ; ++q) rwait0(graw[q]);
+    for (int q = 0; q < F4_NQ; ++q) vmwait<0>(graw[q]);
 #pragma unroll
     for (int q = 0; q < F4_NQ; ++q) Sraw1(Rs, q, graw[q]);
     if (advance(kr, cr)) set_raw_tile(kr);
@@ -325,7 +298,7 @@ __global__ __launch_bounds__(256, 1) void wino4_conv_kernel(Wino4Args a) {
     __syncthreads();
     Tall(0, 0);
 #pragma unroll
-    for (int q = 0; q < F4_NQ; ++q) rwait0(graw1[q]);
+    for (int q = 0; q < F4_NQ; ++q) vmwait<0>(graw1[q]);
 #pragma unroll
     for (int q = 0; q < F4_NQ; ++q) Sraw1(Rs + F4_RAW_BUF, q, graw1[q]);
     if (advance(kr, cr)) set_raw_tile(kr);
@@ -473,7 +446,7 @@ __global__ __launch_bounds__(256, 1) void wino4_conv_kernel(Wino4Args a) {
 #pragma unroll
           for (int j = 0; j < 6; ++j) {
             const int p = 6 * i + j;
-            m[j] = p < 32 ? acc_elem4(accA[p < 32 ? p : 0][h][r]) : accV[p >= 32 ? p - 32 : 0][h][r];
+            m[j] = p < 32 ? acc_elem(accA[p < 32 ? p : 0][h][r]) : accV[p >= 32 ? p - 32 : 0][h][r];
           }
           const float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
           S[i][0] = (m[0] + s12) + s34;
@@ -538,8 +511,8 @@ __global__ __launch_bounds__(256, 1) void wino4_conv_kernel(Wino4Args a) {
 #pragma unroll
           for (int j = 0; j < 6; ++j) {
             const int p = 6 * i + j;
-            m[j][0] = p < 32 ? acc_elem4(accA[p < 32 ? p : 0][h][r0]) : accV[p >= 32 ? p - 32 : 0][h][r0];
-            m[j][1] = p < 32 ? acc_elem4(accA[p < 32 ? p : 0][h][r0 + 1]) : accV[p >= 32 ? p - 32 : 0][h][r0 + 1];
+            m[j][0] = p < 32 ? acc_elem(accA[p < 32 ? p : 0][h][r0]) : accV[p >= 32 ? p - 32 : 0][h][r0];
+            m[j][1] = p < 32 ? acc_elem(accA[p < 32 ? p : 0][h][r0 + 1]) : accV[p >= 32 ? p - 32 : 0][h][r0 + 1];
           }
           const f32x2 s12 = pkadd(m[1], m[2]), d12 = pksub(m[1], m[2]), s34 = pkadd(m[3], m[4]), d34 = pksub(m[3], m[4]);
           S[i][0] = pkadd(pkadd(m[0], s12), s34);
@@ -672,23 +645,14 @@ extern "C" int cy_conv3x3_winograd4(const float* X, const float* U, float* Y, co
   const long long tiles = (long long)B * a.tbh * a.tbw * (a.Np / 64);
   CY_REQUIRE(tiles < (1ll << 31), "cy_conv3x3_winograd4: too many tiles");
   a.ntiles = (int)tiles;
-  int dev = 0, ncu = 0;
-  hipError_t he = hipGetDevice(&dev);
-  if (he == hipSuccess) he = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  if (he != hipSuccess || ncu <= 0) return cy_set_error((int)he, "cy_conv3x3_winograd4: cannot query the CU count: %s", hipGetErrorString(he));
-  const long long blocks = tiles < ncu ? tiles : ncu;   // persistent: one block per CU (512 registers per lane)
+  long long blocks = 0;                                 // persistent: one block per CU (512 registers per lane)
+  if (int rc = cyi_persistent_blocks("cy_conv3x3_winograd4", tiles, &blocks)) return rc;
   const size_t lds = (size_t)(2 * F4_V_BUF + 2 * F4_RAW_BUF) * 4;
-  int rc = cy_allow_lds(wino4_conv_kernel<1>, lds);
-  if (rc) return rc;
-  rc = cy_allow_lds(wino4_conv_kernel<0>, lds);
-  if (rc) return rc;
-  rc = cy_allow_lds(wino4_conv_kernel<2>, lds);
-  if (rc) return rc;
-  if (a.stats != nullptr) wino4_conv_kernel<1><<<(unsigned)blocks, 256, lds, (hipStream_t)stream>>>(a);
-  else if (out_slope != 1.f) wino4_conv_kernel<2><<<(unsigned)blocks, 256, lds, (hipStream_t)stream>>>(a);
-  else wino4_conv_kernel<0><<<(unsigned)blocks, 256, lds, (hipStream_t)stream>>>(a);
-  CY_LAUNCH_CHECK("cy_conv3x3_winograd4");
-  return 0;
+  const char* who = "cy_conv3x3_winograd4";
+  hipStream_t s = (hipStream_t)stream;
+  if (a.stats != nullptr) return cyi_launch_lds(who, wino4_conv_kernel<1>, (unsigned)blocks, 256, lds, s, a);
+  if (out_slope == 1.f) return cyi_launch_lds(who, wino4_conv_kernel<0>, (unsigned)blocks, 256, lds, s, a);
+  return cyi_launch_lds(who, wino4_conv_kernel<2>, (unsigned)blocks, 256, lds, s, a);
 }
 
 #ifdef CY_F4_PROF

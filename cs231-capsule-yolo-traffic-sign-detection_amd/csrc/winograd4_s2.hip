@@ -20,9 +20,10 @@
 // AFFINE: the input is lrelu(X * in_scale[c] + in_shift[c]) (the producer's BatchNorm + LeakyReLU, applied on the way into LDS;
 // padding stays exactly 0 through a select on the item's saved validity).
 #include <type_traits>
-#include "common.h"
+#include "prims.h"
 
 namespace {
+using namespace cyk;
 
 constexpr int H4_PC = 33;                       // patch columns of X' (8 tiles x 4 + 1)
 constexpr int H4_NPIX = 17 * 33;                // 561
@@ -33,8 +34,6 @@ constexpr int H4_NQ = 5;                        // patch float4 items per thread
 constexpr int H4_NP = 13;                       // position pairs (the 26th position does not exist: its B operand is zero, never used)
 constexpr int H4_OG = 272, H4_OSTEP = 4 * H4_OG;
 constexpr int H4_BAR = 92;                      // slot of the chunk's barrier (every fragment read of the chunk was issued at slot 88)
-
-typedef int i32x4h_ __attribute__((ext_vector_type(4)));
 
 struct Wino4S2Args {
   const float* X; const float* U; float* Y; const float* bias; double* stats;
@@ -50,23 +49,6 @@ struct Wino4S2Args {
   const float* bn_z; const float* bn_scale; const float* bn_shift; const float* bn_mean; const float* bn_invstd;
   double* bn_red; float bn_slope;
 };
-
-__device__ __forceinline__ void h4_mfma(f32x4& c, float a, float b) {
-  asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ f32x2 h4_fma(f32x2 x, f32x2 y, f32x2 z) { return __builtin_elementwise_fma(x, y, z); }
-template <int OFF> __device__ __forceinline__ void h4_bload(f32x4& dst, const char* base, unsigned voff) {
-  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(base), "n"(OFF));
-}
-__device__ __forceinline__ void h4_rload(f32x4& dst, i32x4h_ desc, unsigned voff, unsigned soff) {
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(dst) : "v"(voff), "s"(desc), "s"(soff));
-}
-template <int N> __device__ __forceinline__ void h4_vmwait(f32x4& x) { asm volatile("s_waitcnt vmcnt(%1)" : "+v"(x) : "n"(N)); }
-__device__ __forceinline__ float h4_acc_elem(float a_elem) {
-  float x;
-  asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x) : "a"(a_elem));
-  return x;
-}
 
 // ---- compile-time schedule of one chunk: 100 slots; slot s issues the MFMA of position s >> 2, tile half s & 1, k-step (s >> 1) & 1.
 // The A fragment of position p + 2 is fetched in slot 4p.  Pieces (one per slot):
@@ -178,15 +160,16 @@ __device__ __forceinline__ void h4_run(const Wino4S2Args& a, float* smem) {
   const bool rlast_ok = pix0 + 128 * (H4_NQ - 1) < H4_NPIX;
   const int roff4 = roff0 + 512 * (rlast_ok ? H4_NQ - 1 : H4_NQ - 2);
   unsigned gvoff[H4_NQ], hfl[H4_NQ];            // offset of class (0, 0) from the shifted base; border flags (bits 28..31)
-  i32x4h_ xdesc = {0, 0, 0, 0};
+  i32x4 xdesc = {0, 0, 0, 0};
   const int xshift = (a.W + 1) * a.Cin * 4;
   const int img_bytes = a.H * a.W * a.Cin * 4;
   auto set_raw_tile = [&](int k) {
     const TilePos p = tile_pos(k);
     const unsigned long long xb = (unsigned long long)(uintptr_t)((const char*)(a.X + (long long)p.b * a.H * a.W * a.Cin) - xshift);
-    // (readfirstlane: an "s" asm operand must be provably uniform, and the image index comes out of vector-float divisions)
-    xdesc = i32x4h_{__builtin_amdgcn_readfirstlane((int)(unsigned)xb), __builtin_amdgcn_readfirstlane((int)(unsigned)((xb >> 32) & 0xffffu)),
-                    __builtin_amdgcn_readfirstlane(img_bytes + xshift), 0x00020000};
+    // (readfirstlane: an "s" asm operand must be provably uniform, and the image index comes out of vector-float divisions.  Open-coded:
+    // through cyk::bufdesc the size is summed in front of the address words, and the kernels' scalar setup code comes out reordered)
+    xdesc = i32x4{__builtin_amdgcn_readfirstlane((int)(unsigned)xb), __builtin_amdgcn_readfirstlane((int)(unsigned)((xb >> 32) & 0xffffu)),
+                  __builtin_amdgcn_readfirstlane(img_bytes + xshift), 0x00020000};
 #pragma unroll
     for (int q = 0; q < H4_NQ; ++q) {
       const int pix = pix0 + 128 * ((q < H4_NQ - 1 || rlast_ok) ? q : q - 1);
@@ -228,8 +211,8 @@ __device__ __forceinline__ void h4_run(const Wino4S2Args& a, float* smem) {
   unsigned hv[H4_NQ];                           // AFFINE: (flags & class mask) of the item held in graw: nonzero = padding
   int sc0 = 0;                                  // AFFINE: first channel of the chunk held in graw
   auto Graw1 = [&](int q, f32x4& dst, unsigned& hvq) {
-    if constexpr (AFFINE) { hvq = hfl[q] & rbt; h4_rload(dst, xdesc, hvq | gvoff[q], rsoff); }
-    else h4_rload(dst, xdesc, (hfl[q] & rbt) | gvoff[q], rsoff);
+    if constexpr (AFFINE) { hvq = hfl[q] & rbt; bufload(dst, xdesc, hvq | gvoff[q], rsoff); }
+    else bufload(dst, xdesc, (hfl[q] & rbt) | gvoff[q], rsoff);
   };
   f32x4 asc = {1.f, 1.f, 1.f, 1.f}, ash = {0.f, 0.f, 0.f, 0.f};
   auto set_affine = [&](int c0) {
@@ -290,12 +273,12 @@ __device__ __forceinline__ void h4_run(const Wino4S2Args& a, float* smem) {
   auto Tcol = [&](int c, int part) {
     const f32x2* d = dc[c & 1];
     if constexpr (ROLE == 0) {                  // t0 = 2 d0 + d1 - 2 d2 - d3,  t4 = -2 d1 - d2 + 2 d3 + d4
-      if (part == 0) { ca_[0] = h4_fma(k2, d[0], d[1]); ca_[1] = h4_fma(km2, d[1], d[4]); }
-      else if (part == 1) { cb_[0] = h4_fma(km2, d[2], ca_[0]); cb_[1] = h4_fma(k2, d[3], ca_[1]); }
+      if (part == 0) { ca_[0] = pkfma(k2, d[0], d[1]); ca_[1] = pkfma(km2, d[1], d[4]); }
+      else if (part == 1) { cb_[0] = pkfma(km2, d[2], ca_[0]); cb_[1] = pkfma(k2, d[3], ca_[1]); }
       else { tt[0][c] = cb_[0] - d[3]; tt[1][c] = cb_[1] - d[2]; }
     } else {                                    // t1 = 2 d1 + 3 d2 + d3,  t2 = -2 d1 + d2 + d3,  t3 = d1 - d3
-      if (part == 0) { ca_[0] = h4_fma(k2, d[1], d[3]); ca_[1] = h4_fma(km2, d[1], d[3]); tt[2][c] = d[1] - d[3]; }
-      else { tt[0][c] = h4_fma(k3, d[2], ca_[0]); tt[1][c] = ca_[1] + d[2]; }
+      if (part == 0) { ca_[0] = pkfma(k2, d[1], d[3]); ca_[1] = pkfma(km2, d[1], d[3]); tt[2][c] = d[1] - d[3]; }
+      else { tt[0][c] = pkfma(k3, d[2], ca_[0]); tt[1][c] = ca_[1] + d[2]; }
     }
   };
   f32x2 rp_[4], rq_[2];
@@ -303,15 +286,15 @@ __device__ __forceinline__ void h4_run(const Wino4S2Args& a, float* smem) {
     const f32x2* x = tt[k];
     float* v = vb + vdst + (5 * row_of(k)) * 256;
     if (part == 0) {
-      rp_[0] = h4_fma(k2, x[0], x[1]);
-      rp_[1] = h4_fma(k2, x[1], x[3]);
-      rp_[2] = h4_fma(km2, x[1], x[3]);
-      rp_[3] = h4_fma(km2, x[1], x[4]);
+      rp_[0] = pkfma(k2, x[0], x[1]);
+      rp_[1] = pkfma(k2, x[1], x[3]);
+      rp_[2] = pkfma(km2, x[1], x[3]);
+      rp_[3] = pkfma(km2, x[1], x[4]);
       *(f32x2*)(v + 3 * 256) = x[1] - x[3];
     } else if (part == 1) {
-      rq_[0] = h4_fma(km2, x[2], rp_[0]);
-      rq_[1] = h4_fma(k2, x[3], rp_[3]);
-      *(f32x2*)(v + 1 * 256) = h4_fma(k3, x[2], rp_[1]);
+      rq_[0] = pkfma(km2, x[2], rp_[0]);
+      rq_[1] = pkfma(k2, x[3], rp_[3]);
+      *(f32x2*)(v + 1 * 256) = pkfma(k3, x[2], rp_[1]);
       *(f32x2*)(v + 2 * 256) = rp_[2] + x[2];
     } else {
       *(f32x2*)(v + 0 * 256) = rq_[0] - x[3];
@@ -345,7 +328,7 @@ __device__ __forceinline__ void h4_run(const Wino4S2Args& a, float* smem) {
     for (int q = 0; q < H4_NQ; ++q) Graw1(q, graw[q], hv[q]);
     set_affine(rc0);
 #pragma unroll
-    for (int q = 0; q < H4_NQ; ++q) h4_vmwait<0>(graw[q]);
+    for (int q = 0; q < H4_NQ; ++q) vmwait<0>(graw[q]);
 #pragma unroll
     for (int q = 0; q < H4_NQ; ++q) Sraw1(Rs, q, graw[q], hv[q]);
     if (advance(kr, cr)) set_raw_tile(kr);
@@ -357,7 +340,7 @@ __device__ __forceinline__ void h4_run(const Wino4S2Args& a, float* smem) {
     Tall(0, 0);
     set_affine(c1);
 #pragma unroll
-    for (int q = 0; q < H4_NQ; ++q) h4_vmwait<0>(graw1[q]);
+    for (int q = 0; q < H4_NQ; ++q) vmwait<0>(graw1[q]);
 #pragma unroll
     for (int q = 0; q < H4_NQ; ++q) Sraw1(Rs + H4_RAW_BUF, q, graw1[q], hv1[q]);
     if (advance(kr, cr)) set_raw_tile(kr);
@@ -373,7 +356,7 @@ __device__ __forceinline__ void h4_run(const Wino4S2Args& a, float* smem) {
   if (advance(ku, cu)) {}
   const char* up_nxt = u_ptr(ku, cu);
 #pragma unroll
-  for (int q = 0; q < H4_NP; ++q) h4_bload<0>(bq[q], up_cur + (q & 3) * 1024, ulane[q >> 2]);
+  for (int q = 0; q < H4_NP; ++q) gload<0>(bq[q], up_cur + (q & 3) * 1024, ulane[q >> 2]);
 
   const int kgl = lane >> 4, ml = lane & 15;
   const int fragA = (kgl * 16 + (ml ^ (2 * kgl))) * 4;
@@ -419,19 +402,19 @@ __device__ __forceinline__ void h4_run(const Wino4S2Args& a, float* smem) {
       {                                                                                               \
         constexpr int s_ = (SIDX), p_ = s_ >> 2, w_ = s_ & 3, h_ = w_ & 1, ks_ = w_ >> 1, q_ = p_ >> 1; \
         if (s_ == H4_BAR) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");             \
-        if (w_ == 0 && (p_ & 1) == 0) h4_vmwait<h4_younger_b(ROLE, q_)>(bq[q_]);                      \
-        h4_mfma(acc[p_][h_], fa[p_ % 5][2 * h_ + ks_], bq[q_][2 * (p_ & 1) + ks_]);                   \
+        if (w_ == 0 && (p_ & 1) == 0) vmwait<h4_younger_b(ROLE, q_)>(bq[q_]);                         \
+        mfma16_a(acc[p_][h_], fa[p_ % 5][2 * h_ + ks_], bq[q_][2 * (p_ & 1) + ks_]);                  \
         if (w_ == 0 && p_ + 2 < 25) fa[(p_ + 2) % 5] = *(const f32x4*)(va_ + (p_ + 2) * 256);         \
         if (s_ == H4_BAR) fa[0] = *(const f32x4*)(vw_ + fragA);                                       \
         if (s_ == H4_BAR + 4) fa[1] = *(const f32x4*)(vw_ + fragA + 256);                             \
         constexpr int kind = h4_kind(ROLE, s_), k_ = h4_idx(ROLE, s_);                                \
         if (kind == 1) {                                                                              \
           if (k_ == 0) set_affine(sc0);                                                               \
-          h4_vmwait<h4_younger_r(k_ % H4_NQ)>(graw[k_ % H4_NQ]);                                      \
+          vmwait<h4_younger_r(k_ % H4_NQ)>(graw[k_ % H4_NQ]);                                         \
           Sraw1(rw_, k_ % H4_NQ, graw[k_ % H4_NQ], hv[k_ % H4_NQ]);                                   \
           Graw1(k_ % H4_NQ, graw[k_ % H4_NQ], hv[k_ % H4_NQ]);                                        \
         } else if (kind == 2) {                 /* pair k_ of the next chunk into the register pair k_ just left */ \
-          h4_bload<(k_ & 3) * 1024>(bq[k_ % H4_NP], up_nxt, ulane[(k_ % H4_NP) >> 2]);                \
+          gload<(k_ & 3) * 1024>(bq[k_ % H4_NP], up_nxt, ulane[(k_ % H4_NP) >> 2]);                                 \
         } else if (kind == 3) {                                                                       \
           Trd(rb_, k_ % 5);                                                                           \
         } else if (kind == 4) {                                                                       \
@@ -502,21 +485,21 @@ __device__ __forceinline__ void h4_run(const Wino4S2Args& a, float* smem) {
         for (int i = 0; i < 5; ++i) {
           f32x2 m[5];
 #pragma unroll
-          for (int j = 0; j < 5; ++j) { m[j][0] = h4_acc_elem(acc[5 * i + j][h][r0]); m[j][1] = h4_acc_elem(acc[5 * i + j][h][r0 + 1]); }
+          for (int j = 0; j < 5; ++j) { m[j][0] = acc_elem(acc[5 * i + j][h][r0]); m[j][1] = acc_elem(acc[5 * i + j][h][r0 + 1]); }
           const f32x2 s12 = m[1] + m[2], d12 = m[1] - m[2];
           S[i][0] = (m[0] + s12) + m[3];
-          S[i][1] = h4_fma(-kd2, m[3], d12);
-          S[i][2] = h4_fma(kd4, m[3], s12);
-          S[i][3] = h4_fma(-kd8, m[3], d12) + m[4];
+          S[i][1] = pkfma(-kd2, m[3], d12);
+          S[i][2] = pkfma(kd4, m[3], s12);
+          S[i][3] = pkfma(-kd8, m[3], d12) + m[4];
         }
 #pragma unroll
         for (int x = 0; x < 4; ++x) {
           const f32x2 s12 = S[1][x] + S[2][x], d12 = S[1][x] - S[2][x];
           f32x2 y[4];
           y[0] = (S[0][x] + s12) + S[3][x];
-          y[1] = h4_fma(-kd2, S[3][x], d12);
-          y[2] = h4_fma(kd4, S[3][x], s12);
-          y[3] = h4_fma(-kd8, S[3][x], d12) + S[4][x];
+          y[1] = pkfma(-kd2, S[3][x], d12);
+          y[2] = pkfma(kd4, S[3][x], s12);
+          y[3] = pkfma(-kd8, S[3][x], d12) + S[4][x];
 #pragma unroll
           for (int yy = 0; yy < 4; ++yy) {
             ow[g_ * H4_OG + (yy * 4 + x) * 16 + co16] = y[yy][0];
@@ -581,21 +564,21 @@ __device__ __forceinline__ void h4_run(const Wino4S2Args& a, float* smem) {
       for (int i = 0; i < 5; ++i) {
         f32x2 m[5];
 #pragma unroll
-        for (int j = 0; j < 5; ++j) { m[j][0] = h4_acc_elem(acc[5 * i + j][h][r0]); m[j][1] = h4_acc_elem(acc[5 * i + j][h][r0 + 1]); }
+        for (int j = 0; j < 5; ++j) { m[j][0] = acc_elem(acc[5 * i + j][h][r0]); m[j][1] = acc_elem(acc[5 * i + j][h][r0 + 1]); }
         const f32x2 s12 = m[1] + m[2], d12 = m[1] - m[2];
         S[i][0] = (m[0] + s12) + m[3];
-        S[i][1] = h4_fma(-kd2, m[3], d12);
-        S[i][2] = h4_fma(kd4, m[3], s12);
-        S[i][3] = h4_fma(-kd8, m[3], d12) + m[4];
+        S[i][1] = pkfma(-kd2, m[3], d12);
+        S[i][2] = pkfma(kd4, m[3], s12);
+        S[i][3] = pkfma(-kd8, m[3], d12) + m[4];
       }
 #pragma unroll
       for (int x = 0; x < 4; ++x) {
         const f32x2 s12 = (S[1][x] + S[2][x]) + bv2, d12 = (S[1][x] - S[2][x]) + bv2;
         f32x2 y[4];
         y[0] = (S[0][x] + s12) + S[3][x];
-        y[1] = h4_fma(-kd2, S[3][x], d12);
-        y[2] = h4_fma(kd4, S[3][x], s12);
-        y[3] = h4_fma(-kd8, S[3][x], d12) + S[4][x];
+        y[1] = pkfma(-kd2, S[3][x], d12);
+        y[2] = pkfma(kd4, S[3][x], s12);
+        y[3] = pkfma(-kd8, S[3][x], d12) + S[4][x];
 #pragma unroll
         for (int yy = 0; yy < 4; ++yy) {
           f32x2 v = y[yy];
@@ -603,7 +586,7 @@ __device__ __forceinline__ void h4_run(const Wino4S2Args& a, float* smem) {
           ow[g_ * H4_OG + (yy * 4 + x) * 16 + co16] = v[0];
           ow[H4_OSTEP + g_ * H4_OG + (yy * 4 + x) * 16 + co16] = v[1];
           if constexpr (EPI == 1) {
-            if (full) { ssum2 = ssum2 + v; ssq2 = h4_fma(v, v, ssq2); }
+            if (full) { ssum2 = ssum2 + v; ssq2 = pkfma(v, v, ssq2); }
             else {                             // (scalar sums: conditional updates of vector elements sent hipcc's InstCombine into a loop)
               const int T0 = 16 * h + 4 * g_ + r0, T1 = T0 + 1;
               const float v0 = v[0], v1 = v[1];
@@ -649,9 +632,9 @@ __device__ __forceinline__ void h4_run(const Wino4S2Args& a, float* smem) {
   if constexpr (MODE == 2) { if (bn_nb >= 0) flush_bn(bn_nb); }
   // the prefetch behind the block's last chunk is still in flight: its registers must not be reused before it has landed
 #pragma unroll
-  for (int q = 0; q < H4_NQ; ++q) h4_vmwait<0>(graw[q]);
+  for (int q = 0; q < H4_NQ; ++q) vmwait<0>(graw[q]);
 #pragma unroll
-  for (int q = 0; q < H4_NP; ++q) h4_vmwait<0>(bq[q]);
+  for (int q = 0; q < H4_NP; ++q) vmwait<0>(bq[q]);
 }
 
 template <int EPI, bool AFFINE, int MODE = 0>
@@ -765,26 +748,18 @@ extern "C" int cy_conv4x4s2_winograd4(const float* X, const float* U, float* Y, 
   const long long tiles = (long long)B * a.tbh * a.tbw * (a.Np / 64);
   CY_REQUIRE(tiles < (1ll << 31), "cy_conv4x4s2_winograd4: too many tiles");
   a.ntiles = (int)tiles;
-  int dev = 0, ncu = 0;
-  hipError_t he = hipGetDevice(&dev);
-  if (he == hipSuccess) he = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  if (he != hipSuccess || ncu <= 0) return cy_set_error((int)he, "cy_conv4x4s2_winograd4: cannot query the CU count: %s", hipGetErrorString(he));
-  const long long blocks = tiles < ncu ? tiles : ncu;
+  long long blocks = 0;
+  if (int rc = cyi_persistent_blocks("cy_conv4x4s2_winograd4", tiles, &blocks)) return rc;
   const size_t lds = (size_t)(2 * H4_V_BUF + 2 * H4_RAW_BUF + 8 * H4_OSTEP + (in_scale ? 2 * Cin : 0)) * 4;
   hipStream_t s = (hipStream_t)stream;
-#define H4_LAUNCH(EPI, AFF)                                                   \
-  {                                                                           \
-    int rc = cy_allow_lds(wino4s2_conv_kernel<EPI, AFF>, lds);                \
-    if (rc) return rc;                                                        \
-    wino4s2_conv_kernel<EPI, AFF><<<(unsigned)blocks, 256, lds, s>>>(a);      \
+  const char* who = "cy_conv4x4s2_winograd4";
+  if (in_scale != nullptr) {
+    if (stats != nullptr) return cyi_launch_lds(who, wino4s2_conv_kernel<1, true>, (unsigned)blocks, 256, lds, s, a);
+    return cyi_launch_lds(who, wino4s2_conv_kernel<0, true>, (unsigned)blocks, 256, lds, s, a);
   }
-  if (in_scale != nullptr) { if (stats != nullptr) H4_LAUNCH(1, true) else H4_LAUNCH(0, true) }
-  else if (stats != nullptr) H4_LAUNCH(1, false)
-  else if (out_slope != 1.f) H4_LAUNCH(2, false)
-  else H4_LAUNCH(0, false)
-#undef H4_LAUNCH
-  CY_LAUNCH_CHECK("cy_conv4x4s2_winograd4");
-  return 0;
+  if (stats != nullptr) return cyi_launch_lds(who, wino4s2_conv_kernel<1, false>, (unsigned)blocks, 256, lds, s, a);
+  if (out_slope != 1.f) return cyi_launch_lds(who, wino4s2_conv_kernel<2, false>, (unsigned)blocks, 256, lds, s, a);
+  return cyi_launch_lds(who, wino4s2_conv_kernel<0, false>, (unsigned)blocks, 256, lds, s, a);
 }
 
 extern "C" int cy_wino4s2_dgrad_ok(int B, int H, int W, int Cin, int Cout) {     // H, W, Cin, Cout of the LAYER (dX is [B][H][W][Cin])
@@ -823,20 +798,13 @@ extern "C" int cy_conv4x4s2_winograd4_dgrad(const float* dZ, const float* U, flo
   a.ntiles = (int)tiles;
   const long long sp_tiles = (long long)B * a.tbh * a.tbw;
   a.sgroup = sp_tiles % 8 == 0 ? 8 : sp_tiles % 4 == 0 ? 4 : sp_tiles % 2 == 0 ? 2 : 1;
-  int dev = 0, ncu = 0;
-  hipError_t he = hipGetDevice(&dev);
-  if (he == hipSuccess) he = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  if (he != hipSuccess || ncu <= 0) return cy_set_error((int)he, "cy_conv4x4s2_winograd4_dgrad: cannot query the CU count: %s", hipGetErrorString(he));
-  long long blocks = tiles < ncu ? tiles : ncu;
+  long long blocks = 0;
+  if (int rc = cyi_persistent_blocks("cy_conv4x4s2_winograd4_dgrad", tiles, &blocks)) return rc;
   // a grid that is a multiple of the number of channel blocks keeps every block on ONE channel block (its BatchNorm sums leave once)
   const int nblk = a.Np / 64;
   if (blocks > nblk) blocks -= blocks % nblk;
   const size_t lds = (size_t)(2 * H4_V_BUF + 2 * H4_RAW_BUF + 8 * H4_OSTEP) * 4;
-  int rc = cy_allow_lds(wino4s2_conv_kernel<0, false, 1>, lds);
-  if (!rc) rc = cy_allow_lds(wino4s2_conv_kernel<0, false, 2>, lds);
-  if (rc) return rc;
-  if (bn_red != nullptr) wino4s2_conv_kernel<0, false, 2><<<(unsigned)blocks, 256, lds, (hipStream_t)stream>>>(a);
-  else wino4s2_conv_kernel<0, false, 1><<<(unsigned)blocks, 256, lds, (hipStream_t)stream>>>(a);
-  CY_LAUNCH_CHECK("cy_conv4x4s2_winograd4_dgrad");
-  return 0;
+  const char* who = "cy_conv4x4s2_winograd4_dgrad";
+  if (bn_red == nullptr) return cyi_launch_lds(who, wino4s2_conv_kernel<0, false, 1>, (unsigned)blocks, 256, lds, (hipStream_t)stream, a);
+  return cyi_launch_lds(who, wino4s2_conv_kernel<0, false, 2>, (unsigned)blocks, 256, lds, (hipStream_t)stream, a);
 }

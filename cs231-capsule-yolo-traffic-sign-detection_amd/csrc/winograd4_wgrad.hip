@@ -20,14 +20,16 @@
 //   * A operand image V[pos pair][tile][ci pair][pos][ci parity] (one ds_read_b128 per position pair), B operand image
 //     Z[pos][tile][co] with the co bit 4 flipped for odd tiles (conflict-free ds_read_b32).
 // Shapes: H % 4 == 0, W % 16 == 0, Cin % 32 == 0, Cout % 64 == 0, H W C 4 < 2^28 (the caller falls back to winograd.hip).
-#include "common.h"
+#include "prims.h"
 
 namespace {
+using namespace cyk;
 
 // developer knob for timing experiments (results are wrong when set): 1 no dz stores, 2 no loads of z (BNF), 4 no BatchNorm arithmetic
 #ifndef CY_G4_DBG
 #define CY_G4_DBG 0
 #endif
+CY_WRONG_RESULT_KNOB(CY_G4_DBG);
 
 constexpr int G4_XPITCH = 36;                   // floats per raw input pixel: 32 channels + 4 pad; pixels stored COLUMN-major (col * 6 + row):
                                                 // a column's rows are 144 B apart (ds_read2_b64 pairs), a tile's 4 columns 128 B mod 256
@@ -36,7 +38,6 @@ constexpr int G4_RAWZ = 64 * 64;                // raw dz patch [4 x 16 pixels][
 constexpr int G4_V_BUF = 18 * 4 * 16 * 4;       // [pos pair][tile][ci pair][pos in pair][ci parity]
 constexpr int G4_Z_BUF = 36 * 4 * 64;           // [pos][tile][co (bit 4 ^ tile parity)]
 
-typedef int i32x4g_ __attribute__((ext_vector_type(4)));
 #ifdef CY_G4_PROF
 // developer instrumentation (tools/g4prof.py): s_memtime stamps of one chunk per block and role
 __device__ unsigned long long g4_prof_buf[256 * 2 * 16];
@@ -56,32 +57,6 @@ struct Wino4WgradArgs {
   const float *scale, *mean, *invstd;
   const double* red; double inv_count;
 };
-
-__device__ __forceinline__ void g4_mfma_a(f32x4& c, float a, float b) {
-  asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void g4_mfma_v(f32x4& c, float a, float b) {
-  asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ f32x2 g4_fma(f32x2 x, f32x2 y, f32x2 z) { return __builtin_elementwise_fma(x, y, z); }
-__device__ __forceinline__ f32x2 g4_fnma(f32x2 x, f32x2 y, f32x2 z) { return __builtin_elementwise_fma(-x, y, z); }
-// loads hipcc does not count (winograd4.hip: a tracked load pending at the loop header draws vmcnt(0)); waited for by hand
-__device__ __forceinline__ void g4_load(f32x4& dst, i32x4g_ desc, unsigned voff, unsigned soff) {
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(dst) : "v"(voff), "s"(desc), "s"(soff));
-}
-__device__ __forceinline__ void g4_store(const f32x4& src, i32x4g_ desc, unsigned voff, unsigned soff) {
-  asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" : : "v"(src), "v"(voff), "s"(desc), "s"(soff) : "memory");
-}
-template <int N> __device__ __forceinline__ void g4_vmwait(f32x4& x) { asm volatile("s_waitcnt vmcnt(%1)" : "+v"(x) : "n"(N)); }
-__device__ __forceinline__ float g4_acc_elem(float a_elem) {
-  float x;
-  asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x) : "a"(a_elem));
-  return x;
-}
-__device__ __forceinline__ i32x4g_ g4_desc(const void* p, int bytes) {
-  const unsigned long long b = (unsigned long long)(uintptr_t)p;
-  return i32x4g_{(int)(unsigned)b, (int)(unsigned)((b >> 32) & 0xffffu), bytes, 0x00020000};
-}
 
 // ---- compile-time schedule of one chunk: 72 slots; slot s issues the MFMA of position s >> 1, input-channel half s & 1.
 // ROLE 0 (waves 0, 1): 6 T_rd + 12 T_col + 12 T_row pieces of the input transform; ROLE 1 (waves 2, 3): 4 Z_rd + 8 Z_col +
@@ -187,7 +162,7 @@ __device__ __forceinline__ void g4_run(const Wino4WgradArgs& a, float* smem) {
     lgb = gb; lty = gr / a.gw; lcx = gr - lty * a.gw;
   }
   int lrem = nchunk - 1;                        // chunks the cursor may still advance (it stops at the block's last chunk)
-  i32x4g_ xdesc, zdesc, zzdesc, odesc;
+  i32x4 xdesc, zdesc, zzdesc, odesc;
   unsigned xsoff = 0, zsoff = 0, xbt = 0;
   bool phantom = false;                         // the cursor stands behind the block's last real chunk
   // The chunk offsets RUN (one add per chunk) and the four descriptors are rebuilt only when the image changes: recomputed from (image,
@@ -195,11 +170,11 @@ __device__ __forceinline__ void g4_run(const Wino4WgradArgs& a, float* smem) {
   // every instruction of the wave, scalar or not, takes an issue slot.  (No new uniform state: the kernel stands at 100 SGPRs, and
   // running image pointers pushed it into v_writelane spills.)
   auto set_desc = [&]() {
-    xdesc = g4_desc((const char*)(a.X + (long long)lgb * a.H * a.W * a.Cin) - xshift, phantom ? 0 : ximg_bytes + xshift);
-    zdesc = g4_desc(a.dZ + (long long)lgb * a.H * a.W * a.Cout, zimg_bytes);
+    xdesc = bufdesc((const char*)(a.X + (long long)lgb * a.H * a.W * a.Cin) - xshift, phantom ? 0 : ximg_bytes + xshift);
+    zdesc = bufdesc(a.dZ + (long long)lgb * a.H * a.W * a.Cout, zimg_bytes);
     if constexpr (BNF) {
-      zzdesc = g4_desc(a.Z + (long long)lgb * a.H * a.W * a.Cout, zimg_bytes);
-      odesc = g4_desc(a.dZout + (long long)lgb * a.H * a.W * a.Cout, phantom ? 0 : zimg_bytes);
+      zzdesc = bufdesc(a.Z + (long long)lgb * a.H * a.W * a.Cout, zimg_bytes);
+      odesc = bufdesc(a.dZout + (long long)lgb * a.H * a.W * a.Cout, phantom ? 0 : zimg_bytes);
     }
   };
   auto set_edges = [&]() {
@@ -234,11 +209,11 @@ __device__ __forceinline__ void g4_run(const Wino4WgradArgs& a, float* smem) {
   // flight (a load has two chunks = 2 us to return: with one set -- 1 us -- the S_raw waits were the loop's largest stall)
   f32x4 gx[2][4], gz[2][4], zz[2][4];
   unsigned osoff[2] = {0u, 0u};                 // BNF: scalar offset / descriptor of the chunk held in set P (its dz goes there)
-  i32x4g_ odesc_held[2];
-  auto Gx = [&](int P, int q) { g4_load(gx[P][q], xdesc, (xhfl[q] & xbt) | xvoff[q], xsoff); };
+  i32x4 odesc_held[2];
+  auto Gx = [&](int P, int q) { bufload(gx[P][q], xdesc, (xhfl[q] & xbt) | xvoff[q], xsoff); };
   auto Gz = [&](int P, int q) {
-    g4_load(gz[P][q], zdesc, zvoff[q], zsoff);
-    if constexpr (BNF) { if (CY_G4_DBG & 2) zz[P][q] = gz[P][q]; else g4_load(zz[P][q], zzdesc, zvoff[q], zsoff); }
+    bufload(gz[P][q], zdesc, zvoff[q], zsoff);
+    if constexpr (BNF) { if (CY_G4_DBG & 2) zz[P][q] = gz[P][q]; else bufload(zz[P][q], zzdesc, zvoff[q], zsoff); }
   };
   // BNF: per-channel constants of this thread's 4 dz channels: dz = d * sc + (z - mu) * kb + kc
   // dz = d * sc + z * kb + kc with kc = -sc * mean(d) - mean * kb folded (two packed FMAs per channel pair)
@@ -262,12 +237,12 @@ __device__ __forceinline__ void g4_run(const Wino4WgradArgs& a, float* smem) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const f32x2 zv = {zz[P][q][2 * h], zz[P][q][2 * h + 1]}, dv = {gz[P][q][2 * h], gz[P][q][2 * h + 1]};
-          const f32x2 r = g4_fma(dv, k2sc[h], g4_fma(zv, k2b[h], k2c[h]));
+          const f32x2 r = pkfma(dv, k2sc[h], pkfma(zv, k2b[h], k2c[h]));
           o[2 * h] = r[0]; o[2 * h + 1] = r[1];
         }
       }
       *(f32x4*)(Rz + zroff[q]) = o;
-      if (!(CY_G4_DBG & 1) && (BNF != 4 || q == 0)) g4_store(o, odesc_held[P], zsto[q], osoff[P]);
+      if (!(CY_G4_DBG & 1) && (BNF != 4 || q == 0)) bufstore(o, odesc_held[P], zsto[q], osoff[P]);
     } else {
       *(f32x4*)(Rz + zroff[q]) = gz[P][q];
     }
@@ -298,34 +273,34 @@ __device__ __forceinline__ void g4_run(const Wino4WgradArgs& a, float* smem) {
   auto Tcol = [&](int c, int part) {
     const f32x2* d = dc[c & 1];
     if (part == 0) {
-      cx_ = g4_fma(kal, d[4], d[6]);
-      cy_ = g4_fma(kal, d[3], d[5]);
-      ci_ = g4_fma(km5, d[1], d[2]);
+      cx_ = pkfma(kal, d[4], d[6]);
+      cy_ = pkfma(kal, d[3], d[5]);
+      ci_ = pkfma(km5, d[1], d[2]);
     } else {
-      tt[1][c] = g4_fma(kga, cy_, cx_);
-      tt[2][c] = g4_fnma(kga, cy_, cx_);
-      tt[0][c] = g4_fma(k4, d[0], ci_);
+      tt[1][c] = pkfma(kga, cy_, cx_);
+      tt[2][c] = pkfnma(kga, cy_, cx_);
+      tt[0][c] = pkfma(k4, d[0], ci_);
     }
   };
   auto Trow = [&](float* vb, int r, int part) {
     const f32x2* x = tt[r];
     float* v = vb + (r == 0 ? vd0 : r == 1 ? vd1 : vd2);   // + (j >> 1) * 256 + (j & 1) * 2
     if (part == 0) {
-      rt_[0] = g4_fma(km5, x[2], x[4]);
-      rt_[1] = g4_fma(km4, x[2], x[4]);
-      rt_[2] = g4_fma(km4, x[1], x[3]);
+      rt_[0] = pkfma(km5, x[2], x[4]);
+      rt_[1] = pkfma(km4, x[2], x[4]);
+      rt_[2] = pkfma(km4, x[1], x[3]);
     } else if (part == 1) {
       rt_[3] = x[4] - x[2];
       rt_[4] = x[3] - x[1];
-      rt_[5] = g4_fma(km5, x[3], x[5]);
+      rt_[5] = pkfma(km5, x[3], x[5]);
     } else if (part == 2) {
-      *(f32x2*)(v + 0) = g4_fma(k4, x[0], rt_[0]);
+      *(f32x2*)(v + 0) = pkfma(k4, x[0], rt_[0]);
       *(f32x2*)(v + 2) = rt_[1] + rt_[2];
       *(f32x2*)(v + 256) = rt_[1] - rt_[2];
     } else {
-      *(f32x2*)(v + 256 + 2) = g4_fma(k2, rt_[4], rt_[3]);
-      *(f32x2*)(v + 512) = g4_fnma(k2, rt_[4], rt_[3]);
-      *(f32x2*)(v + 512 + 2) = g4_fma(k4, x[1], rt_[5]);
+      *(f32x2*)(v + 256 + 2) = pkfma(k2, rt_[4], rt_[3]);
+      *(f32x2*)(v + 512) = pkfnma(k2, rt_[4], rt_[3]);
+      *(f32x2*)(v + 512 + 2) = pkfma(k4, x[1], rt_[5]);
     }
   };
   // ---- ROLE 1: dz transform, thread (co pair cp, tile kg): U = G z G^T (6x6 from 4x4) for channels 2 cp, 2 cp + 1
@@ -341,13 +316,13 @@ __device__ __forceinline__ void g4_run(const Wino4WgradArgs& a, float* smem) {
     if (part == 0) {
       za_[0] = zin[0][c] + zin[2][c];
       za_[1] = zin[1][c] + zin[3][c];
-      za_[2] = g4_fma(k4, zin[2][c], zin[0][c]);
-      za_[3] = g4_fma(k4, zin[3][c], zin[1][c]);
+      za_[2] = pkfma(k4, zin[2][c], zin[0][c]);
+      za_[3] = pkfma(k4, zin[3][c], zin[1][c]);
     } else {
       zt[1][c] = za_[0] + za_[1];
       zt[2][c] = za_[0] - za_[1];
-      zt[3][c] = g4_fma(k2, za_[3], za_[2]);
-      zt[4][c] = g4_fnma(k2, za_[3], za_[2]);
+      zt[3][c] = pkfma(k2, za_[3], za_[2]);
+      zt[4][c] = pkfnma(k2, za_[3], za_[2]);
       zt[0][c] = zin[0][c];
       zt[5][c] = zin[3][c];
     }
@@ -358,14 +333,14 @@ __device__ __forceinline__ void g4_run(const Wino4WgradArgs& a, float* smem) {
     if (part == 0) {
       za_[0] = x[0] + x[2];
       za_[1] = x[1] + x[3];
-      za_[2] = g4_fma(k4, x[2], x[0]);
-      za_[3] = g4_fma(k4, x[3], x[1]);
+      za_[2] = pkfma(k4, x[2], x[0]);
+      za_[3] = pkfma(k4, x[3], x[1]);
     } else {
       *(f32x2*)(u + 0 * 256) = x[0];
       *(f32x2*)(u + 1 * 256) = za_[0] + za_[1];
       *(f32x2*)(u + 2 * 256) = za_[0] - za_[1];
-      *(f32x2*)(u + 3 * 256) = g4_fma(k2, za_[3], za_[2]);
-      *(f32x2*)(u + 4 * 256) = g4_fnma(k2, za_[3], za_[2]);
+      *(f32x2*)(u + 3 * 256) = pkfma(k2, za_[3], za_[2]);
+      *(f32x2*)(u + 4 * 256) = pkfnma(k2, za_[3], za_[2]);
       *(f32x2*)(u + 5 * 256) = x[3];
     }
   };
@@ -402,7 +377,7 @@ __device__ __forceinline__ void g4_run(const Wino4WgradArgs& a, float* smem) {
   };
   auto Wall = [&](int P) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) { g4_vmwait<0>(gx[P][q]); g4_vmwait<0>(gz[P][q]); if constexpr (BNF) g4_vmwait<0>(zz[P][q]); }
+    for (int q = 0; q < 4; ++q) { vmwait<0>(gx[P][q]); vmwait<0>(gz[P][q]); if constexpr (BNF) vmwait<0>(zz[P][q]); }
   };
   auto Sall = [&](int P) {
 #pragma unroll
@@ -468,8 +443,8 @@ __device__ __forceinline__ void g4_run(const Wino4WgradArgs& a, float* smem) {
       constexpr int s_ = (SIDX), p_ = s_ >> 1, mt_ = s_ & 1, q_ = p_ >> 1;                            \
       G4_STAMP(s_)                                                                                    \
       if (s_ == G4_MID || s_ == G4_END) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
-      if (p_ < 32) g4_mfma_a(accA[p_ < 32 ? p_ : 0][mt_], fa[q_ % 3][2 * (p_ & 1) + mt_], fb[q_ % 3][p_ & 1]); \
-      else g4_mfma_v(accV[p_ >= 32 ? p_ - 32 : 0][mt_], fa[q_ % 3][2 * (p_ & 1) + mt_], fb[q_ % 3][p_ & 1]);   \
+      if (p_ < 32) mfma16_a(accA[p_ < 32 ? p_ : 0][mt_], fa[q_ % 3][2 * (p_ & 1) + mt_], fb[q_ % 3][p_ & 1]); \
+      else mfma16_v(accV[p_ >= 32 ? p_ - 32 : 0][mt_], fa[q_ % 3][2 * (p_ & 1) + mt_], fb[q_ % 3][p_ & 1]); \
       if (s_ < G4_END) {                                                                              \
         if ((s_ & 3) == 0 && q_ + 2 < 18) {                                                           \
           fa[(q_ + 2) % 3] = *(const f32x4*)(va_ + (q_ + 2) * 256);                                   \
@@ -487,8 +462,8 @@ __device__ __forceinline__ void g4_run(const Wino4WgradArgs& a, float* smem) {
       } else if (kind == 3) {                                                                         \
         if constexpr (ROLE == 0) Trow(vw_, (k_ >> 2) % 3, k_ & 3); else Zrow(zw_, (k_ >> 1) % 6, k_ & 1); \
       } else if (kind == 4) {                   /* S_raw: x items 0..3, then dz items 0..3 */        \
-        if (k_ < 4) { g4_vmwait<VMW>(gx[P_][k_ & 3]); Sx(P_, k_ & 3); }                               \
-        else { g4_vmwait<VMW>(gz[P_][k_ & 3]); if constexpr (BNF) g4_vmwait<VMW>(zz[P_][k_ & 3]); Sz(P_, k_ & 3); } \
+        if (k_ < 4) { vmwait<VMW>(gx[P_][k_ & 3]); Sx(P_, k_ & 3); }                                 \
+        else { vmwait<VMW>(gz[P_][k_ & 3]); if constexpr (BNF) vmwait<VMW>(zz[P_][k_ & 3]); Sz(P_, k_ & 3); } \
       } else if (kind == 5) {                                                                         \
         if (k_ < 4) Gx(P_, k_ & 3); else Gz(P_, k_ & 3);                                              \
       } else if (kind == 6) {                                                                         \
@@ -517,7 +492,7 @@ __device__ __forceinline__ void g4_run(const Wino4WgradArgs& a, float* smem) {
 #pragma unroll
   for (int q = 0; q < 4; ++q)
 #pragma unroll
-    for (int P = 0; P < 2; ++P) { g4_vmwait<0>(gx[P][q]); g4_vmwait<0>(gz[P][q]); if constexpr (BNF) g4_vmwait<0>(zz[P][q]); }
+    for (int P = 0; P < 2; ++P) { vmwait<0>(gx[P][q]); vmwait<0>(gz[P][q]); if constexpr (BNF) vmwait<0>(zz[P][q]); }
   // ---- the block's partial sums: slab[range][pos][ci][co]; lane l, register e of accumulator (pos, mt): ci pair 4 (l >> 4) + e
   float* sl = a.slab + ((long long)jr * 36 * a.Cin + cib * 32) * a.Cout + cob * 64 + 16 * wave + ml;
 #pragma unroll
@@ -526,7 +501,7 @@ __device__ __forceinline__ void g4_run(const Wino4WgradArgs& a, float* smem) {
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float v = p < 32 ? g4_acc_elem(accA[p < 32 ? p : 0][mt][e]) : accV[p >= 32 ? p - 32 : 0][mt][e];
+        const float v = p < 32 ? acc_elem(accA[p < 32 ? p : 0][mt][e]) : accV[p >= 32 ? p - 32 : 0][mt][e];
         sl[((long long)p * a.Cin + 2 * (4 * kgl + e) + mt) * a.Cout] = v;
       }
 }
@@ -577,8 +552,8 @@ __global__ void wino4_wgrad_finish_kernel(const float* __restrict__ slab, float*
 }
 
 int g4_nrange(int B, int H, int W, int Cin, int Cout) {
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  int ncu = cyi_cu_count();
+  if (ncu == 0) ncu = 256;
   const long long tiles = ((long long)B * (H / 4) * (W / 16) + 1) / 2;   // chunk pairs
   const int per = (Cin / 32) * (Cout / 64);
   long long n = ncu / per;
@@ -606,16 +581,12 @@ static int g4_launch(Wino4WgradArgs& a, float* dW, bool bnf, hipStream_t s) {
   a.nrange = g4_nrange(a.B, a.H, a.W, a.Cin, a.Cout);
   const int blocks = a.nrange * (a.Cin / 32) * (a.Cout / 64);
   const size_t lds = (size_t)(2 * G4_V_BUF + 2 * G4_Z_BUF + G4_RAWX + G4_RAWZ) * 4;
-  int rc = cy_allow_lds(wino4_wgrad_kernel<0>, lds);
+  const char* who = "cy_conv3x3_winograd4_wgrad";
+  int rc;
+  if (!bnf) rc = cyi_launch_lds(who, wino4_wgrad_kernel<0>, (unsigned)blocks, 256, lds, s, a);
+  else if (a.Cin != 128) rc = cyi_launch_lds(who, wino4_wgrad_kernel<1>, (unsigned)blocks, 256, lds, s, a);
+  else rc = cyi_launch_lds(who, wino4_wgrad_kernel<4>, (unsigned)blocks, 256, lds, s, a);   // four input-channel blocks: one dz row each
   if (rc) return rc;
-  rc = cy_allow_lds(wino4_wgrad_kernel<1>, lds);
-  if (rc) return rc;
-  rc = cy_allow_lds(wino4_wgrad_kernel<4>, lds);
-  if (rc) return rc;
-  if (bnf && a.Cin == 128) wino4_wgrad_kernel<4><<<(unsigned)blocks, 256, lds, s>>>(a);   // four input-channel blocks: one dz row each
-  else if (bnf) wino4_wgrad_kernel<1><<<(unsigned)blocks, 256, lds, s>>>(a);
-  else wino4_wgrad_kernel<0><<<(unsigned)blocks, 256, lds, s>>>(a);
-  CY_LAUNCH_CHECK("cy_conv3x3_winograd4_wgrad");
   const int n = a.Cin * a.Cout;
   if (a.nrange > 1) {
     wino4_wgrad_reduce_kernel<<<(unsigned)cy_ceil_div(36ll * n, 256), 256, 0, s>>>(a.slab, a.nrange, 36ll * n);

@@ -25,7 +25,8 @@
 #define W2_SKIP 0
 #endif
 #define W2_SKIPPED(k) ((((W2_SKIP) & 1) && ((k) == 4 || (k) == 5)) || (((W2_SKIP) & 2) && ((k) == 1 || (k) == 7)) || (((W2_SKIP) & 4) && ((k) == 2 || (k) == 3)))
-#include "common.h"
+#include "prims.h"
+CY_WRONG_RESULT_KNOB(W2_SKIP);
 
 // The outputs of these layers (and the z tensor the fused BatchNorm sums read) are streamed once and are far larger than the
 // 4 MB L2 of an XCD: marked nontemporal they do not push the transformed weights, which every tile re-reads, out of it
@@ -43,6 +44,7 @@
 
 
 namespace {
+using namespace cyk;
 
 constexpr int TR2 = 8, TC2 = 16;            // tile rows / columns per block
 constexpr int NT2 = TR2 * TC2;              // 128 tiles
@@ -68,20 +70,6 @@ struct Wino2Args {
   float out_slope;                          // ACT (forward, eval mode): Y = lrelu(conv + bias) with this slope, BatchNorm folded into U / bias
 };
 
-// 18 accumulator tiles = 288 registers, the AGPR file has 256: left to itself the compiler shuttles accumulators
-// between the two files in every chunk (288 v_accvgpr_write per chunk measured).  The MFMAs are therefore written
-// with an explicit register class: positions 0..7 accumulate in AGPRs, position 8 (32 registers) in arch VGPRs.
-__device__ __forceinline__ void mfma_a(f32x16& c, float a, float b) {
-  asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma_v(f32x16& c, float a, float b) {
-  asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ f32x2 pk_sub(f32x2 x, f32x2 y) {
-  f32x2 r;
-  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(x), "v"(y));
-  return r;
-}
 // lrelu(v * sc + sh) on 4 channels with packed math (the producer's BatchNorm + LeakyReLU applied on the way into LDS,
 // so that the activation tensor never exists in HBM); slope in (0, 1]: lrelu(y) = max(y, slope * y)
 __device__ __forceinline__ f32x4 affine_lrelu4(f32x4 v, f32x4 sc, f32x4 sh, float slope) {
@@ -98,11 +86,6 @@ __device__ __forceinline__ f32x4 affine_lrelu4(f32x4 v, f32x4 sc, f32x4 sh, floa
   asm("v_max_f32 %0, %1, %2" : "=v"(r[2]) : "v"(hi[0]), "v"(hi2[0]));
   asm("v_max_f32 %0, %1, %2" : "=v"(r[3]) : "v"(hi[1]), "v"(hi2[1]));
   return r;
-}
-__device__ __forceinline__ float acc_elem(float a_elem) {   // one accumulator element, read where the statement stands
-  float x;
-  asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x) : "a"(a_elem));
-  return x;
 }
 
 // ---- compile-time schedule of one chunk: 72 slots; slot s issues the MFMA of position s / 8, row tile s & 1,
@@ -303,11 +286,11 @@ __global__ __launch_bounds__(256, 1) void wino2_conv_kernel(Wino2Args a) {
     f32x2 t0[3];
 #pragma unroll
     for (int cc = 0; cc < 3; ++cc)
-      t0[cc] = R == 0 ? pk_sub(xv[it][0][cc], xv[it][1][cc]) : R == 1 ? xv[it][1][cc] : pk_sub(xv[it][2][cc], xv[it][1][cc]);
+      t0[cc] = R == 0 ? asm_pk_sub(xv[it][0][cc], xv[it][1][cc]) : R == 1 ? xv[it][1][cc] : asm_pk_sub(xv[it][2][cc], xv[it][1][cc]);
     float* v = vb + it * (4 * TC2 * 4);
-    *(f32x2*)(v + (R * 3 + 0) * 2 * SLABV) = pk_sub(t0[0], t0[1]);
+    *(f32x2*)(v + (R * 3 + 0) * 2 * SLABV) = asm_pk_sub(t0[0], t0[1]);
     *(f32x2*)(v + (R * 3 + 1) * 2 * SLABV) = t0[1];
-    *(f32x2*)(v + (R * 3 + 2) * 2 * SLABV) = pk_sub(t0[2], t0[1]);
+    *(f32x2*)(v + (R * 3 + 2) * 2 * SLABV) = asm_pk_sub(t0[2], t0[1]);
   };
   auto Tall = [&](int buf_raw, int buf_v) {
     const float* rb = Rs + buf_raw * RAW2_BUF + tbase;
@@ -439,8 +422,8 @@ __global__ __launch_bounds__(256, 1) void wino2_conv_kernel(Wino2Args a) {
       constexpr int xi = sidx >> 3, w_ = sidx & 7, mi = w_ & 1, e = w_ >> 1;                        \
       W2_STAMP(sidx)                                                                                \
       if (w_ == 0) __builtin_amdgcn_s_waitcnt(0xC07F | (s2_younger(xi) << 8));                      \
-      if (xi < 8) mfma_a(acc[xi][mi], fa_[xi & 1][mi][e], fb_[xi & 1][e]);                          \
-      else mfma_v(acc[xi][mi], fa_[xi & 1][mi][e], fb_[xi & 1][e]);                                 \
+      if (xi < 8) mfma32_a(acc[xi][mi], fa_[xi & 1][mi][e], fb_[xi & 1][e]);                        \
+      else mfma32_v(acc[xi][mi], fa_[xi & 1][mi][e], fb_[xi & 1][e]);                               \
       if (w_ < 3 && xi + 1 < 9) {                                                                   \
         constexpr int nx = (xi + 1 < 9) ? xi + 1 : 0;                                               \
         if (w_ == 0) fa_[nx & 1][0] = *(const f32x4*)(vb_ + nx * 2 * SLABV);                        \
@@ -746,18 +729,6 @@ struct Wino2WgradArgs {
   int nsplit;                               // tile groups of one image are cut into nsplit ranges (more blocks for small layers)
 };
 
-template <int O0, int O1>
-__device__ __forceinline__ f32x2 lds_pair_st64(unsigned addr) {   // (dword[O0*64], dword[O1*64]) as one register pair
-  f32x2 r;
-  asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(r) : "v"(addr), "n"(O0), "n"(O1));
-  return r;
-}
-__device__ __forceinline__ f32x2 pk_add(f32x2 x, f32x2 y) {
-  f32x2 r;
-  asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
-  return r;
-}
-
 // side work of one chunk (72 slots, fragment fetches in slots 0..2 of every position):
 //   4 T   two paired reads of the raw patches of chunk c+1: dY first (2 pieces), then X' (9 pieces)
 //   5 Z   one row of G z G^T (3 pieces)      6 V  one row of B^T d B of one of the two items (6 pieces)
@@ -909,17 +880,17 @@ __global__ __launch_bounds__(256, 1) void wino2_wgrad_kernel(Wino2WgradArgs a) {
     f32x2 t0[3];
 #pragma unroll
     for (int cc = 0; cc < 3; ++cc)
-      t0[cc] = R == 0 ? pk_sub(xv[it][0][cc], xv[it][1][cc]) : R == 1 ? xv[it][1][cc] : pk_sub(xv[it][2][cc], xv[it][1][cc]);
+      t0[cc] = R == 0 ? asm_pk_sub(xv[it][0][cc], xv[it][1][cc]) : R == 1 ? xv[it][1][cc] : asm_pk_sub(xv[it][2][cc], xv[it][1][cc]);
     float* v = vb + 2 * it;
-    *(f32x2*)(v + (R * 3 + 0) * 2 * SLABV) = pk_sub(t0[0], t0[1]);
+    *(f32x2*)(v + (R * 3 + 0) * 2 * SLABV) = asm_pk_sub(t0[0], t0[1]);
     *(f32x2*)(v + (R * 3 + 1) * 2 * SLABV) = t0[1];
-    *(f32x2*)(v + (R * 3 + 2) * 2 * SLABV) = pk_sub(t0[2], t0[1]);
+    *(f32x2*)(v + (R * 3 + 2) * 2 * SLABV) = asm_pk_sub(t0[2], t0[1]);
   };
   auto Zrow = [&](float* zb, int R) {       // row R of G z G^T
-    const f32x2 u0 = R == 0 ? zv[0][0] : R == 1 ? pk_add(zv[0][0], zv[1][0]) : zv[1][0];
-    const f32x2 u1 = R == 0 ? zv[0][1] : R == 1 ? pk_add(zv[0][1], zv[1][1]) : zv[1][1];
+    const f32x2 u0 = R == 0 ? zv[0][0] : R == 1 ? asm_pk_add(zv[0][0], zv[1][0]) : zv[1][0];
+    const f32x2 u1 = R == 0 ? zv[0][1] : R == 1 ? asm_pk_add(zv[0][1], zv[1][1]) : zv[1][1];
     *(f32x2*)(zb + (R * 3 + 0) * 2 * SLABU) = u0;
-    *(f32x2*)(zb + (R * 3 + 1) * 2 * SLABU) = pk_add(u0, u1);
+    *(f32x2*)(zb + (R * 3 + 1) * 2 * SLABU) = asm_pk_add(u0, u1);
     *(f32x2*)(zb + (R * 3 + 2) * 2 * SLABU) = u1;
   };
   auto Tall_plain = [&]() {                 // prologue only: plain loads (the compiler waits for them itself)
@@ -989,8 +960,8 @@ __global__ __launch_bounds__(256, 1) void wino2_wgrad_kernel(Wino2WgradArgs a) {
       constexpr int sidx = (SIDX);                                                                  \
       constexpr int xi = sidx >> 3, w_ = sidx & 7, mi = w_ & 1, e = w_ >> 1;                        \
       if (w_ == 0) __builtin_amdgcn_s_waitcnt(0xC07F | (g2_younger(xi) << 8));                      \
-      if (xi < 8) mfma_a(acc[xi][mi], fa_[xi & 1][mi][e], fb_[xi & 1][e]);                          \
-      else mfma_v(acc[xi][mi], fa_[xi & 1][mi][e], fb_[xi & 1][e]);                                 \
+      if (xi < 8) mfma32_a(acc[xi][mi], fa_[xi & 1][mi][e], fb_[xi & 1][e]);                        \
+      else mfma32_v(acc[xi][mi], fa_[xi & 1][mi][e], fb_[xi & 1][e]);                               \
       if (w_ < 3 && xi + 1 < 9) {                                                                   \
         constexpr int nx = (xi + 1 < 9) ? xi + 1 : 0;                                               \
         if (w_ == 0) fa_[nx & 1][0] = *(const f32x4*)(vb_ + nx * 2 * SLABV);                        \
@@ -1130,16 +1101,6 @@ extern "C" int cy_wino2_pack_weights(const float* W, float* U, int Cout, int Cin
   return 0;
 }
 
-// persistent grid: one block per CU (153 KB of LDS, 512 registers per lane)
-static int wino2_persistent_blocks(long long tiles, long long* blocks, const char* who) {
-  int dev = 0, ncu = 0;
-  hipError_t he = hipGetDevice(&dev);
-  if (he == hipSuccess) he = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  if (he != hipSuccess || ncu <= 0) return cy_set_error((int)he, "%s: cannot query the CU count: %s", who, hipGetErrorString(he));
-  *blocks = tiles < ncu ? tiles : ncu;
-  return 0;
-}
-
 extern "C" int cy_conv4x4s2_winograd(const float* X, const float* U, float* Y, const float* bias, double* stats,
                                      const float* in_scale, const float* in_shift, float in_slope, float out_slope, int B, int H,
                                      int W, int Cin, int Cout, void* stream) {
@@ -1164,7 +1125,7 @@ extern "C" int cy_conv4x4s2_winograd(const float* X, const float* U, float* Y, c
   CY_REQUIRE(tiles < (1ll << 31), "cy_conv4x4s2_winograd: too many tiles");
   a.ntiles = (int)tiles;
   long long blocks = 0;
-  int rcq = wino2_persistent_blocks(tiles, &blocks, "cy_conv4x4s2_winograd");
+  int rcq = cyi_persistent_blocks("cy_conv4x4s2_winograd", tiles, &blocks);   // persistent grid: one block per CU (153 KB of LDS, 512 registers per lane)
   if (rcq) return rcq;
   const size_t lds = (size_t)(2 * V2_BUF + 2 * U2_BUF + 2 * RAW2_BUF + (in_scale ? 2 * Cin : 0)) * 4;
   CY_REQUIRE(lds <= 160 * 1024, "cy_conv4x4s2_winograd: Cin=%d too large for the fused input affine", Cin);
@@ -1173,14 +1134,11 @@ extern "C" int cy_conv4x4s2_winograd(const float* X, const float* U, float* Y, c
   if (const char* e = getenv("CY_W2_PROF")) a.bn_red = (double*)strtoull(e, nullptr, 0);
   if (const char* e = getenv("CY_W2_STAMPS")) a.bn_scale = (const float*)strtoull(e, nullptr, 0);
 #endif
-  int rc = in_scale ? cy_allow_lds(wino2_conv_kernel<0, true>, lds)
-                    : out_slope != 1.f ? cy_allow_lds(wino2_conv_kernel<0, false, true>, lds) : cy_allow_lds(wino2_conv_kernel<0, false>, lds);
-  if (rc) return rc;
-  if (in_scale) wino2_conv_kernel<0, true><<<(unsigned)blocks, 256, lds, (hipStream_t)stream>>>(a);
-  else if (out_slope != 1.f) wino2_conv_kernel<0, false, true><<<(unsigned)blocks, 256, lds, (hipStream_t)stream>>>(a);
-  else wino2_conv_kernel<0, false><<<(unsigned)blocks, 256, lds, (hipStream_t)stream>>>(a);
-  CY_LAUNCH_CHECK("cy_conv4x4s2_winograd");
-  return 0;
+  const char* who = "cy_conv4x4s2_winograd";
+  hipStream_t s = (hipStream_t)stream;
+  if (in_scale) return cyi_launch_lds(who, wino2_conv_kernel<0, true>, (unsigned)blocks, 256, lds, s, a);
+  if (out_slope != 1.f) return cyi_launch_lds(who, wino2_conv_kernel<0, false, true>, (unsigned)blocks, 256, lds, s, a);
+  return cyi_launch_lds(who, wino2_conv_kernel<0, false>, (unsigned)blocks, 256, lds, s, a);
 }
 
 // tile-group ranges per image: enough blocks to cover the chip (one block per CU) when B * 4Cin/128 * Cout/64 is small
@@ -1214,12 +1172,10 @@ extern "C" int cy_conv4x4s2_winograd_wgrad(const float* X, const float* dZ, floa
   const long long blocks = (long long)B * a.nsplit * (4 * Cin / WQ) * (Cout / 64);
   CY_REQUIRE(blocks < (1ll << 31), "cy_conv4x4s2_winograd_wgrad: grid too large");
   const size_t lds = (size_t)(2 * V2_BUF + 2 * U2_BUF + RAWG_BUF) * 4;
-  int rc = in_scale ? cy_allow_lds(wino2_wgrad_kernel<true>, lds) : cy_allow_lds(wino2_wgrad_kernel<false>, lds);
-  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (in_scale) wino2_wgrad_kernel<true><<<(unsigned)blocks, 256, lds, s>>>(a);
-  else wino2_wgrad_kernel<false><<<(unsigned)blocks, 256, lds, s>>>(a);
-  CY_LAUNCH_CHECK("cy_conv4x4s2_winograd_wgrad");
+  int rc = in_scale ? cyi_launch_lds("cy_conv4x4s2_winograd_wgrad", wino2_wgrad_kernel<true>, (unsigned)blocks, 256, lds, s, a)
+                    : cyi_launch_lds("cy_conv4x4s2_winograd_wgrad", wino2_wgrad_kernel<false>, (unsigned)blocks, 256, lds, s, a);
+  if (rc) return rc;
   const long long n = (long long)4 * Cin * Cout;
   wino2_wgrad_finish_kernel<<<(unsigned)cy_ceil_div(n, 256), 256, 0, s>>>(ws, dW, B * a.nsplit, Cin, Cout);
   CY_LAUNCH_CHECK("cy_conv4x4s2_winograd_wgrad(finish)");
@@ -1266,12 +1222,8 @@ extern "C" int cy_conv4x4s2_winograd_dgrad(const float* dZ, const float* U, floa
   CY_REQUIRE(tiles < (1ll << 31), "cy_conv4x4s2_winograd_dgrad: too many tiles");
   a.ntiles = (int)tiles;
   long long blocks = 0;
-  int rcq = wino2_persistent_blocks(tiles, &blocks, "cy_conv4x4s2_winograd_dgrad");
+  int rcq = cyi_persistent_blocks("cy_conv4x4s2_winograd_dgrad", tiles, &blocks);
   if (rcq) return rcq;
   const size_t lds = (size_t)(2 * V2_BUF + 2 * U2_BUF + 2 * RAW2_BUF) * 4;
-  int rc = cy_allow_lds(wino2_conv_kernel<1, false>, lds);
-  if (rc) return rc;
-  wino2_conv_kernel<1, false><<<(unsigned)blocks, 256, lds, (hipStream_t)stream>>>(a);
-  CY_LAUNCH_CHECK("cy_conv4x4s2_winograd_dgrad");
-  return 0;
+  return cyi_launch_lds("cy_conv4x4s2_winograd_dgrad", wino2_conv_kernel<1, false>, (unsigned)blocks, 256, lds, (hipStream_t)stream, a);
 }

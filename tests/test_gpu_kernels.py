@@ -139,6 +139,20 @@ def test_conv3x3_winograd_input_gradient_splits_its_reduction(case, monkeypatch)
     close(dx, dx_unsplit, 2e-5, 2e-5)
 
 
+def test_workspace_queries_on_the_device():
+    """The workspace queries with the device's real CU count (cyi_cu_count; 256 on the MI355X): the 13 x 13 input gradient splits in two here
+    and not where no device answers (tests/test_launch_host.py has the same shapes there), the others come out as with the assumed 256."""
+    from capsyolo_amd._lib import query
+    assert query('cy_wino4_wgrad_ws_floats', 2, 16, 32, 32, 64) == 589824
+    assert query('cy_wino4_wgrad_ws_floats', 32, 208, 208, 128, 128) == 18874368
+    assert query('cy_wino4_wgrad_ws_floats', 1, 4, 16, 32, 64) == 73728
+    assert query('cy_wino_split_ws_floats', 16, 13, 13, 1024, 512, 1) == 2768896
+    assert query('cy_wino_split_ws_floats', 16, 13, 13, 1024, 512, 0) == 0
+    assert query('cy_wino_wgrad_ws_floats', 16, 64, 64) == 16778240
+    assert query('cy_wino_wgrad_ws_floats', 32, 128, 128) == 16778240
+    assert query('cy_wino2_wgrad_ws_floats', 4, 128, 256) == 18874368
+
+
 @pytest.mark.parametrize('case', [(2, 128, 16, 256), (1, 8, 10, 64), (3, 64, 37, 40), (2, 256, 18, 128), (2, 32, 15, 10),
                                   (3, 8, 200, 64), (2, 16, 104, 128)])   # > 256 tiles: persistent blocks walk several tiles
 @pytest.mark.parametrize('f4', [False, True])
