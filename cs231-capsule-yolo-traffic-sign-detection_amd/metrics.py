@@ -1,16 +1,20 @@
-"""Detection metrics of the reference on the device: metrics.detect_acc / detect_and_recog_acc / detect_AP /
-detect_and_recog_mAP (metrics.py:193-339).
+"""Metrics of the reference on the device: metrics.detect_acc / detect_and_recog_acc / detect_AP /
+detect_and_recog_mAP (metrics.py:193-339) and the classifier's report recog_auc / recog_pr (metrics.py:13-96).
 
 The reference decodes both arrays to boxes with numpy and matches them with two nested Python loops per image
 (metrics.py:136-147) every `eval_every` epochs; here the decoding (`cy_yolo_decode_boxes`) and the IoU matching
 (`cy_detect_confusion`, one block per image) stay on the GPU and only TP / FP / FN come back.  `confusion_sweep` does the whole
 confidence x IoU threshold sweep of the AP metrics with one decode per array and one launch (`cy_confusion_sweep`).
+
+The reference computes recog_auc / recog_pr with sklearn's sort-based curves on the host.  Both are rank statistics of the N
+positive scores, so here the device counts, for every row, the population elements at or above its positive score
+(`cy_rank_counts`, no sort of the scores) and the host folds the integer counts into the two numbers.
 """
 import numpy as np
 import torch
 
 from . import utils
-from ._lib import call
+from ._lib import call, query
 
 
 def _confusion_of_boxes(gt, pr, y, y_hat, params, iou_th):
@@ -83,6 +87,98 @@ def recog_acc(y, y_hat, params):
     """metrics.py:9-11."""
     y, y_hat = [t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in (y, y_hat)]
     return np.sum(y == np.argmax(y_hat, axis=1)) / len(y)
+
+
+def recog_counts(y, y_hat, n_classes):
+    """The rank counts of the classifier's report: (counts, correct) with counts int64 numpy [2][N][4] = (cnt_ge, cnt_gt, tp_ge,
+    tp_gt) per row i -- the number of elements of a population, and of its positives, whose score is >= and > the row's positive
+    score y_hat[i][y[i]]; counts[0]: micro (all N * C elements, positive iff column == label), counts[1]: per class (column y[i]) --
+    and correct = np.sum(y == np.argmax(y_hat, axis=1)).  y [N] integer labels, y_hat [N][n_classes] scores, numpy arrays or
+    device tensors.  Scores are compared as float32 VALUES (-0.0 == +0.0): another dtype is converted to float32 first, so
+    float64 scores that differ only beyond float32 count as ties.  ValueError: no rows, a label outside 0..n_classes-1, a
+    non-finite score (the reference stops on these too: sklearn refuses NaN / inf, np.eye(C)[y] a bad label)."""
+    C = int(n_classes)
+    s = _as_device_f32(y_hat)
+    if s.dim() != 2 or int(s.shape[1]) != C or C < 1:
+        raise ValueError('recog_counts: scores of shape %s for %d classes' % (tuple(s.shape), C))
+    N = int(s.shape[0])
+    lab = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y)
+    if lab.is_floating_point() or lab.dtype == torch.bool or lab.dim() != 1 or int(lab.shape[0]) != N:
+        raise ValueError('recog_counts: labels %s %s for %d rows of scores' % (lab.dtype, tuple(lab.shape), N))
+    if N == 0:
+        raise ValueError('recog_counts: no samples')
+    lab = lab.to(device='cuda', dtype=torch.int64).contiguous()
+    order = torch.sort(lab, stable=True)[1].to(torch.int32)               # rows grouped by label: the LABELS are sorted, never the scores
+    ws = torch.empty(max(int(query('cy_rank_ws_ints', N, C)), 1), dtype=torch.int32, device='cuda')
+    out = torch.zeros(8 * N + 2, dtype=torch.int32, device='cuda')        # the table, the number of correct rows, the error word
+    call('cy_rank_counts', s.data_ptr(), lab.data_ptr(), order.data_ptr(), N, C, ws.data_ptr(), out.data_ptr(),
+         out.data_ptr() + 4 * 8 * N, out.data_ptr() + 4 * (8 * N + 1), torch.cuda.current_stream().cuda_stream)
+    host = out.cpu().numpy()
+    if host[-1]:
+        raise ValueError('recog_counts: %d label(s) outside 0..%d or non-finite score(s)' % (host[-1], C - 1))
+    return host[:8 * N].astype(np.int64).reshape(2, N, 4), int(host[-2])
+
+
+def auc_from_counts(cnt, n_pos, n_neg):
+    """roc_curve + auc (trapezoid over the distinct thresholds) of a population with n_pos positives and n_neg negatives from
+    the rows cnt [n_pos][4] of its positives: a positive beats the negatives below it and half of those it ties with.  The
+    numerator is an integer (about 1.3e10 for the GTSRB test set: int64); NaN without a positive or without a negative."""
+    if n_pos == 0 or n_neg == 0:
+        return float('nan')
+    neg_ge, neg_gt = cnt[:, 0] - cnt[:, 2], cnt[:, 1] - cnt[:, 3]
+    return int(np.sum(2 * (n_neg - neg_ge) + (neg_ge - neg_gt), dtype=np.int64)) / (2 * int(n_pos) * int(n_neg))
+
+
+def ap_from_counts(cnt, n_pos, n_neg):
+    """average_precision_score (step-wise): every positive adds 1 / n_pos of recall at the precision of its threshold."""
+    if n_pos == 0 or n_neg == 0:
+        return float('nan')
+    return float(np.sum(cnt[:, 2] / cnt[:, 0]) / n_pos)
+
+
+def _per_class(fold, y, y_hat, n_classes):
+    counts, _ = recog_counts(y, y_hat, n_classes)
+    lab = (y.detach().cpu().numpy() if torch.is_tensor(y) else np.asarray(y)).astype(np.int64)
+    out = np.full(int(n_classes), np.nan)
+    for c in range(int(n_classes)):
+        rows = counts[1][lab == c]
+        out[c] = fold(rows, len(rows), len(lab) - len(rows))
+    return out
+
+
+def recog_auc_per_class(y, y_hat, n_classes):
+    """[C] ROC AUC of every class against the rest (the roc_auc[i] the reference computes and drops, metrics.py:20-22); NaN for
+    a class without a positive or without a negative."""
+    return _per_class(auc_from_counts, y, y_hat, n_classes)
+
+
+def recog_pr_per_class(y, y_hat, n_classes):
+    """[C] average precision of every class (metrics.py:61-65); NaN for a class without a positive or without a negative."""
+    return _per_class(ap_from_counts, y, y_hat, n_classes)
+
+
+def recog_auc(y, y_hat, params, show=False, save=False, save_dir=None):
+    """metrics.py:13-51 (the plot is out of scope: show / save are accepted and nothing is drawn): the micro-averaged ROC AUC
+    over all N * C (sample, class) elements.  Scores are compared as float32, see recog_counts."""
+    counts, _ = recog_counts(y, y_hat, params.n_classes)
+    n = counts.shape[1]
+    return auc_from_counts(counts[0], n, n * (int(params.n_classes) - 1))
+
+
+def recog_pr(y, y_hat, params, show=False, save=False, save_dir=None):
+    """metrics.py:54-96 (the plot is out of scope): the micro-averaged average precision.  Scores are compared as float32, see
+    recog_counts."""
+    counts, _ = recog_counts(y, y_hat, params.n_classes)
+    return float(np.sum(counts[0][:, 2] / counts[0][:, 0]) / counts.shape[1])
+
+
+def recog_report(y, y_hat, params):
+    """What the class-only branch of predict mode reports (main.py:312-317), in its key order, from ONE count:
+    {'recog_pr', 'recog_acc', 'recog_auc'}, each equal to what the function of that name returns."""
+    counts, correct = recog_counts(y, y_hat, params.n_classes)
+    n = counts.shape[1]
+    return {'recog_pr': float(np.sum(counts[0][:, 2] / counts[0][:, 0]) / n), 'recog_acc': correct / n,
+            'recog_auc': auc_from_counts(counts[0], n, n * (int(params.n_classes) - 1))}
 
 
 def average_precision(p, r):

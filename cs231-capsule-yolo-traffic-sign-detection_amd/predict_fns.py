@@ -20,19 +20,33 @@ def _restore(model, model_dir, params, restore_file):
     utils.load_checkpoint(path, model, params)
 
 
-def _eval_forward_batched(x, model, params, batch_size):
+def _eval_chunks(x, model, params, batch_size):
     """The reference pushes the WHOLE set through the model in one call (predict_fns.py:40-43, 65-69: x [N,3,448,448]).
     In eval mode every sample is independent (BatchNorm uses the running statistics, folded into the conv weights here:
-    ops.fold_eval_bn), so the set goes through in chunks of `batch_size` with identical results and bounded memory."""
+    ops.fold_eval_bn), so the set goes through in chunks of `batch_size` with identical results and bounded memory.
+    Yields each chunk's output as a device tensor."""
     n = int(x.shape[0])
     bs = n if not batch_size else int(batch_size)
-    outs = []
     model.eval()
     with torch.no_grad():
         for lo in range(0, n, max(bs, 1)):
             xt = torch.from_numpy(np.ascontiguousarray(x[lo:lo + bs])).to(device=params.device, dtype=torch.float32)
-            outs.append(model(xt.permute(0, 3, 1, 2).contiguous()).data.cpu().numpy())
+            yield model(xt.permute(0, 3, 1, 2).contiguous()).data
+
+
+def _eval_forward_batched(x, model, params, batch_size):
+    outs = [o.cpu().numpy() for o in _eval_chunks(x, model, params, batch_size)]
     return np.concatenate(outs, axis=0) if len(outs) != 1 else outs[0]
+
+
+def class_scores_device(x, model, params, batch_size=1024):
+    """The forward of class_pred (same chunks, same kernels, so the same bits) with the scores left on the device: x NHWC numpy
+    -> float32 device tensor [N, n_classes], no per-chunk copy to the host.  What metrics.recog_counts reads in place.  The
+    checkpoint is the caller's business (class_pred restores it, this does not)."""
+    outs = list(_eval_chunks(x, model, params, batch_size))
+    if not outs:
+        raise ValueError('class_scores_device: no samples')
+    return torch.cat(outs, 0) if len(outs) != 1 else outs[0]
 
 
 def class_pred(x, model, model_dir, params, restore_file, batch_size=1024):

@@ -504,6 +504,22 @@ int cy_yolo_decode_boxes_conf(const float* y, const long long* image_hw, double 
 int cy_confusion_sweep(const int* gt_key, const double* gt_xy, const float* gt_conf, int n_gt, const int* pr_key,
                        const double* pr_xy, const float* pr_conf, int n_pr, int n_groups, int C, const double* conf_ths, int K,
                        const double* iou_ths, int T, int max_per_group, int* out, int* err, void* stream);
+/* ------------------------------------------------------------------ classifier report (csrc/rank.hip)
+ * The integer rank counts behind metrics.recog_auc / recog_pr / recog_acc (metrics.py:9-96; sklearn's roc_curve + auc and
+ * average_precision_score there), with no sort of the scores.  scores[N][C] fp32, labels[N] int64; element (i, c) is positive iff
+ * c == labels[i], and p_i = scores[i][labels[i]].  Values are compared as floats (-0.0 == +0.0, denormals are not flushed).
+ * For every row i, counts[2][N][4] (int32, caller-zeroed) receives (cnt_ge, cnt_gt, tp_ge, tp_gt): the number of elements of
+ * a population, and of its positives, whose score is >= p_i and > p_i --
+ *   counts[0]: micro, the population is all N*C elements;  counts[1]: per class, the population is column labels[i].
+ * *correct (caller-zeroed) += the rows whose label is the FIRST maximum of the row (np.argmax).  *err (caller-zeroed) +=
+ * the labels outside 0..C-1 and the non-finite scores (then the counts mean nothing; nothing is read or written out of bounds).
+ * order[N] int32: the row indices sorted by label ascending (any order inside a label; the caller sorts the LABELS, the scores
+ * are never sorted); an entry outside 0..N-1 or a descending pair of labels is counted in *err.  ws: cy_rank_ws_ints(N, C)
+ * ints of scratch.  Integer atomics only: the result is bit-identical from run to run and does not depend on the grid.
+ * N*C >= 2^31 is refused (CY_EINVAL); cy_rank_ws_ints returns 0 for such a shape. */
+long long cy_rank_ws_ints(int N, int C);
+int cy_rank_counts(const float* scores, const long long* labels, const int* order, int N, int C, int* ws, int* counts,
+                   int* correct, int* err, void* stream);
 /* torch.gather of the labelled capsule (models.py:122): backward=0: out[B][D] = caps[b][y[b]][:];
  * backward=1: caps is d(out) [B][D], out = d(caps) [B][C][D] (zero off the labelled capsule) */
 int cy_pick_capsule(const float* caps, const long long* y, float* out, int B, int C, int D, int backward, void* stream);

@@ -14,7 +14,9 @@ keys, same registry shape ``name -> (ModelCls, loss_fn, predict_fn, metric)`` (m
   --model darkcapsule2 | darkcapsule3   the reference's unwired variants with their losses (models.py:271-337, 403-463)
 ``--mode predict --model darknet_d|darknet_r --combine cnn|capsule --restore last|best`` runs the two-stage chain
 (predict_fns.dark_class_pred) and writes detect_and_recog_mAP / detect_and_recog_acc to combine-<name>_metric_output.txt
-(main.py:329-356); drawing the boxes and the detect-only / class-only predict branches are not wired (see predict()).
+(main.py:329-356); ``--mode predict --model cnn|capsule --restore last|best`` runs the classifier over the test set and writes
+recog_pr / recog_acc / recog_auc to metric_output.txt (main.py:309-317, 349-356), the curves counted on the device
+(metrics.recog_report).  Drawing the boxes and curves and the detect-only predict branch are not wired (see predict()).
 Data-parallel: launch with ``python -m torch.distributed.run --nproc-per-node N main.py ...``; every rank takes
 its equal shard of each global batch, gradients are averaged with one RCCL all-reduce per step, epoch losses are
 averaged over the ranks before the LR scheduler sees them, metrics run on the gathered predictions, rank 0 writes.
@@ -38,7 +40,7 @@ from capsyolo_amd.loss_fns import (capsule_loss, cnn_loss, dark_loss, darkcapsul
                                    darkcapsule_loss)
 from capsyolo_amd.models import CapsuleNet, ConvNet, DarkCapsuleNet, DarkCapsuleNet2, DarkCapsuleNet3, DarkNet  # noqa: E402
 from capsyolo_amd.optim import Adam  # noqa: E402
-from capsyolo_amd.predict_fns import class_pred, dark_class_pred, dark_forward  # noqa: E402
+from capsyolo_amd.predict_fns import class_pred, class_scores_device, dark_class_pred, dark_forward  # noqa: E402
 
 parser = argparse.ArgumentParser()
 parser.add_argument('--model', default='cnn', help=' | '.join(config.model_names))
@@ -319,17 +321,46 @@ def synthetic_data(args, params):
     return x_tr, y_tr, x_ev, y_ev
 
 
+def predict_class(args, model, model_dir, data_dir, params):
+    """main.py:303-317, 349-356, the class-only branch: `--model cnn|capsule --restore last|best` pushes the test set (`--synthetic
+    N`: N synthetic GTSRB-shaped samples, otherwise the pickled (x, y) at data_dir/test.p) through the restored classifier and
+    writes recog_pr / recog_acc / recog_auc to <model_dir>/metric_output.txt in the reference's format and key order.  The
+    scores stay on the device, where the rank counts behind all three numbers are taken in one call (metrics.recog_report); the
+    reference's two curve plots (r_auc.png, r_pr.png) are not drawn."""
+    if params.device != 'cuda':
+        raise SystemExit('predict mode runs on hand-written gfx950 kernels only; no GPU is visible')
+    if args.synthetic:
+        x, y = synth.images(args.synthetic, 32), synth.gtsrb_labels(args.synthetic, params.n_classes)
+    else:
+        import pickle
+        with open(data_dir + config.te_d, 'rb') as f:
+            x, y = pickle.load(f)
+    path = os.path.join(model_dir, args.restore + '.pth.tar')
+    print("Restoring parameters from {}".format(path))
+    utils.load_checkpoint(path, model, params)
+    scores = class_scores_device(np.asarray(x), model, params, batch_size=params.batch_size)
+    metric_out = metrics.recog_report(y, scores.reshape(len(y), -1), params)
+    with open(os.path.join(model_dir, 'metric_output.txt'), 'w') as text_file:
+        for k, v in metric_out.items():
+            text_file.write("{}:{}, ".format(k, v))
+            print("{}:{}, ".format(k, v))
+    return metric_out
+
+
 def predict(args, model, model_dir, data_dir, params):
-    """main.py:293-356, the combined branch: `--model darknet_d|darknet_r --combine cnn|capsule --restore last|best` runs
+    """main.py:293-356: `--model cnn|capsule` is the class-only branch (predict_class).  The combined branch,
+    `--model darknet_d|darknet_r --combine cnn|capsule --restore last|best`, runs
     dark_class_pred and writes detect_and_recog_mAP / detect_and_recog_acc to <model_dir>/combine-<name>_metric_output.txt.
     The images are a list of raw HWC uint8 arrays: `--synthetic N` draws them (with labels) from synth, otherwise they come from
     data_dir/test_images.npy (an object array) next to data_dir/test.p.  The classifier's directory is config.model_dir[--combine]
     or, with --model_dir, its sibling <model_dir>/../<name>.  Nothing is drawn and no cv2 is needed."""
     if args.restore is None:
         raise SystemExit('Must give restore file last/best')                           # main.py:294-296
+    if args.model in ('cnn', 'capsule'):
+        return predict_class(args, model, model_dir, data_dir, params)
     if args.model not in ('darknet_d', 'darknet_r') or args.combine not in ('cnn', 'capsule'):
-        raise SystemExit('predict mode runs the combined chain only: --model darknet_d|darknet_r --combine cnn|capsule; the '
-                         'eval-mode forwards of the other branches are capsyolo_amd.predict_fns.class_pred / dark_pred')
+        raise SystemExit('predict mode runs --model cnn|capsule, or the combined chain --model darknet_d|darknet_r --combine '
+                         'cnn|capsule; the eval-mode forward of the detect-only branch is capsyolo_amd.predict_fns.dark_pred')
     class_model_dir = config.model_dir[args.combine] if args.model_dir is None else \
         os.path.join(os.path.dirname(os.path.abspath(model_dir)), args.combine)
     class_args = argparse.Namespace(**dict(vars(args), model=args.combine))
