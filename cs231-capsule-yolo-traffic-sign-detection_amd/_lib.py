@@ -47,6 +47,12 @@ class RoutingBwd(C.Structure):
                 ('n_iter', C.c_int), ('gather_g', C.c_int), ('gather_B', C.c_int)]
 
 
+class Decoder(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ('caps', 'labels', 'deltas', 'x', 'lin_w', 'lin_b', 'w4', 'b4', 'w7', 'b7', 'w10', 'b10',
+                                          'w12', 'b12', 'out_f32', 'out_u8', 'sqerr', 'err')] + \
+               [(k, C.c_int) for k in ('n', 'C', 'D', 'n_delta')]
+
+
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_longlong
 
 # name -> argtypes (all return int unless listed in _RET)
@@ -127,6 +133,7 @@ _SIGS = {
     'cy_confusion_sweep': [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P],
     'cy_rank_counts': [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
     'cy_pick_capsule': [_P, _P, _P, _I, _I, _I, _I, _P],
+    'cy_decoder_fwd': [C.POINTER(Decoder), _P],
     'cy_zero_bytes': [_P, _L, _P],
     'cy_conv_bf16_pack_weights': [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     'cy_conv_gemm_bf16': [C.POINTER(ConvGemm), _I, _P],

@@ -254,6 +254,12 @@ class CapsuleNet(nn.Module):
             return scores
         return scores, self.decoder(ops.pick_capsule(caps, y))
 
+    def capsules(self, x):
+        """The capsule vectors [B,C,16] that forward reduces to lengths (capsule_interpret.py:54-56): forward up to
+        traffic_sign_capsules, x NCHW."""
+        h = self.conv1(x, nchw_in=True, slope=0.0)
+        return self.traffic_sign_capsules(self.primary_capsules(h))
+
 
 _DARKNET_PLAN = [
     (32, 3, 'M'), (64, 3, 'M'), (128, 3, 'D'), (64, 1, 'D'), (128, 3, 'M'),

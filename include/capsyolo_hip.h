@@ -523,6 +523,25 @@ int cy_rank_counts(const float* scores, const long long* labels, const int* orde
 /* torch.gather of the labelled capsule (models.py:122): backward=0: out[B][D] = caps[b][y[b]][:];
  * backward=1: caps is d(out) [B][D], out = d(caps) [B][C][D] (zero off the labelled capsule) */
 int cy_pick_capsule(const float* caps, const long long* y, float* out, int B, int C, int D, int backward, void* stream);
+/* ------------------------------------------------------------------ capsule interpretation (csrc/decoder.hip)
+ * The whole decoder forward of CapsuleNet (models.py:96-111) in one launch, with the gather and the perturbation of
+ * capsule_interpret.py:58-68 formed in the kernel.  The ten parameter pointers are the state-dict tensors of decoder.0 / 4 / 7 / 10 /
+ * 12 as they are (Linear [256][16], convolutions OIHW); nothing is packed on the host.
+ * Launch rows: with deltas, row (b, v, i) = (b * 16 + v) * n_delta + i decodes source vector b with deltas[i] added (fp32) to its
+ * component v; without, row b decodes source vector b.  Source vector b is caps[b][labels[b]][:] of caps [n][C][16], or, without
+ * labels (then C = 1), row b of a dense caps [n][16].  *err (caller-zeroed; required with labels) += the rows whose label lies
+ * outside 0..C-1; such rows write nothing.
+ * Outputs, each optional, at least one, all from the same arithmetic: out_f32 [rows][3][32][32]; out_u8 [rows][32][32][3] =
+ * rint(v * 128 + 128) (half to even) clamped to 0..255; sqerr [rows] = sum over the 3 072 elements of (x[b] - out)^2 against the
+ * NCHW image x [n][3][32][32], summed in a fixed order (bit-identical from run to run).  D must be 16.  Nothing is allocated. */
+typedef struct {
+  const float* caps; const long long* labels; const float* deltas; const float* x;
+  const float* lin_w; const float* lin_b; const float* w4; const float* b4; const float* w7; const float* b7;
+  const float* w10; const float* b10; const float* w12; const float* b12;
+  float* out_f32; unsigned char* out_u8; float* sqerr; int* err;
+  int n, C, D, n_delta;
+} cy_decoder_t;
+int cy_decoder_fwd(const cy_decoder_t* a, void* stream);
 
 /* ------------------------------------------------------------------ optimizer
  * torch.optim.Adam step (main.py:72,280) for a list of tensors in ONE launch.

@@ -17,6 +17,9 @@ keys, same registry shape ``name -> (ModelCls, loss_fn, predict_fn, metric)`` (m
 (main.py:329-356); ``--mode predict --model cnn|capsule --restore last|best`` runs the classifier over the test set and writes
 recog_pr / recog_acc / recog_auc to metric_output.txt (main.py:309-317, 349-356), the curves counted on the device
 (metrics.recog_report).  Drawing the boxes and curves and the detect-only predict branch are not wired (see predict()).
+``--mode interpret --model capsule --restore last|best [--synthetic N] [--index I]`` is the reference's capsule_interpret.py:
+the 16 x 11 perturbation sweep of sample I's labelled capsule through the fused decoder kernel, written to <model_dir>/img/
+(see interpret()).
 Data-parallel: launch with ``python -m torch.distributed.run --nproc-per-node N main.py ...``; every rank takes
 its equal shard of each global batch, gradients are averaged with one RCCL all-reduce per step, epoch losses are
 averaged over the ranks before the LR scheduler sees them, metrics run on the gathered predictions, rank 0 writes.
@@ -35,6 +38,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 import capsyolo_amd  # noqa: E402,F401
 from capsyolo_amd import config, dp, metrics, synth, utils  # noqa: E402
+from capsyolo_amd import interpret as capsule_interpret  # noqa: E402
 from capsyolo_amd.input_pipeline import DeviceFeeder, quantize_if_exact  # noqa: E402
 from capsyolo_amd.loss_fns import (capsule_loss, cnn_loss, dark_loss, darkcapsule2_loss, darkcapsule3_loss,  # noqa: E402
                                    darkcapsule_loss)
@@ -44,7 +48,7 @@ from capsyolo_amd.predict_fns import class_pred, class_scores_device, dark_class
 
 parser = argparse.ArgumentParser()
 parser.add_argument('--model', default='cnn', help=' | '.join(config.model_names))
-parser.add_argument('--mode', default='train', help='train | predict | overfit')
+parser.add_argument('--mode', default='train', help='train | predict | overfit | interpret')
 parser.add_argument('--summary', default=True, help='if summarize model', action='store_true')
 parser.add_argument('--seed', type=int, default=0, help='random seed')
 parser.add_argument('--lr', type=float, default=1e-3, help='learning rate')
@@ -61,6 +65,7 @@ parser.add_argument('--model_dir', default=None, help='model dir')
 parser.add_argument('--show', default=False, help='save result', action='store_true')
 parser.add_argument('--npy', default=False, help='data is npy file', action='store_true')
 parser.add_argument('--synthetic', type=int, default=0, help='use N synthetic samples instead of data/')
+parser.add_argument('--index', type=int, default=0, help='--mode interpret: which sample of the eval set (or of the --synthetic samples)')
 parser.add_argument('--n_epochs', type=int, default=0, help='override params.json n_epochs')
 parser.add_argument('--batch_size', type=int, default=0, help='override params.json batch_size')
 parser.add_argument('--graph', action='store_true',
@@ -384,6 +389,43 @@ def predict(args, model, model_dir, data_dir, params):
     return metric_out
 
 
+def interpret(args, model, model_dir, data_dir, params):
+    """capsule_interpret.py:27-68 as a mode: restore the checkpoint, take sample --index of the eval set (data_dir/eval.p, or of
+    `--synthetic N` samples), and write into <model_dir>/img/ the sample (orig.ppm), the 16 x 11 reconstructions <v>-<i>.ppm of its
+    labelled capsule with offset i added to component v (the reference's file names; binary PPM, neither cv2 nor a PNG encoder is
+    needed), all of them as sweep.npy (uint8 [16,11,32,32,3]) and as one contact sheet sheet.ppm (row v, column i).  Prints the
+    sample's label, its predicted class and the squared error of the unperturbed reconstruction."""
+    if args.model != 'capsule':
+        raise SystemExit('interpret mode decodes capsule vectors: it runs --model capsule only')
+    if args.restore is None:
+        raise SystemExit('Must give restore file last/best')
+    if params.device != 'cuda':
+        raise SystemExit('interpret mode runs on hand-written gfx950 kernels only; no GPU is visible')
+    if args.synthetic:
+        x, y = synth.images(args.synthetic, 32), synth.gtsrb_labels(args.synthetic, params.n_classes)
+    else:
+        import pickle
+        with open(data_dir + config.ev_d, 'rb') as f:
+            x, y = pickle.load(f)
+    if not 0 <= args.index < len(y):
+        raise SystemExit('--index %d: the set has %d samples' % (args.index, len(y)))
+    path = os.path.join(model_dir, args.restore + '.pth.tar')
+    print("Restoring parameters from {}".format(path))
+    utils.load_checkpoint(path, model, params)
+    res = capsule_interpret.interpret_sample(model, np.asarray(x[args.index]), int(y[args.index]), params)
+    sweep = res['sweep'].cpu().numpy()
+    img_dir = os.path.join(model_dir, 'img')
+    os.makedirs(img_dir, exist_ok=True)
+    capsule_interpret.write_ppm(os.path.join(img_dir, 'orig.ppm'), capsule_interpret.to_bytes(x[args.index]))
+    for v in range(sweep.shape[0]):
+        for i in range(sweep.shape[1]):
+            capsule_interpret.write_ppm(os.path.join(img_dir, '%d-%d.ppm' % (v, i)), sweep[v, i])
+    np.save(os.path.join(img_dir, 'sweep.npy'), sweep)
+    capsule_interpret.write_ppm(os.path.join(img_dir, 'sheet.ppm'), capsule_interpret.contact_sheet(sweep))
+    print('sample {} | label: {} | predicted: {} | sqerr: {:.6f}'.format(args.index, res['label'], res['pred'], res['sqerr']))
+    return res
+
+
 def main(argv=None):
     args = parser.parse_args(argv)
     if args.model not in config.model_names:
@@ -432,6 +474,8 @@ def main(argv=None):
         return train_and_evaluate(model, optimizer, loss_fn, metric, params, data, model_dir, restore_file=args.restore)
     if args.mode == 'predict':
         return predict(args, model, model_dir, data_dir, params)
+    if args.mode == 'interpret':
+        return interpret(args, model, model_dir, data_dir, params)
 
 
 if __name__ == '__main__':
