@@ -131,6 +131,7 @@ _SIGS = {
     'cy_combine_scores': [_P, _P, _P, _P, _I, _P, C.c_double, _I, _I, _I, _I, _P, _P, _P, _P],
     'cy_yolo_decode_boxes_conf': [_P, _P, C.c_double, C.c_double, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P],
     'cy_confusion_sweep': [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P],
+    'cy_draw_boxes_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _I, _P, _P, _P],
     'cy_rank_counts': [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
     'cy_pick_capsule': [_P, _P, _P, _I, _I, _I, _I, _P],
     'cy_decoder_fwd': [C.POINTER(Decoder), _P],

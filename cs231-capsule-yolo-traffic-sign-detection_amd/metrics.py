@@ -1,5 +1,5 @@
 """Metrics of the reference on the device: metrics.detect_acc / detect_and_recog_acc / detect_AP /
-detect_and_recog_mAP (metrics.py:193-339) and the classifier's report recog_auc / recog_pr (metrics.py:13-96).
+detect_and_recog_mAP (metrics.py:193-339), detect_report (the two numbers of predict mode's detect-only branch from one sweep) and the classifier's report recog_auc / recog_pr (metrics.py:13-96).
 
 The reference decodes both arrays to boxes with numpy and matches them with two nested Python loops per image
 (metrics.py:136-147) every `eval_every` epochs; here the decoding (`cy_yolo_decode_boxes`) and the IoU matching
@@ -261,6 +261,18 @@ def _ap_table(counts):
             pr = [precision_and_recall(*[int(v) for v in counts[k, c, t]]) for k in range(K)]
             table[c, t] = average_precision(np.array([p for p, _ in pr]), np.array([r for _, r in pr]))
     return table
+
+
+def detect_report(y, y_hat, params):
+    """What the detect-only branch of predict mode reports (main.py:324-327), in its key order, from ONE sweep:
+    {'detect_AP', 'detect_acc'}, each equal to what the function of that name returns (the same integer counts, folded the same
+    way).  The class-agnostic count table over the 100 confidence thresholds of detect_AP plus detect_acc's 0.5, and the 10 IoU
+    thresholds, whose first is detect_acc's 0.5: one decode per array and one launch where detect_AP decodes 200 times and
+    launches 1000 times."""
+    conf_ths, iou_ths = np.concatenate([np.linspace(0, 1, 100), [0.5]]), np.linspace(0.5, 0.95, 10)
+    counts = confusion_sweep(y, y_hat, params, conf_ths, iou_ths, per_class=False)
+    p, r = precision_and_recall(*[int(v) for v in counts[100, 0, 0]])
+    return {'detect_AP': np.mean(_ap_table(counts[:100])[0]), 'detect_acc': 2 * p * r / (p + r + 1e-8)}
 
 
 def detect_and_recog_mAP(y, y_hat, params, show=False, save=False, save_dir=None):

@@ -3,13 +3,15 @@ box crops -> classifier -> combined y_hat with every step between the two forwar
 
 Resizing follows cv2.resize's INTER_LINEAR half-pixel convention (source coordinate (o + 0.5) * n_in / n_out - 0.5, neighbours
 clamped into the image or crop), interpolated in fp32.  cv2's 11-bit fixed-point rounding of the weights is NOT reproduced (cv2
-is not a dependency, so the difference could not be measured; it is expected to stay within one grey level).  Drawing boxes
-and writing JPEGs (plot.draw_boxes_vec's images) is out of scope: where the reference returns the drawn images, None is returned."""
+is not a dependency, so the difference could not be measured; it is expected to stay within one grey level).  The images with the
+boxes drawn (plot.draw_boxes_vec) are returned where `draw=True` asks for them, drawn on the device while a chunk's packed images
+are there (draw.py, `cy_draw_boxes_u8`); the default returns None in their place and draws nothing.  JPEGs are not written."""
 import os
 
 import numpy as np
 import torch
 
+from . import draw as box_draw
 from . import utils
 from ._lib import call
 
@@ -114,20 +116,28 @@ def resize_images_device(images, side):
     return PackedImages(images).resize(int(side), to_nchw=True)
 
 
-def _detect_and_crop(images, model, params, conf_th, batch_size, crop_side, shift, scale, to_nchw):
+def _chunk_size(n, batch_size):
+    return max(int(batch_size) if batch_size else n, 1)
+
+
+def _detect_and_crop(images, model, params, conf_th, batch_size, crop_side, shift, scale, to_nchw, drawer=None):
     """Chunks of `batch_size` images: upload -> resize -> eval forward -> decode with the images' own sizes -> rectangles ->
     crops, all but the rectangle rule (a few integers per box, in double on the host) on the device.
-    Returns (y_hat device [B,g,g,D], crops device, image_indices int64 numpy, boxes_xy float64 numpy)."""
+    Returns (y_hat device [B,g,g,D], crops device, image_indices int64 numpy, boxes_xy float64 numpy).  drawer (optional):
+    called as drawer(lo, packed, image_indices, boxes_xy, classes) with every chunk's boxes (indices inside the chunk, classes an
+    int64 numpy array or None) while its packed images are on the device."""
     n = len(images)
-    bs = max(int(batch_size) if batch_size else n, 1)
+    bs = _chunk_size(n, batch_size)
     y_hats, crops, idxs, xys = [], [], [], []
     model.eval()
     with torch.no_grad():
         for lo in range(0, n, bs):
             packed = PackedImages(images[lo:lo + bs], params.device)
             y_hat = model(packed.resize(int(params.darknet_input), to_nchw=True)).data
-            nbox, idx, xy, _ = utils.decode_boxes_device(y_hat, params, packed.hw, conf_th)
+            nbox, idx, xy, cls = utils.decode_boxes_device(y_hat, params, packed.hw, conf_th)
             idx_np, xy_np = idx.cpu().numpy().astype(np.int64), xy.cpu().numpy()
+            if drawer is not None:
+                drawer(lo, packed, idx_np, xy_np, cls.cpu().numpy().astype(np.int64) if cls is not None else None)
             try:
                 rect = utils.crop_rectangles(xy_np, idx_np, packed.hw)
             except ValueError as e:
@@ -139,23 +149,42 @@ def _detect_and_crop(images, model, params, conf_th, batch_size, crop_side, shif
     return torch.cat(y_hats, 0), torch.cat(crops, 0), np.concatenate(idxs), np.concatenate(xys, 0)
 
 
-def dark_pred(images, model, model_dir, params, restore_file, is_end=True, conf_th=0.5, y=None, batch_size=32):
-    """predict_fns.py:10-58.  images: list of HWC uint8 arrays of different sizes.  is_end=True: (y_hat, None) -- the reference
-    returns the images with the boxes drawn, which is out of scope (`y` only adds the ground-truth boxes to that drawing and is
-    ignored).  is_end=False: (y_hat, crops float32 numpy [n_boxes, ci, ci, 3] on the raw 0..255 scale like the reference,
+def dark_pred(images, model, model_dir, params, restore_file, is_end=True, conf_th=0.5, y=None, batch_size=32, draw=False):
+    """predict_fns.py:10-58.  images: list of HWC uint8 arrays of different sizes.  is_end=True: (y_hat, None), or with draw=True
+    (new, optional) (y_hat, images): the reference's second value, copies of the images with the boxes over conf_th in green,
+    labelled with the detector's argmax class when params.n_classes > 0, and, when the labels y [n, g, g, 5 + C] are given, the
+    ground-truth boxes in red on top (predict_fns.py:46-51; decoded like the predictions, so from float32 values).  Both sets
+    are drawn in one launch per chunk, ground truth last (draw.draw_boxes_device).  Without draw, y is not read.
+    is_end=False: (y_hat, crops float32 numpy [n_boxes, ci, ci, 3] on the raw 0..255 scale like the reference,
     image_indices [n_boxes], boxes_xy [n_boxes, 4] in pixels of the original images)."""
     _restore(model, model_dir, params, restore_file)
     ci = int(params.capsule_input)
-    y_hat, crops, idx, xy = _detect_and_crop(images, model, params, conf_th, batch_size, ci, 0.0, 1.0, False)
+    drawn = []
+
+    def drawer(lo, packed, idx, xy, cls):
+        colors = np.tile(np.array(box_draw.GREEN, dtype=np.uint8), (len(idx), 1))
+        if y is not None:
+            _, t_idx, t_xy, t_cls = utils.decode_boxes_device(y[lo:lo + packed.n], params, packed.hw, conf_th)
+            idx = np.concatenate([idx, t_idx.cpu().numpy().astype(np.int64)])
+            xy = np.concatenate([xy.reshape(-1, 4), t_xy.cpu().numpy().reshape(-1, 4)])
+            if cls is not None:
+                cls = np.concatenate([cls, t_cls.cpu().numpy().astype(np.int64)])
+            colors = np.concatenate([colors, np.tile(np.array(box_draw.RED, dtype=np.uint8), (len(idx) - len(colors), 1))])
+        drawn.extend(box_draw.unpack_images(box_draw.draw_boxes_device(packed, idx, xy, colors, cls), packed))
+    want = bool(draw) and is_end
+    y_hat, crops, idx, xy = _detect_and_crop(images, model, params, conf_th, batch_size, ci, 0.0, 1.0, False, drawer if want else None)
     if is_end:
-        return y_hat.cpu().numpy(), None
+        return y_hat.cpu().numpy(), (drawn if want else None)
     return y_hat.cpu().numpy(), crops.cpu().numpy(), idx, xy
 
 
 def dark_class_pred(images, dark_model, dark_model_dir, dark_params, class_model, class_model_dir, class_params, restore_file,
-                    batch_size=32, conf_th=0.5):
+                    batch_size=32, conf_th=0.5, draw=False):
     """predict_fns.py:75-82: detector -> crop of every box -> classifier -> utils.combine_y_hat.  Returns (y_hat float64 numpy
-    [B, g, g, D + n_classes], None); the second value is the reference's drawn images (out of scope).  The crops are produced
+    [B, g, g, D + n_classes], None), or with draw=True (new, optional) (y_hat, images): the reference's second value, copies of
+    the images with every box in green, labelled with the CLASSIFIER's argmax (predict_fns.py:80).  The classifier runs after the
+    last detection chunk, so drawing walks the chunks a second time (upload, draw, download) and holds one chunk's images at a
+    time; y_hat does not depend on it.  The crops are produced
     already centred ((v - 128) / 128, utils.center_rgb) in the classifier's NCHW layout and never leave the device.  No box over
     conf_th (new, optional; the reference's dark_pred default 0.5) is a valid outcome: the class part stays zero."""
     _restore(dark_model, dark_model_dir, dark_params, restore_file)
@@ -173,4 +202,15 @@ def dark_class_pred(images, dark_model, dark_model_dir, dark_params, class_model
     class_y_hat = torch.cat(scores, 0) if scores else torch.zeros((0, n_classes), dtype=torch.float32, device=dark_y_hat.device)
     image_hw = np.array([np.asarray(im).shape[0:2] for im in images])
     y_hat = utils.combine_y_hat_device(image_hw, dark_y_hat, class_y_hat, idx, xy, dark_params)
-    return y_hat.cpu().numpy().astype(np.float64), None
+    y_out = y_hat.cpu().numpy().astype(np.float64)
+    if not draw:
+        return y_out, None
+    classes = np.argmax(class_y_hat.cpu().numpy(), axis=1).astype(np.int64) if n else np.zeros(0, np.int64)   # class_pred's argmax
+    drawn = []
+    bs = _chunk_size(len(images), batch_size)
+    for lo in range(0, len(images), bs):
+        packed = PackedImages(images[lo:lo + bs], dark_params.device)
+        mine = (idx >= lo) & (idx < lo + packed.n)
+        buf = box_draw.draw_boxes_device(packed, idx[mine] - lo, xy[mine], box_draw.GREEN, classes[mine])
+        drawn.extend(box_draw.unpack_images(buf, packed))
+    return y_out, drawn

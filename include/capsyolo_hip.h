@@ -504,6 +504,29 @@ int cy_yolo_decode_boxes_conf(const float* y, const long long* image_hw, double 
 int cy_confusion_sweep(const int* gt_key, const double* gt_xy, const float* gt_conf, int n_gt, const int* pr_key,
                        const double* pr_xy, const float* pr_conf, int n_pr, int n_groups, int C, const double* conf_ths, int K,
                        const double* iou_ths, int T, int max_per_group, int* out, int* err, void* stream);
+/* ------------------------------------------------------------------ box drawing (csrc/draw.hip)
+ * plot.draw_boxes (plot.py:24-33) for n boxes in one launch, IN PLACE in a packed buffer of n_images HWC uint8 images described
+ * as for cy_crop_resize_u8 (imgs / img_off / img_hw / imgs_bytes); the caller draws into a copy if it still needs the images.
+ * Box b belongs to image box_img[b], has the integer corners box_xy[b] = (x1, y1, x2, y2), the 3 bytes box_color[b] in the
+ * image's channel order and the label box_label[b] (-1: none, else 0..999; box_label NULL: no box has one).  The result is
+ * what drawing the boxes one after the other in index order leaves behind:
+ *   outline  cv2.rectangle(img, (x1, y1), (x2, y2), color, 1) taken as: every pixel (x, y) of the image with y in {y1, y2} and
+ *            min(x1, x2) <= x <= max(x1, x2), or x in {x1, x2} and min(y1, y2) <= y <= max(y1, y2).  A box partly or wholly
+ *            outside the image is clipped (no error); a degenerate or inverted box draws what the rule says.
+ *   label    the decimal digits of the label (1-3, most significant first) in the 5 x 7 font glyphs[10][7] (device pointer; one
+ *            byte per glyph row, bit 4 = the leftmost column), one empty column between digits, in the box's colour, clipped
+ *            at the image border.  The bottom-left corner of the block is (xc, yc) = (floor((x1 + x2) / 2),
+ *            floor((y1 + y2) / 2)): rows yc-6 .. yc, digit k in columns xc + 6 k .. xc + 6 k + 4.  (The reference writes the
+ *            class NAME with cv2.putText at that origin; neither the names nor the font are available.)
+ *   order    where boxes of one image set the same pixel, the highest box index wins.  box_img must ascend (the boxes of an
+ *            image contiguous); every pixel is stored by one box only, so the result is bit-identical from run to run.
+ * max_items: threads per box, at least 2 * (columns + rows the box spans inside its image) + 119 for a labelled box;
+ * 2 * (max width + max height) + 119 always suffices.  *err (caller-zeroed) += the boxes with an image index outside
+ * 0..n_images-1, an image outside [0, imgs_bytes), a label outside -1..999, an image index below its predecessor's or more
+ * items than max_items; such a box draws nothing.  n = 0 is valid and launches nothing. */
+int cy_draw_boxes_u8(unsigned char* imgs, const long long* img_off, const int* img_hw, int n_images, long long imgs_bytes,
+                     const int* box_img, const int* box_xy, const unsigned char* box_color, const int* box_label, int n,
+                     int max_items, const unsigned char* glyphs, int* err, void* stream);
 /* ------------------------------------------------------------------ classifier report (csrc/rank.hip)
  * The integer rank counts behind metrics.recog_auc / recog_pr / recog_acc (metrics.py:9-96; sklearn's roc_curve + auc and
  * average_precision_score there), with no sort of the scores.  scores[N][C] fp32, labels[N] int64; element (i, c) is positive iff

@@ -16,7 +16,12 @@ keys, same registry shape ``name -> (ModelCls, loss_fn, predict_fn, metric)`` (m
 (predict_fns.dark_class_pred) and writes detect_and_recog_mAP / detect_and_recog_acc to combine-<name>_metric_output.txt
 (main.py:329-356); ``--mode predict --model cnn|capsule --restore last|best`` runs the classifier over the test set and writes
 recog_pr / recog_acc / recog_auc to metric_output.txt (main.py:309-317, 349-356), the curves counted on the device
-(metrics.recog_report).  Drawing the boxes and curves and the detect-only predict branch are not wired (see predict()).
+(metrics.recog_report).  ``--draw`` (new) makes the combined branch write its annotated images to <model_dir>/output/<i>.ppm.
+``--mode detect --model darknet_d|darknet_r --restore last|best [--synthetic N]`` is the reference's detect-only predict branch
+(main.py:319-327, 349-363: `--mode predict` without `--combine` there).  It is a mode of its own here because `--mode predict`
+without `--combine` has always exited with a message for the detectors, and callers rely on that.  It writes detect_AP /
+detect_acc to metric_output.txt and the images with the predictions in green and the ground truth in red, drawn on the device, to
+<model_dir>/output/<i>.ppm (see detect()).  The metric curves are not plotted.
 ``--mode interpret --model capsule --restore last|best [--synthetic N] [--index I]`` is the reference's capsule_interpret.py:
 the 16 x 11 perturbation sweep of sample I's labelled capsule through the fused decoder kernel, written to <model_dir>/img/
 (see interpret()).
@@ -44,11 +49,11 @@ from capsyolo_amd.loss_fns import (capsule_loss, cnn_loss, dark_loss, darkcapsul
                                    darkcapsule_loss)
 from capsyolo_amd.models import CapsuleNet, ConvNet, DarkCapsuleNet, DarkCapsuleNet2, DarkCapsuleNet3, DarkNet  # noqa: E402
 from capsyolo_amd.optim import Adam  # noqa: E402
-from capsyolo_amd.predict_fns import class_pred, class_scores_device, dark_class_pred, dark_forward  # noqa: E402
+from capsyolo_amd.predict_fns import class_pred, class_scores_device, dark_class_pred, dark_forward, dark_pred  # noqa: E402
 
 parser = argparse.ArgumentParser()
 parser.add_argument('--model', default='cnn', help=' | '.join(config.model_names))
-parser.add_argument('--mode', default='train', help='train | predict | overfit | interpret')
+parser.add_argument('--mode', default='train', help='train | predict | detect | overfit | interpret')
 parser.add_argument('--summary', default=True, help='if summarize model', action='store_true')
 parser.add_argument('--seed', type=int, default=0, help='random seed')
 parser.add_argument('--lr', type=float, default=1e-3, help='learning rate')
@@ -56,6 +61,8 @@ parser.add_argument('--dropout', type=float, default=-1, help='dropout rate')
 parser.add_argument('--train_frac', type=float, default=1, help='fraction of train data')
 parser.add_argument('--restore', default=None, help="last | best")
 parser.add_argument('--combine', default=None, help="cnn | capsule: the classifier behind --model darknet_d|darknet_r in predict mode")
+parser.add_argument('--draw', default=False, action='store_true',
+                    help='--mode predict --combine: also write the images with the boxes drawn to <model_dir>/output/<i>.ppm')
 parser.add_argument('--recon', help='if use reconstruction loss', action='store_false')
 parser.add_argument('--recon_coef', default=5e-4, help='reconstruction coefficient')
 parser.add_argument('--eval_every', default=1, type=int, help='evaluate metric every # epochs')
@@ -358,14 +365,16 @@ def predict(args, model, model_dir, data_dir, params):
     dark_class_pred and writes detect_and_recog_mAP / detect_and_recog_acc to <model_dir>/combine-<name>_metric_output.txt.
     The images are a list of raw HWC uint8 arrays: `--synthetic N` draws them (with labels) from synth, otherwise they come from
     data_dir/test_images.npy (an object array) next to data_dir/test.p.  The classifier's directory is config.model_dir[--combine]
-    or, with --model_dir, its sibling <model_dir>/../<name>.  Nothing is drawn and no cv2 is needed."""
+    or, with --model_dir, its sibling <model_dir>/../<name>.  With --draw the images with every box in green, labelled with the
+    classifier's class index, are written to <model_dir>/output/<i>.ppm (main.py:358-363); without it nothing is drawn.  No cv2
+    is needed.  The detect-only branch (no --combine) is `--mode detect`, see detect()."""
     if args.restore is None:
         raise SystemExit('Must give restore file last/best')                           # main.py:294-296
     if args.model in ('cnn', 'capsule'):
         return predict_class(args, model, model_dir, data_dir, params)
     if args.model not in ('darknet_d', 'darknet_r') or args.combine not in ('cnn', 'capsule'):
         raise SystemExit('predict mode runs --model cnn|capsule, or the combined chain --model darknet_d|darknet_r --combine '
-                         'cnn|capsule; the eval-mode forward of the detect-only branch is capsyolo_amd.predict_fns.dark_pred')
+                         'cnn|capsule; the detect-only branch of --model darknet_d|darknet_r is --mode detect')
     class_model_dir = config.model_dir[args.combine] if args.model_dir is None else \
         os.path.join(os.path.dirname(os.path.abspath(model_dir)), args.combine)
     class_args = argparse.Namespace(**dict(vars(args), model=args.combine))
@@ -379,13 +388,54 @@ def predict(args, model, model_dir, data_dir, params):
         with open(data_dir + config.te_d, 'rb') as f:
             _, y = pickle.load(f)
         x = list(np.load(data_dir + '/test_images.npy', allow_pickle=True))
-    y_hat, _ = dark_class_pred(x, model, model_dir, params, class_model, class_model_dir, class_params, args.restore,
-                               batch_size=params.batch_size)
+    y_hat, output = dark_class_pred(x, model, model_dir, params, class_model, class_model_dir, class_params, args.restore,
+                                    batch_size=params.batch_size, draw=args.draw)
     metric_out = {name: fn(y, y_hat, params) for name, fn in combine_metrics.items()}
     with open(os.path.join(model_dir, 'combine-{}_metric_output.txt'.format(args.combine)), 'w') as text_file:
         for k, v in metric_out.items():
             text_file.write("{}:{}, ".format(k, v))
             print("{}:{}, ".format(k, v))
+    if args.draw:
+        _write_output_images(model_dir, output)
+    return metric_out
+
+
+def _write_output_images(model_dir, images):
+    """main.py:358-363: <model_dir>/output/<i>.ppm (binary PPM where the reference writes a JPEG: no encoder is available)."""
+    save_dir = os.path.join(model_dir, 'output')
+    os.makedirs(save_dir, exist_ok=True)
+    for i, image in enumerate(images):
+        capsule_interpret.write_ppm(os.path.join(save_dir, str(i) + '.ppm'), image)
+
+
+def detect(args, model, model_dir, data_dir, params):
+    """main.py:319-327, 349-363, the detect-only branch: `--model darknet_d|darknet_r --restore last|best` pushes the raw test
+    images through the restored detector (predict_fns.dark_pred with the labels, so at its default confidence threshold 0.5) and
+    writes detect_AP / detect_acc to <model_dir>/metric_output.txt in the reference's format and key order, both from one
+    threshold sweep (metrics.detect_report), and the images with the predicted boxes in green and the ground truth in red to
+    <model_dir>/output/<i>.ppm.  The data are those of the combined branch: `--synthetic N` draws images and labels from synth,
+    otherwise data_dir/test_images.npy next to data_dir/test.p.  The precision-recall plots (detect_ap/) are not drawn."""
+    if args.model not in ('darknet_d', 'darknet_r'):
+        raise SystemExit('detect mode runs the detectors only: --model darknet_d|darknet_r')
+    if args.restore is None:
+        raise SystemExit('Must give restore file last/best')                           # main.py:294-296
+    if params.device != 'cuda':
+        raise SystemExit('detect mode runs on hand-written gfx950 kernels only; no GPU is visible')
+    if args.synthetic:
+        x = synth.raw_images(args.synthetic)
+        y = synth.gtsdb_labels(args.synthetic, params.n_grid, params.n_classes)
+    else:
+        import pickle
+        with open(data_dir + config.te_d, 'rb') as f:
+            _, y = pickle.load(f)
+        x = list(np.load(data_dir + '/test_images.npy', allow_pickle=True))
+    y_hat, output = dark_pred(x, model, model_dir, params, args.restore, y=y, batch_size=params.batch_size, draw=True)
+    metric_out = metrics.detect_report(y, y_hat, params)
+    with open(os.path.join(model_dir, 'metric_output.txt'), 'w') as text_file:
+        for k, v in metric_out.items():
+            text_file.write("{}:{}, ".format(k, v))
+            print("{}:{}, ".format(k, v))
+    _write_output_images(model_dir, output)
     return metric_out
 
 
@@ -474,6 +524,8 @@ def main(argv=None):
         return train_and_evaluate(model, optimizer, loss_fn, metric, params, data, model_dir, restore_file=args.restore)
     if args.mode == 'predict':
         return predict(args, model, model_dir, data_dir, params)
+    if args.mode == 'detect':
+        return detect(args, model, model_dir, data_dir, params)
     if args.mode == 'interpret':
         return interpret(args, model, model_dir, data_dir, params)
 
