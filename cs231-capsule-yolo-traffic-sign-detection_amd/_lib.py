@@ -132,6 +132,7 @@ _SIGS = {
     'cy_yolo_decode_boxes_conf': [_P, _P, C.c_double, C.c_double, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P],
     'cy_confusion_sweep': [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P],
     'cy_draw_boxes_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _I, _P, _P, _P],
+    'cy_paste_resize_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _I, _L, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P],
     'cy_rank_counts': [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
     'cy_pick_capsule': [_P, _P, _P, _I, _I, _I, _I, _P],
     'cy_decoder_fwd': [C.POINTER(Decoder), _P],
@@ -182,6 +183,7 @@ _RET = {
     'cy_routing_general_fwd_ws_floats': (_L, [C.POINTER(RoutingFwd)]),
     'cy_routing_specialised': (_I, [C.POINTER(RoutingFwd)]),
     'cy_rank_ws_ints': (_L, [_I, _I]),
+    'cy_paste_resize_max_pastes': (_I, []),
     'cy_conv_gemm_bf16_plan': (_I, [C.POINTER(ConvGemm), _I, _I, C.POINTER(C.c_int)]),
     'cy_routing_plan': (_I, [C.POINTER(RoutingFwd), _I, _I, C.POINTER(_L), _I]),
 }

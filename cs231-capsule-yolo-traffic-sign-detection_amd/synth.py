@@ -44,3 +44,34 @@ def raw_images(n, seed=1234, first=0, min_side=48, max_side=160):
         ramp = np.add.outer(np.linspace(0, 96, h), np.linspace(0, 96, w))[:, :, None]
         out.append(np.clip(ramp + rng.integers(0, 64, (h, w, 3)), 0, 255).astype(np.uint8))
     return out
+
+
+def raw_boxes(images, n_classes=43, seed=1234, first=0):
+    """Per image a float64 [k, 5] array (x1, y1, x2, y2, class), k = 1..3, the shape of the gt.txt rows of a GTSDB frame: boxes of
+    8 .. a third of the shorter side, wholly inside the image, with fractional corners (so the truncation of the paste plan is
+    exercised).  The boxes of image i depend only on (seed, first + i) and the image's size."""
+    out = []
+    for i, im in enumerate(images):
+        h, w = np.asarray(im).shape[0:2]
+        rng = np.random.default_rng([seed, 15, first + i])
+        rows = []
+        for _ in range(int(rng.integers(1, 4))):
+            bw, bh = (int(v) for v in rng.integers(8, max(min(h, w) // 3, 9) + 1, 2))
+            x1, y1 = float(rng.uniform(0, w - bw - 1)), float(rng.uniform(0, h - bh - 1))
+            rows.append([x1, y1, x1 + bw, y1 + bh, float(rng.integers(0, max(n_classes, 1)))])
+        out.append(np.array(rows, dtype=np.float64))
+    return out
+
+
+def sign_bank(n, n_classes=43, seed=1234):
+    """(images, rois, classes) of n GTSRB-shaped signs: uint8 images of 12 .. 32 pixels per side, the ROI (y0, y1, x0, x1) 1 .. 3
+    pixels inside the border like the csv's Roi columns, a class each.  Sign i depends only on (seed, i)."""
+    images, rois, classes = [], [], []
+    for i in range(n):
+        rng = np.random.default_rng([seed, 16, i])
+        h, w = (int(v) for v in rng.integers(12, 33, 2))
+        m = [int(v) for v in rng.integers(1, 4, 4)]
+        images.append(rng.integers(0, 256, (h, w, 3), dtype=np.uint8))
+        rois.append([m[0], h - m[1], m[2], w - m[3]])
+        classes.append(int(rng.integers(0, max(n_classes, 1))))
+    return images, np.array(rois, dtype=np.int64), np.array(classes, dtype=np.int64)

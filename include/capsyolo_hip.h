@@ -527,6 +527,34 @@ int cy_confusion_sweep(const int* gt_key, const double* gt_xy, const float* gt_c
 int cy_draw_boxes_u8(unsigned char* imgs, const long long* img_off, const int* img_hw, int n_images, long long imgs_bytes,
                      const int* box_img, const int* box_xy, const unsigned char* box_color, const int* box_label, int n,
                      int max_items, const unsigned char* glyphs, int* err, void* stream);
+/* ------------------------------------------------------------------ sign-paste augmentation and data-set resize (csrc/augment.hip)
+ * build_data.py:80 (a frame resized), 28-29 + 44 (a sign's ROI resized) and 171-288 (signs pasted over a frame, then the frame
+ * resized) for n output samples in one launch.  imgs / img_off / img_hw / n_images / imgs_bytes: the background images, and
+ * signs / sign_off / sign_hw / n_signs / signs_bytes: the sign images, both packed as for the crop-and-resize entry point above.
+ * Sample s reads image sample_img[s], its half-open source rectangle sample_rect[s] = (y0, y1, x0, x1) and the rows
+ * begin[s] .. begin[s + 1] - 1 of the paste table (begin has n + 1 entries).  A paste row is 9 ints: (sign, sy0, sy1, sx0, sx1,
+ * dy0, dy1, dx0, dx1) = the sign image, its source rectangle, and the destination rectangle in FULL-IMAGE coordinates of the
+ * background (both half-open).  Output s is the source rectangle of the composited image resized to OH x OW, the composited image
+ * being the background with the sample's pastes applied in table order (a later paste overwrites an earlier one), each paste the
+ * sign's source rectangle resized to the destination's size as a stand-alone image.  The composited image is never stored.
+ * Both resizes use the half-pixel rule of INTER_LINEAR in exact integers and each yields a BYTE: for output index o of n_out from
+ * n_in, num = (2 o + 1) n_in - n_out, r = floor(num / (2 n_out)), a = num - r 2 n_out, taps r and r + 1 clamped into the
+ * rectangle (b for the columns), value = ((2 OW - b)(2 OH - a) aa + b (2 OH - a) ab + (2 OW - b) a ba + b a bb + 2 OW OH) /
+ * (4 OW OH) rounded down, i.e. round-half-up of the exact bilinear value; equal sizes give the identity.  cv2's 11-bit
+ * fixed-point weights are not reproduced.  mode: CY_PASTE_OUT_U8 bytes [n][OH][OW][3]; CY_PASTE_OUT_F32_NHWC and
+ * CY_PASTE_OUT_F32_NCHW ([n][3][OH][OW]) hold (byte - 128) / 128 as fp32.  *err (caller-zeroed) += the samples with an image or
+ * sign index out of range, an image outside its buffer, a side of 2^24 or more, an empty source rectangle or one that reaches
+ * outside its image, an empty destination or one that reaches outside the background, a begin[] that decreases or runs past
+ * n_pastes, or more pastes than the query below returns (64); such a sample is zero-filled, the others are untouched.
+ * n = 0 is valid and launches nothing; at most 65535 samples per launch; the sign set and the table may be NULL when n_pastes = 0. */
+#define CY_PASTE_OUT_U8 0
+#define CY_PASTE_OUT_F32_NHWC 1
+#define CY_PASTE_OUT_F32_NCHW 2
+int cy_paste_resize_max_pastes(void);
+int cy_paste_resize_u8(const unsigned char* imgs, const long long* img_off, const int* img_hw, int n_images, long long imgs_bytes,
+                       const unsigned char* signs, const long long* sign_off, const int* sign_hw, int n_signs, long long signs_bytes,
+                       const int* sample_img, const int* sample_rect, const int* begin, int n, const int* pastes, int n_pastes,
+                       int OH, int OW, int mode, void* out, int* err, void* stream);
 /* ------------------------------------------------------------------ classifier report (csrc/rank.hip)
  * The integer rank counts behind metrics.recog_auc / recog_pr / recog_acc (metrics.py:9-96; sklearn's roc_curve + auc and
  * average_precision_score there), with no sort of the scores.  scores[N][C] fp32, labels[N] int64; element (i, c) is positive iff

@@ -25,6 +25,10 @@ detect_acc to metric_output.txt and the images with the predictions in green and
 ``--mode interpret --model capsule --restore last|best [--synthetic N] [--index I]`` is the reference's capsule_interpret.py:
 the 16 x 11 perturbation sweep of sample I's labelled capsule through the fused decoder kernel, written to <model_dir>/img/
 (see interpret()).
+``--mode train --model darknet_d|darknet_r|darkcapsule* --augment [--gtsrb DIR] [--synthetic N]`` (new) trains on the reference's
+sign-paste augmentation (build_data.py:171-288) made fresh for every batch on the device instead of frozen as ``--aug N`` copies:
+the raw frames of <data_dir>/train_raw.p (``build_data.py --keep_raw``) stay on the device, ``add_signs`` comes from params.json
+(default 0), the eval set is not augmented (see augmented_data()).
 Data-parallel: launch with ``python -m torch.distributed.run --nproc-per-node N main.py ...``; every rank takes
 its equal shard of each global batch, gradients are averaged with one RCCL all-reduce per step, epoch losses are
 averaged over the ranks before the LR scheduler sees them, metrics run on the gathered predictions, rank 0 writes.
@@ -42,7 +46,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 import capsyolo_amd  # noqa: E402,F401
-from capsyolo_amd import config, dp, metrics, synth, utils  # noqa: E402
+from capsyolo_amd import augment, config, dp, metrics, synth, utils  # noqa: E402
 from capsyolo_amd import interpret as capsule_interpret  # noqa: E402
 from capsyolo_amd.input_pipeline import DeviceFeeder, quantize_if_exact  # noqa: E402
 from capsyolo_amd.loss_fns import (capsule_loss, cnn_loss, dark_loss, darkcapsule2_loss, darkcapsule3_loss,  # noqa: E402
@@ -78,6 +82,9 @@ parser.add_argument('--batch_size', type=int, default=0, help='override params.j
 parser.add_argument('--graph', action='store_true',
                     help='capture the training step (forward + loss + backward + Adam) once in a HIP graph and replay it per batch: '
                          'for the launch-bound small models (capsule); single process only')
+parser.add_argument('--augment', action='store_true',
+                    help='--mode train of a detector: paste GTSRB signs over the raw frames on the device, fresh for every batch')
+parser.add_argument('--gtsrb', default=config.GTSRB, help='--augment: the GTSRB root whose Images/ are the signs to paste')
 parser.add_argument('--fix_ckpt_dir', action='store_true',
                     help='save checkpoints into model_dir (where --restore reads) instead of model_dir + str(train_frac)')
 
@@ -120,11 +127,14 @@ def _shard(x_bch, y_bch, params):
     return x_bch, y_bch
 
 
-def _feed(it, params):
+def _feed(it, params, source=None):
     """main.py:57-59 (H2D + float + NHWC->NCHW) through the buffered device-side pipeline; batches smaller than
-    the number of ranks are dropped on every rank alike."""
+    the number of ranks are dropped on every rank alike.  source (--augment, training only): the batches are frame numbers, and
+    the samples are made on the device by its feeder."""
     shards = [_shard(x_np, y_np, params) for x_np, y_np in it]
     shards = [(x_np, y_np) for x_np, y_np in shards if len(y_np) > 0]
+    if source is not None:
+        return source.feeder([x_np for x_np, _ in shards])
     if params.device == 'cpu':          # only the plain-torch `cnn` baseline gets here (main() refuses the others)
         return _host_batches(shards)
     return DeviceFeeder(shards, params.device)
@@ -196,7 +206,7 @@ def train(x, y, model, optimizer, loss_fn, metric, params, bucket, if_eval=True)
     avg_loss, avg_iou, y_hat, y_true = 0.0, 0.0, [], []
     want_metric = if_eval and metric is not None
     graphed = getattr(params, 'graph', False) and params.world == 1 and params.device != 'cpu'
-    for x_bch, y_bch in _feed(it, params):
+    for x_bch, y_bch in _feed(it, params, getattr(params, 'augment_source', None)):
         if graphed:
             # the whole step as one graph replay (capsyolo_amd/graph_step.py); captured on the first batch of this shape
             key = (id(model), id(optimizer), tuple(x_bch.shape), tuple(y_bch.shape))
@@ -331,6 +341,44 @@ def synthetic_data(args, params):
     x_tr, y_tr = mk(n, 0)
     x_ev, y_ev = mk(n_ev, n)
     return x_tr, y_tr, x_ev, y_ev
+
+
+def augmented_data(args, params, data_dir):
+    """--augment: (frame numbers, frame numbers, x_ev, y_ev) in place of (x_tr, y_tr, x_ev, y_ev), and params.augment_source, which
+    turns a batch of frame numbers into device tensors (augment.AugmentSource).  The raw frames and their boxes come from
+    data_dir/train_raw.p and the signs from --gtsrb, or with --synthetic N from synth.raw_images / raw_boxes / sign_bank.  The eval
+    set is not augmented: data_dir/eval.p, or the synthetic eval frames resized with no pastes."""
+    if args.model not in ('darknet_d', 'darknet_r', 'darkcapsule', 'darkcapsule2', 'darkcapsule3') or args.mode != 'train':
+        raise SystemExit('--augment pastes signs over detector frames: --mode train --model darknet_d|darknet_r|darkcapsule*')
+    if args.graph:
+        raise SystemExit('--augment --graph: the augmented batches are planned on the host per step; run without --graph')
+    if params.device != 'cuda':
+        raise SystemExit('--augment runs on hand-written gfx950 kernels only; no GPU is visible')
+    side, g, C = int(params.darknet_input), int(params.n_grid), int(params.n_classes)
+    if args.synthetic:
+        n = args.synthetic
+        n_ev = max(params.batch_size, n // 4)
+        frames = synth.raw_images(n + n_ev)
+        boxes = synth.raw_boxes(frames, C)
+        bank = augment.SignBank(*synth.sign_bank(16, C))
+        from capsyolo_amd.predict_fns import PackedImages
+        ev = PackedImages(frames[n:], params.device)
+        x_ev = augment.paste_resize_device(ev, None, np.arange(ev.n), augment.full_rects(ev.hw), None, None, side, side,
+                                           'u8').cpu().numpy()
+        y_ev = np.stack([augment.label_grid(b[:, 0:4], b[:, 4], hw, side, g, C, True) for b, hw in zip(boxes[n:], ev.hw)])
+        frames, boxes = frames[:n], boxes[:n]
+    else:
+        import pickle
+        from capsyolo_amd import build_data
+        with open(data_dir + '/train_raw.p', 'rb') as f:
+            frames, boxes = pickle.load(f)
+        with open(data_dir + config.ev_d, 'rb') as f:
+            x_ev, y_ev = pickle.load(f)
+        bank = build_data.load_bank(args.gtsrb)
+    params.augment_source = augment.AugmentSource(frames, boxes, bank, side, g, C, int(getattr(params, 'add_signs', 0)),
+                                                  args.seed, params.device)
+    idx = np.arange(len(frames))
+    return idx, idx.copy(), x_ev, y_ev
 
 
 def predict_class(args, model, model_dir, data_dir, params):
@@ -515,13 +563,17 @@ def main(argv=None):
     optimizer = torch.optim.Adam(trainable, lr=args.lr) if args.model == 'cnn' else Adam(trainable, lr=args.lr)
 
     if args.mode in ('train', 'overfit'):
-        if args.synthetic:
+        if args.augment:
+            data = augmented_data(args, params, data_dir)
+        elif args.synthetic:
             data = synthetic_data(args, params)
         else:
             if args.mode == 'overfit':
                 raise SystemExit('--mode overfit needs the real dataset under %s (or use --synthetic 3)' % data_dir)
             data = utils.load_data(data_dir, False, npy=args.npy)
         return train_and_evaluate(model, optimizer, loss_fn, metric, params, data, model_dir, restore_file=args.restore)
+    if args.augment:
+        raise SystemExit('--augment belongs to --mode train')
     if args.mode == 'predict':
         return predict(args, model, model_dir, data_dir, params)
     if args.mode == 'detect':
