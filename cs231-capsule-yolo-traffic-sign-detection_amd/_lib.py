@@ -133,6 +133,7 @@ _SIGS = {
     'cy_confusion_sweep': [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P],
     'cy_draw_boxes_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _I, _P, _P, _P],
     'cy_paste_resize_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _I, _L, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P],
+    'cy_gather_jitter_u8': [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P],
     'cy_rank_counts': [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
     'cy_pick_capsule': [_P, _P, _P, _I, _I, _I, _I, _P],
     'cy_decoder_fwd': [C.POINTER(Decoder), _P],

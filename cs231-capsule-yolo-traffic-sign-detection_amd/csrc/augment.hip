@@ -2,6 +2,8 @@
 // (ROI crop of a GTSRB sign, resized) and 171-288 (gtsdb_aug_: signs pasted over a frame, then the frame resized) as ONE kernel
 // that never forms the composited frame.  DESIGN section 6h.
 //   paste_resize_u8_kernel   output sample = resize(source rectangle of (background with the sample's pastes applied in order))
+// The classifiers' augmentation (utils.py:126-143: shift with zero fill, lightness increase) as one gather kernel.  DESIGN section 6i.
+//   gather_jitter_u8_kernel  output sample = centre(brighten(shift(resident image index[b]))), NHWC bytes -> NCHW floats
 #include "common.h"
 
 namespace {
@@ -137,6 +139,40 @@ __global__ __launch_bounds__(256) void paste_resize_u8_kernel(
   }
 }
 
+// Grid (pixel tiles, batch): the sample number, its shift and its lightness are uniform per block (scalar loads), a thread owns one
+// output pixel: three byte loads of its source pixel, three stores that are contiguous across the wave in each colour plane.
+// A sample number outside the set reads nothing: zeros, label -1, one count in *err (by the first thread of its first tile).
+__global__ __launch_bounds__(256) void gather_jitter_u8_kernel(
+    const unsigned char* __restrict__ set, const long long* __restrict__ labels, int n_set, int H, int W,
+    const int* __restrict__ shift, const float* __restrict__ light, const int* __restrict__ index, float* __restrict__ x_out,
+    long long* __restrict__ y_out, int* err) {
+  const int t = threadIdx.x, b = blockIdx.y, s = index[b];
+  const bool ok = s >= 0 && s < n_set;
+  if (blockIdx.x == 0 && t == 0) {
+    y_out[b] = ok ? labels[s] : -1ll;
+    if (!ok) atomicAdd(err, 1);
+  }
+  const int plane = H * W, i = (int)blockIdx.x * 256 + t;
+  if (i >= plane) return;
+  float f[3] = {0.f, 0.f, 0.f};                                      // off the image: grey on the centred scale, not brightened
+  if (ok) {
+    const int y = i / W, x = i - y * W;
+    const long long sy = (long long)y - (shift ? shift[2 * s] : 0), sx = (long long)x - (shift ? shift[2 * s + 1] : 0);
+    if (sy >= 0 && sy < H && sx >= 0 && sx < W) {
+      const unsigned char* q = set + ((long long)s * plane + sy * W + sx) * 3;
+      float k[3] = {(float)q[0], (float)q[1], (float)q[2]};
+      // hsv_to_rgb(rgb_to_hsv(k / 256) + (0, 0, d)): V = max(k) grows by d, hue and saturation stay, so every channel is scaled by
+      // (v + 256 d) / v; a black pixel has saturation 0 and becomes the grey 256 d.  d = 0: the gain is exactly 1.
+      const float add = light ? 256.f * light[s] : 0.f, v = fmaxf(k[0], fmaxf(k[1], k[2]));
+      const float g = (v + add) / v;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) f[c] = ((v > 0.f ? k[c] * g : add) - 128.f) * 0.0078125f;
+    }
+  }
+  float* o = x_out + (long long)b * 3 * plane + i;
+  o[0] = f[0]; o[plane] = f[1]; o[2 * (long long)plane] = f[2];
+}
+
 }  // namespace
 
 extern "C" int cy_paste_resize_max_pastes(void) { return MAX_PASTES; }
@@ -160,5 +196,21 @@ extern "C" int cy_paste_resize_u8(const unsigned char* imgs, const long long* im
       imgs, img_off, img_hw, n_images, imgs_bytes, signs, sign_off, sign_hw, n_pastes ? n_signs : 0, signs_bytes, sample_img,
       sample_rect, begin, pastes, n_pastes, OH, OW, mode, out, err);
   CY_LAUNCH_CHECK("cy_paste_resize_u8");
+  return 0;
+}
+
+extern "C" int cy_gather_jitter_u8(const unsigned char* set, const long long* labels, int n_set, int H, int W, const int* shift,
+                                   const float* light, const int* index, int B, float* x_out, long long* y_out, int* err,
+                                   void* stream) {
+  CY_REQUIRE(B >= 0, "cy_gather_jitter_u8: B = %d samples", B);
+  if (B == 0) return 0;
+  CY_REQUIRE(set && labels && index && x_out && y_out && err, "cy_gather_jitter_u8: null argument");
+  CY_REQUIRE(n_set > 0 && H > 0 && W > 0, "cy_gather_jitter_u8: a set of %d images of %d x %d", n_set, H, W);
+  CY_REQUIRE((long long)H * W <= (1ll << 30), "cy_gather_jitter_u8: %d x %d pixels are too many for one image", H, W);
+  CY_REQUIRE(B <= 65535, "cy_gather_jitter_u8: %d samples are too many for one launch (65535)", B);
+  const long long tiles = cy_ceil_div((long long)H * W, 256);
+  gather_jitter_u8_kernel<<<dim3((unsigned)tiles, (unsigned)B), 256, 0, (hipStream_t)stream>>>(set, labels, n_set, H, W, shift, light,
+                                                                                                  index, x_out, y_out, err);
+  CY_LAUNCH_CHECK("cy_gather_jitter_u8");
   return 0;
 }

@@ -555,6 +555,18 @@ int cy_paste_resize_u8(const unsigned char* imgs, const long long* img_off, cons
                        const unsigned char* signs, const long long* sign_off, const int* sign_hw, int n_signs, long long signs_bytes,
                        const int* sample_img, const int* sample_rect, const int* begin, int n, const int* pastes, int n_pastes,
                        int OH, int OW, int mode, void* out, int* err, void* stream);
+/* ------------------------------------------------------------------ classifier augmentation (csrc/augment.hip)
+ * utils.augmentation (utils.py:126-143) as it is evidently meant, per sample, fused with the gather of a batch from a resident
+ * data set, the centring and the NHWC -> NCHW permute.  set [n_set][H][W][3] bytes, labels [n_set]; index [B] sample numbers.
+ * shift [n_set][2] = (dy, dx) and light [n_set] = the lightness increase d on the 0..1 V scale are indexed by SAMPLE NUMBER;
+ * either may be NULL (no shift / d = 0).  Output pixel (b, y, x) with s = index[b] reads pixel (y - dy, x - dx) of image s; off
+ * the image all three channels are exactly 0.0f (grey on the centred scale, not brightened); any int shift is legal.  With the
+ * source bytes k as floats and v = max(k): k' = k (v + 256 d) / v for v > 0 and k' = 256 d on all channels for v = 0, which is
+ * hsv_to_rgb(rgb_to_hsv(k / 256) + (0, 0, d)); x_out [B][3][H][W] = (k' - 128) / 128, not clipped.  d = 0 gives exactly what
+ * cy_center_u8 gives.  y_out [B] = labels[s].  A sample number outside 0..n_set-1 is never dereferenced: its output is zeros,
+ * its y_out -1, and *err (caller-zeroed) += 1.  B = 0 is valid and launches nothing; at most 65535 samples per launch. */
+int cy_gather_jitter_u8(const unsigned char* set, const long long* labels, int n_set, int H, int W, const int* shift,
+                        const float* light, const int* index, int B, float* x_out, long long* y_out, int* err, void* stream);
 /* ------------------------------------------------------------------ classifier report (csrc/rank.hip)
  * The integer rank counts behind metrics.recog_auc / recog_pr / recog_acc (metrics.py:9-96; sklearn's roc_curve + auc and
  * average_precision_score there), with no sort of the scores.  scores[N][C] fp32, labels[N] int64; element (i, c) is positive iff

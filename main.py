@@ -29,6 +29,11 @@ the 16 x 11 perturbation sweep of sample I's labelled capsule through the fused 
 sign-paste augmentation (build_data.py:171-288) made fresh for every batch on the device instead of frozen as ``--aug N`` copies:
 the raw frames of <data_dir>/train_raw.p (``build_data.py --keep_raw``) stay on the device, ``add_signs`` comes from params.json
 (default 0), the eval set is not augmented (see augmented_data()).
+``--mode train|overfit --model cnn|capsule --class_augment [--synthetic N] [--graph]`` (new) trains the classifiers on the reference's
+shift-and-lightness augmentation (utils.py:126-143, `utils.augmentation`, dead code there) drawn fresh per sample and per epoch: the
+training set stays on the device as bytes and every batch is one gather kernel (capsyolo_amd.class_augment).  Optional params.json
+keys ``aug_max_shift`` (pixels, default 4) and ``aug_max_light`` (on the 0..1 V scale, default 0.05); both 0 give the resident feed
+without jitter.  The eval set is not augmented (see class_augmented_data()).  ``--augment`` stays the detectors' flag.
 Data-parallel: launch with ``python -m torch.distributed.run --nproc-per-node N main.py ...``; every rank takes
 its equal shard of each global batch, gradients are averaged with one RCCL all-reduce per step, epoch losses are
 averaged over the ranks before the LR scheduler sees them, metrics run on the gathered predictions, rank 0 writes.
@@ -46,7 +51,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 import capsyolo_amd  # noqa: E402,F401
-from capsyolo_amd import augment, config, dp, metrics, synth, utils  # noqa: E402
+from capsyolo_amd import augment, class_augment, config, dp, metrics, synth, utils  # noqa: E402
 from capsyolo_amd import interpret as capsule_interpret  # noqa: E402
 from capsyolo_amd.input_pipeline import DeviceFeeder, quantize_if_exact  # noqa: E402
 from capsyolo_amd.loss_fns import (capsule_loss, cnn_loss, dark_loss, darkcapsule2_loss, darkcapsule3_loss,  # noqa: E402
@@ -84,6 +89,9 @@ parser.add_argument('--graph', action='store_true',
                          'for the launch-bound small models (capsule); single process only')
 parser.add_argument('--augment', action='store_true',
                     help='--mode train of a detector: paste GTSRB signs over the raw frames on the device, fresh for every batch')
+parser.add_argument('--class_augment', action='store_true',
+                    help='--mode train|overfit of a classifier (cnn | capsule): shift and lightness jitter per sample and epoch, '
+                         'made on the device from the resident training set')
 parser.add_argument('--gtsrb', default=config.GTSRB, help='--augment: the GTSRB root whose Images/ are the signs to paste')
 parser.add_argument('--fix_ckpt_dir', action='store_true',
                     help='save checkpoints into model_dir (where --restore reads) instead of model_dir + str(train_frac)')
@@ -381,6 +389,36 @@ def augmented_data(args, params, data_dir):
     return idx, idx.copy(), x_ev, y_ev
 
 
+def check_class_augment(args):
+    """The refusals of --class_augment that need neither the data nor a device."""
+    if args.augment:
+        raise SystemExit('--class_augment jitters the classifiers\' samples and --augment pastes signs over detector frames: give one')
+    if args.model not in ('cnn', 'capsule') or args.mode not in ('train', 'overfit'):
+        raise SystemExit('--class_augment shifts and brightens classifier samples: --mode train|overfit --model cnn|capsule')
+
+
+def class_augmented_data(args, params, data_dir):
+    """--class_augment: (sample numbers, sample numbers, x_ev, y_ev) in place of (x_tr, y_tr, x_ev, y_ev), and params.augment_source,
+    which turns a batch of sample numbers into jittered device tensors (class_augment.ClassAugmentSource).  The training set is the
+    one a plain run would read (data_dir, or --synthetic N) and must be byte-exact (input_pipeline.quantize_if_exact).  train_frac
+    keeps the leading sample numbers, as it keeps the leading samples of a plain run."""
+    if params.device != 'cuda':
+        raise SystemExit('--class_augment runs on hand-written gfx950 kernels only; no GPU is visible')
+    if args.synthetic:
+        x_tr, y_tr, x_ev, y_ev = synthetic_data(args, params)
+    else:
+        if args.mode == 'overfit':
+            raise SystemExit('--mode overfit needs the real dataset under %s (or use --synthetic 3)' % data_dir)
+        x_tr, y_tr, x_ev, y_ev = utils.load_data(data_dir, False, npy=args.npy)
+    x_u8 = quantize_if_exact(x_tr)
+    if x_u8 is None:
+        raise SystemExit('--class_augment keeps the training set on the device as bytes, and this one is not (uint8 - 128) / 128')
+    params.augment_source = class_augment.ClassAugmentSource(x_u8, y_tr, args.seed, int(getattr(params, 'aug_max_shift', 4)),
+                                                             float(getattr(params, 'aug_max_light', 0.05)), params.device)
+    idx = np.arange(len(y_tr))
+    return idx, idx.copy(), x_ev, y_ev
+
+
 def predict_class(args, model, model_dir, data_dir, params):
     """main.py:303-317, 349-356, the class-only branch: `--model cnn|capsule --restore last|best` pushes the test set (`--synthetic
     N`: N synthetic GTSRB-shaped samples, otherwise the pickled (x, y) at data_dir/test.p) through the restored classifier and
@@ -529,6 +567,8 @@ def main(argv=None):
     if args.model not in config.model_names:
         print("Did not recognize model, choose from: ", *config.model_names)
         sys.exit()
+    if args.class_augment:
+        check_class_augment(args)
     data_dir, model_dir = config.data_dir[args.model], config.model_dir[args.model]
     if args.model_dir is not None:
         model_dir = args.model_dir
@@ -565,6 +605,8 @@ def main(argv=None):
     if args.mode in ('train', 'overfit'):
         if args.augment:
             data = augmented_data(args, params, data_dir)
+        elif args.class_augment:
+            data = class_augmented_data(args, params, data_dir)
         elif args.synthetic:
             data = synthetic_data(args, params)
         else:
