@@ -66,6 +66,8 @@ _SIGS = {
     'cy_conv1_3x3_stats': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     'cy_conv1_bn_bwd_onepass': [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     'cy_conv1_bn_bwd_onepass_bf16': [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    'cy_conv1_3x3_fwd_act_mask': [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _P],
+    'cy_conv1_bn_bwd_onepass_mask': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     'cy_conv1_3x3_wgrad': [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     'cy_conv1_bn_bwd_reduce': [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _P],
     'cy_conv1_bn_bwd_reduce_bf16': [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _P],
@@ -168,6 +170,7 @@ _RET = {
     'cy_conv1_3x3_stats_ws_floats': (_L, [_I, _I]),
     'cy_conv1_3x3_stats_m2_offset': (_L, [_I, _I]),
     'cy_conv1_bn_bwd_wgrad_ws_floats': (_L, [_I, _I, _I, _I]),
+    'cy_conv1_signmask_bytes': (_L, [_I, _I, _I, _I]),
     'cy_wino2_packed_floats': (_L, [_I, _I]),
     'cy_wino4s2_packed_floats': (_L, [_I, _I]),
     'cy_wino4s2_ok': (_I, [_I, _I, _I, _I, _I]),

@@ -33,11 +33,27 @@ struct Conv1Args {
   const float* scale; const float* shift; float slope;   // forward only, optional: Y = lrelu((conv + bias) * scale + shift)
   int B, H, Wd, Cout;
   long long ntiles;                         // B * H * Wd / 32
+  void* mask;                               // MASK only: the sign words of the activation pass, [ntiles][64 lanes]
 };
 
+// ---- the sign mask of the first block.  The activation pass has z of every element in registers; the one-pass backward needs of it
+// only lrelu'(y), one bit.  The bit is y > 0 of y = fma(acc + bias, scale, shift), the form in which the backward's recompute passes
+// build y -- NOT the sign of the epilogue's own y = fma(acc, scale, bias * scale + shift), which can fall on the other side of zero
+// within rounding: the backward with the mask has to see what the backward without it sees, element for element.  A lane's 16 NT accumulator elements of a tile, taken in the order e = NT r + nt of
+// the epilogue loops, are shifted into words of n = min(32, 16 NT) bits from the right: element e is bit n - 1 - e % n of word e / n,
+// and the backward shifts them out at the left in the same order.  Per tile and lane: 2 words for Cout = 128, 1 for 64, a 16-bit word
+// for 32 (B H W Cout / 8 bytes in all), stored at mask[tile][lane] by the GLOBAL tile number, so forward and backward need not give
+// the same tiles to the same waves.
+template <int NT> struct Conv1MaskWord;
+template <> struct Conv1MaskWord<4> { typedef unsigned type __attribute__((ext_vector_type(2))); };
+template <> struct Conv1MaskWord<2> { typedef unsigned type; };
+template <> struct Conv1MaskWord<1> { typedef unsigned short type; };
+
 // OBF: the activation is written as bf16 (the bf16 path's second block reads it as such: no fp32 copy, no cast pass)
-template <int NT, bool AFF, bool STORE, bool OBF = false>
+// MASK: the activation pass also stores the sign words (fp32 output only)
+template <int NT, bool AFF, bool STORE, bool OBF = false, bool MASK = false>
 __global__ __launch_bounds__(256, 1) void conv1_fwd_kernel(Conv1Args a) {
+  static_assert(!MASK || (AFF && STORE && !OBF), "the sign mask belongs to the fp32 activation pass");
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const long long gw = (long long)blockIdx.x * 4 + wave, nw = (long long)gridDim.x * 4;
@@ -70,9 +86,11 @@ __global__ __launch_bounds__(256, 1) void conv1_fwd_kernel(Conv1Args a) {
   // store-bound and its input tiny, so recomputing the convolution is cheaper than reading z back): folded into bias
   constexpr bool aff = AFF;                 // compile time: a uniform branch per element would cost more than the layer
   float asc[NT];
+  float mb[NT], msh[NT];                    // MASK: bias and shift unfolded, as conv1_bn_bwd_kernel has them
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     asc[nt] = aff ? a.scale[NT * li + nt] : 1.f;
+    if constexpr (MASK) { mb[nt] = bv[nt]; msh[nt] = a.shift[NT * li + nt]; }
     if (aff) bv[nt] = bv[nt] * asc[nt] + a.shift[NT * li + nt];
   }
 
@@ -114,6 +132,7 @@ __global__ __launch_bounds__(256, 1) void conv1_fwd_kernel(Conv1Args a) {
     // ---- epilogue: + bias, statistics; MFMA tile nt holds the channels NT * column + nt, so a lane owns NT
     // consecutive channels of each of its 16 pixels: one 4 NT-byte store per pixel, a pixel's Cout channels are contiguous
     float* yp = a.Y + (size_t)tile * 32 * a.Cout + NT * li;
+    unsigned mw[2] = {0u, 0u};                // MASK: the lane's sign words of this tile
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       typedef float vecn __attribute__((ext_vector_type(NT)));
@@ -125,6 +144,13 @@ __global__ __launch_bounds__(256, 1) void conv1_fwd_kernel(Conv1Args a) {
           const float y = __builtin_fmaf(acc[nt][r], asc[nt], bv[nt]);
           const float ys = y * a.slope;                         // slope in [0, 1]: lrelu(y) = max(y, slope y)
           asm("v_max_f32 %0, %1, %2" : "=v"(v[nt]) : "v"(y), "v"(ys));   // fmaxf() would canonicalise both operands first
+          if constexpr (MASK) {
+            // the backward's y (conv1_bn_bwd_kernel: z = acc + bias, y = fma(z, scale, shift)), then word = 2 word + (0 < y): the
+            // compare leaves the bit in vcc, the add takes it as its carry (a select and a shift-or would be one instruction more)
+            const float yb = __builtin_fmaf(acc[nt][r] + mb[nt], asc[nt], msh[nt]);
+            asm("v_cmp_lt_f32_e32 vcc, 0, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc"
+                : "+v"(mw[NT == 4 ? r >> 3 : 0]) : "v"(yb) : "vcc");
+          }
         } else {
           v[nt] = acc[nt][r] + bv[nt];
           ssum[nt] += v[nt];
@@ -154,6 +180,12 @@ __global__ __launch_bounds__(256, 1) void conv1_fwd_kernel(Conv1Args a) {
         for (int nt = 0; nt < NT; ++nt) o[nt] = v[nt];
         CY_C1_ST(o, (vecn*)(yp + (size_t)p * a.Cout));
       }
+    }
+    if constexpr (MASK) {                   // one word per lane, 64 consecutive words per tile
+      typedef typename Conv1MaskWord<NT>::type mword;
+      mword* mp = (mword*)a.mask + (size_t)tile * 64 + lane;
+      if constexpr (NT == 4) CY_C1_ST((mword{mw[0], mw[1]}), mp);
+      else CY_C1_ST((mword)mw[0], mp);
     }
 #pragma unroll
     for (int s = 0; s < 14; ++s) acur[s] = anext[s];
@@ -356,13 +388,17 @@ __global__ __launch_bounds__(256, 1) void conv1_wgrad_kernel(Conv1Args a, float*
 
 // ---- backward of the whole first block (conv -> BatchNorm -> LeakyReLU) without z and without dz in memory.
 // The block's z (2.8 GB) would be read twice (BatchNorm-backward sums, then the apply pass) and dz written and read once
-// more by the weight gradient; instead both passes RECOMPUTE z = conv(x) + bias per 32-pixel tile (56 MFMAs, the image
-// is L2-resident) and read only dA, the gradient with respect to the activation:
+// more by the weight gradient; instead PASS 0 - 2 RECOMPUTE z = conv(x) + bias per 32-pixel tile (56 MFMAs, the image
+// is L2-resident) and read only dA, the gradient with respect to the activation (PASS 3 reads dA and one bit per element):
 //   PASS 0: red[c] += (sum d, sum d * xhat), d = dA * lrelu'(z * scale + shift), xhat = (z - mean) * invstd
 //   PASS 1: dz = scale * (d - m1 - xhat * m2) (m = red / count) is formed in registers IN THE LAYOUT the weight-gradient
 //           MFMA wants: the accumulator of the recomputed tile has lane = channel column, 16 pixel rows p(r, half), and the
 //           weight gradient's k dimension (pixels) may be enumerated in any order, so step s takes pixel p(s, half) --
 //           the lane's own accumulator row s -- and the image operand is fetched for the same pixel.
+//   PASS 2: one pass instead of the two (sum d and the weight gradient OF d; conv1_bn_bwd_finish_kernel has the rest from the
+//           forward's patch moments); it recomputes z like the others, but only for the sign of y.
+//   PASS 3: PASS 2 WITHOUT the recomputation: the sign of y comes from the bit mask that the forward's activation pass stored
+//           (conv1_fwd_kernel<.., MASK>) -- the fp32 training step from 2^18 pixels on takes this one.
 struct Conv1BnArgs {
   const float* X; const float* W; const float* bias; const float* dA;
   const float* scale; const float* shift; const float* mean; const float* invstd; float slope;
@@ -371,11 +407,20 @@ struct Conv1BnArgs {
   float* slabs;                             // PASS 1: per-wave partial dW
   int B, H, Wd, Cout;
   long long ntiles;
+  const void* mask;                         // PASS 3: the forward's sign words (Conv1MaskWord), [ntiles][64 lanes]
 };
 
 // GBF: dA is bf16 (it comes from the bf16 path's second block)
+// PASS 3 is PASS 2 without the recomputation: PASS 2 needs of the recomputed z nothing but the sign of y (xhat is dead there: the
+// finish kernel has sum d xhat from the patch moments), and the activation pass of the forward has left that bit per element
+// (conv1_fwd_kernel<.., MASK>).  The lane loads its sign word with the tile's dA and forms d = bit ? g : g * slope: no accumulator
+// of z, none of the 14 NT MFMAs, no image taps, no weights -- the patch operand of the weight gradient, the tile walk, the MFMA order
+// of dW, the slabs and the sum of d stay as they are, and the forward forms the bit from y = fma(acc + bias, scale, shift)
+// exactly as PASS 2 does (same MFMA order, same operations), so the results are those of PASS 2 to the bit.
 template <int NT, int PASS, bool GBF = false>
 __global__ __launch_bounds__(256, 1) void conv1_bn_bwd_kernel(Conv1BnArgs a) {
+  static_assert(PASS != 3 || !GBF, "the sign-mask pass reads an fp32 gradient");
+  constexpr bool RECOMP = PASS != 3;
   typedef float vecn __attribute__((ext_vector_type(NT)));
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int li = lane & 31, lh = lane >> 5;
@@ -385,17 +430,19 @@ __global__ __launch_bounds__(256, 1) void conv1_bn_bwd_kernel(Conv1BnArgs a) {
   // forward operand geometry (conv1_fwd_kernel): lane = pixel li, step s = taps 2 s + lh
   int toff[14], tky[14], tkx[14];
   float wreg[NT][14];
+  if constexpr (RECOMP) {
 #pragma unroll
-  for (int s = 0; s < 14; ++s) {
-    const int k = 2 * s + lh;
-    const int kk = k < 27 ? k : 0;
-    const int c = kk / 9, kh = (kk % 9) / 3, kw = kk % 3;
-    tky[s] = k < 27 ? kh - 1 : (1 << 20);
-    tkx[s] = kw - 1;
-    toff[s] = (int)(c * plane) + (kh - 1) * a.Wd + (kw - 1);
+    for (int s = 0; s < 14; ++s) {
+      const int k = 2 * s + lh;
+      const int kk = k < 27 ? k : 0;
+      const int c = kk / 9, kh = (kk % 9) / 3, kw = kk % 3;
+      tky[s] = k < 27 ? kh - 1 : (1 << 20);
+      tkx[s] = kw - 1;
+      toff[s] = (int)(c * plane) + (kh - 1) * a.Wd + (kw - 1);
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-      wreg[nt][s] = k < 27 ? a.W[((size_t)(NT * li + nt) * 3 + c) * 9 + kh * 3 + kw] : 0.f;
+      for (int nt = 0; nt < NT; ++nt)
+        wreg[nt][s] = k < 27 ? a.W[((size_t)(NT * li + nt) * 3 + c) * 9 + kh * 3 + kw] : 0.f;
+    }
   }
   // weight-gradient operand geometry (conv1_wgrad_kernel): lane = tap li, step s = pixel p(s, lh)
   const int kt = li < 27 ? li : 0;
@@ -406,8 +453,10 @@ __global__ __launch_bounds__(256, 1) void conv1_bn_bwd_kernel(Conv1BnArgs a) {
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     const int c = NT * li + nt;
-    bv[nt] = a.bias != nullptr ? a.bias[c] : 0.f;
-    sc[nt] = a.scale[c]; sh[nt] = a.shift[c]; is[nt] = a.invstd[c]; nm[nt] = -a.mean[c] * is[nt];
+    if constexpr (RECOMP) {
+      bv[nt] = a.bias != nullptr ? a.bias[c] : 0.f;
+      sc[nt] = a.scale[c]; sh[nt] = a.shift[c]; is[nt] = a.invstd[c]; nm[nt] = -a.mean[c] * is[nt];
+    }
     m1[nt] = PASS == 1 ? (float)(a.red_in[2 * c] * a.inv_count) : 0.f;
     m2[nt] = PASS == 1 ? (float)(a.red_in[2 * c + 1] * a.inv_count) : 0.f;
   }
@@ -423,18 +472,22 @@ __global__ __launch_bounds__(256, 1) void conv1_bn_bwd_kernel(Conv1BnArgs a) {
     const float* px = p0 + li;
     const bool inner = y >= 1 && y + 1 < a.H && seg >= 1 && seg + 1 < segs;    // uniform
     if (inner) {
+      if constexpr (RECOMP) {
 #pragma unroll
-      for (int s = 0; s < 14; ++s) av[s] = (s < 13 || lh == 0) ? px[toff[s]] : 0.f;
+        for (int s = 0; s < 14; ++s) av[s] = (s < 13 || lh == 0) ? px[toff[s]] : 0.f;
+      }
       if (PASS >= 1) {
 #pragma unroll
         for (int s = 0; s < 16; ++s) bw[s] = p0[woff + (s & 3) + 8 * (s >> 2)];
       }
     } else {
+      if constexpr (RECOMP) {
 #pragma unroll
-      for (int s = 0; s < 14; ++s) {
-        const bool ok = (unsigned)(y + tky[s]) < (unsigned)a.H && (unsigned)(seg * 32 + li + tkx[s]) < (unsigned)a.Wd;
-        const float v = px[ok ? toff[s] : 0];
-        av[s] = ok ? v : 0.f;
+        for (int s = 0; s < 14; ++s) {
+          const bool ok = (unsigned)(y + tky[s]) < (unsigned)a.H && (unsigned)(seg * 32 + li + tkx[s]) < (unsigned)a.Wd;
+          const float v = px[ok ? toff[s] : 0];
+          av[s] = ok ? v : 0.f;
+        }
       }
       if (PASS >= 1) {
         const bool rowok = (unsigned)(y + wkh - 1) < (unsigned)a.H;
@@ -482,22 +535,41 @@ __global__ __launch_bounds__(256, 1) void conv1_bn_bwd_kernel(Conv1BnArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) g[r] = CY_C1_LD((const vecn*)(pg + (size_t)((r & 3) + 8 * (r >> 2) + 4 * lh) * a.Cout));
     }
+    unsigned mw[2] = {0u, 0u};                // PASS 3: the lane's sign words of this tile, next element at the top bit
+    if constexpr (!RECOMP) {
+      typedef typename Conv1MaskWord<NT>::type mword;
+      const mword m = CY_C1_LD((const mword*)a.mask + (size_t)tile * 64 + lane);
+      if constexpr (NT == 4) { mw[0] = m[0]; mw[1] = m[1]; }
+      else if constexpr (NT == 2) mw[0] = m;
+      else mw[0] = (unsigned)m << 16;
+    }
     const long long tn = tile + nw;
     if (tn < a.ntiles) load_img(tn, anext, bwnext);
     f32x16 acc[NT];
+    if constexpr (RECOMP) {
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
+      for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
+        for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
 #pragma unroll
-    for (int s = 0; s < 14; ++s)
+      for (int s = 0; s < 14; ++s)
 #pragma unroll
-      for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(acur[s], wreg[nt][s], acc[nt], 0, 0, 0);
+        for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(acur[s], wreg[nt][s], acc[nt], 0, 0, 0);
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       float dzr[NT];
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
+        if constexpr (!RECOMP) {              // sum d and the weight gradient OF d, as PASS 2
+          unsigned& m = mw[NT == 4 ? r >> 3 : 0];
+          const float gv = ((const float*)&g[r])[nt];
+          const float d = (int)m < 0 ? gv : gv * a.slope;
+          m <<= 1;
+          b1[nt] += d;
+          dzr[nt] = d;
+          continue;
+        }
         const float z = acc[nt][r] + bv[nt];
         const float y = __builtin_fmaf(z, sc[nt], sh[nt]);
         const float gv = ((const float*)&g[r])[nt];
@@ -518,14 +590,16 @@ __global__ __launch_bounds__(256, 1) void conv1_bn_bwd_kernel(Conv1BnArgs a) {
         for (int nt = 0; nt < NT; ++nt) accw[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(dzr[nt], bwcur[r], accw[nt], 0, 0, 0);
       }
     }
+    if constexpr (RECOMP) {
 #pragma unroll
-    for (int s = 0; s < 14; ++s) acur[s] = anext[s];
+      for (int s = 0; s < 14; ++s) acur[s] = anext[s];
+    }
     if (PASS >= 1) {
 #pragma unroll
       for (int s = 0; s < 16; ++s) bwcur[s] = bwnext[s];
     }
   }
-  if (PASS == 0 || PASS == 2) {
+  if (PASS == 0 || PASS >= 2) {
     double* rd = a.red_out + (size_t)((blockIdx.x * 4 + wave) % CY_STATS_COPIES) * a.Cout * 2;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -813,7 +887,7 @@ extern "C" int cy_conv1_3x3_wgrad(const float* X, const float* dZ, float* dW, fl
   CY_REQUIRE(Cout == 32 || Cout == 64 || Cout == 128, "cy_conv1_3x3_wgrad: Cout=%d must be 32, 64 or 128", Cout);
   CY_REQUIRE((long long)3 * H * Wd < (1ll << 30), "cy_conv1_3x3_wgrad: image too large for 32-bit offsets");
   Conv1Args a;
-  a.X = X; a.W = nullptr; a.bias = nullptr; a.Y = const_cast<float*>(dZ); a.stats = nullptr;
+  a.X = X; a.W = nullptr; a.bias = nullptr; a.Y = const_cast<float*>(dZ); a.stats = nullptr; a.mask = nullptr;
   a.scale = a.shift = nullptr; a.slope = 1.f;
   a.B = B; a.H = H; a.Wd = Wd; a.Cout = Cout;
   a.ntiles = (long long)B * H * (Wd / 32);
@@ -849,7 +923,7 @@ static int conv1_bn_bwd_reduce_impl(const char* who, const float* X, const float
   CY_REQUIRE(red != nullptr, "%s: red is NULL", who);
   Conv1BnArgs a;
   a.X = X; a.W = W; a.bias = bias; a.dA = (const float*)dA; a.scale = scale; a.shift = shift; a.mean = mean; a.invstd = invstd;
-  a.slope = slope; a.red_out = red; a.red_in = nullptr; a.inv_count = 0.0; a.slabs = nullptr;
+  a.slope = slope; a.red_out = red; a.red_in = nullptr; a.inv_count = 0.0; a.slabs = nullptr; a.mask = nullptr;
   a.B = B; a.H = H; a.Wd = Wd; a.Cout = Cout; a.ntiles = (long long)B * H * (Wd / 32);
   long long blocks = 0;
   rc = conv1_blocks(a.ntiles, &blocks, who);
@@ -890,11 +964,12 @@ extern "C" int cy_conv1_bn_bwd_reduce_bf16(const float* X, const float* W, const
 static int conv1_bn_bwd_onepass_impl(const char* who, const float* X, const float* W, const float* bias, const void* dA, bool da_bf16,
                                      const float* scale, const float* shift, const float* mean, const float* invstd, float slope,
                                      const double* M2, double* redc, float* dW, float* dgamma, float* dbeta, double* red_out,
-                                     float* ws, int B, int H, int Wd, int Cout, void* stream) {
+                                     float* ws, int B, int H, int Wd, int Cout, void* stream, const void* mask = nullptr) {
   int rc = conv1_bn_check(who, X, W, (const float*)dA, scale, shift, mean, invstd, slope, B, H, Wd, Cout);
   if (rc) return rc;
   CY_REQUIRE(M2 && redc && dW && dgamma && dbeta && ws, "%s: NULL argument", who);
   Conv1BnArgs a;
+  a.mask = mask;
   a.X = X; a.W = W; a.bias = bias; a.dA = (const float*)dA; a.scale = scale; a.shift = shift; a.mean = mean; a.invstd = invstd;
   a.slope = slope; a.red_out = redc; a.red_in = nullptr; a.inv_count = 0.0; a.slabs = ws;
   a.B = B; a.H = H; a.Wd = Wd; a.Cout = Cout; a.ntiles = (long long)B * H * (Wd / 32);
@@ -902,7 +977,11 @@ static int conv1_bn_bwd_onepass_impl(const char* who, const float* X, const floa
   rc = conv1_blocks(a.ntiles, &blocks, who);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (da_bf16) {
+  if (mask != nullptr) {
+    if (Cout == 128) conv1_bn_bwd_kernel<4, 3><<<(unsigned)blocks, 256, 0, s>>>(a);
+    else if (Cout == 64) conv1_bn_bwd_kernel<2, 3><<<(unsigned)blocks, 256, 0, s>>>(a);
+    else conv1_bn_bwd_kernel<1, 3><<<(unsigned)blocks, 256, 0, s>>>(a);
+  } else if (da_bf16) {
 #ifdef CY_C1_F32MM
     if (Cout == 128) conv1_bn_bwd_kernel<4, 2, true><<<(unsigned)blocks, 256, 0, s>>>(a);
     else if (Cout == 64) conv1_bn_bwd_kernel<2, 2, true><<<(unsigned)blocks, 256, 0, s>>>(a);
@@ -938,6 +1017,17 @@ extern "C" int cy_conv1_bn_bwd_onepass_bf16(const float* X, const float* W, cons
                                    dW, dgamma, dbeta, red_out, ws, B, H, Wd, Cout, stream);
 }
 
+// ... and without the recomputation of z: the sign of y comes from the words that cy_conv1_3x3_fwd_act_mask stored
+extern "C" int cy_conv1_bn_bwd_onepass_mask(const float* X, const float* W, const float* bias, const float* dA, const void* mask,
+                                            const float* scale, const float* shift, const float* mean, const float* invstd, float slope,
+                                            const double* M2, double* redc, float* dW, float* dgamma, float* dbeta, double* red_out,
+                                            float* ws, int B, int H, int Wd, int Cout, void* stream) {
+  CY_REQUIRE(mask != nullptr, "cy_conv1_bn_bwd_onepass_mask: mask is NULL");
+  CY_REQUIRE((((uintptr_t)dA | (uintptr_t)mask) & 15) == 0, "cy_conv1_bn_bwd_onepass_mask: operands must be 16-byte aligned");
+  return conv1_bn_bwd_onepass_impl("cy_conv1_bn_bwd_onepass_mask", X, W, bias, dA, false, scale, shift, mean, invstd, slope, M2, redc, dW,
+                                   dgamma, dbeta, red_out, ws, B, H, Wd, Cout, stream, mask);
+}
+
 extern "C" long long cy_conv1_bn_bwd_wgrad_ws_floats(int B, int H, int Wd, int Cout) {
   return cy_conv1_3x3_wgrad_ws_floats(B, H, Wd, Cout);
 }
@@ -951,7 +1041,7 @@ static int conv1_bn_bwd_wgrad_impl(const char* who, bool da_bf16, const float* X
   CY_REQUIRE(red && dW && ws && count > 0, "cy_conv1_bn_bwd_wgrad: bad arguments");
   Conv1BnArgs a;
   a.X = X; a.W = W; a.bias = bias; a.dA = (const float*)dA; a.scale = scale; a.shift = shift; a.mean = mean; a.invstd = invstd;
-  a.slope = slope; a.red_out = nullptr; a.red_in = red; a.inv_count = 1.0 / (double)count; a.slabs = ws;
+  a.slope = slope; a.red_out = nullptr; a.red_in = red; a.inv_count = 1.0 / (double)count; a.slabs = ws; a.mask = nullptr;
   a.B = B; a.H = H; a.Wd = Wd; a.Cout = Cout; a.ntiles = (long long)B * H * (Wd / 32);
   long long blocks = 0;
   rc = conv1_blocks(a.ntiles, &blocks, who);
@@ -993,37 +1083,60 @@ extern "C" int cy_conv1_bn_bwd_wgrad_bf16(const float* X, const float* W, const 
                                  ws, B, H, Wd, Cout, stream);
 }
 
-extern "C" int cy_conv1_3x3_fwd(const float* X, const float* W, const float* bias, float* Y, double* stats,
-                                const float* scale, const float* shift, float slope, int B, int H, int Wd, int Cout,
-                                void* stream) {
-  CY_REQUIRE(X && W && (Y || (stats && !scale)) && B > 0 && H > 0 && Wd > 0, "cy_conv1_3x3_fwd: bad arguments");
-  CY_REQUIRE((scale == nullptr) == (shift == nullptr), "cy_conv1_3x3_fwd: scale and shift go together");
+static int conv1_fwd_impl(const char* who, const float* X, const float* W, const float* bias, float* Y, double* stats,
+                         const float* scale, const float* shift, float slope, void* mask, int B, int H, int Wd, int Cout,
+                         void* stream) {
+  CY_REQUIRE(X && W && (Y || (stats && !scale)) && B > 0 && H > 0 && Wd > 0, "%s: bad arguments", who);
+  CY_REQUIRE((scale == nullptr) == (shift == nullptr), "%s: scale and shift go together", who);
   CY_REQUIRE(scale == nullptr || (stats == nullptr && slope >= 0.f && slope <= 1.f),
-             "cy_conv1_3x3_fwd: the affine pass takes no statistics and a slope in [0, 1]");
-  CY_REQUIRE(Wd % 32 == 0, "cy_conv1_3x3_fwd: W=%d must be a multiple of 32", Wd);
-  CY_REQUIRE(Cout == 32 || Cout == 64 || Cout == 128, "cy_conv1_3x3_fwd: Cout=%d must be 32, 64 or 128", Cout);
-  CY_REQUIRE((long long)3 * H * Wd < (1ll << 30), "cy_conv1_3x3_fwd: image too large for 32-bit offsets");
+             "%s: the affine pass takes no statistics and a slope in [0, 1]", who);
+  CY_REQUIRE(Wd % 32 == 0, "%s: W=%d must be a multiple of 32", who, Wd);
+  CY_REQUIRE(Cout == 32 || Cout == 64 || Cout == 128, "%s: Cout=%d must be 32, 64 or 128", who, Cout);
+  CY_REQUIRE((long long)3 * H * Wd < (1ll << 30), "%s: image too large for 32-bit offsets", who);
   Conv1Args a;
   a.X = X; a.W = W; a.bias = bias; a.Y = Y; a.stats = stats;
   a.scale = scale; a.shift = shift; a.slope = slope;
   a.B = B; a.H = H; a.Wd = Wd; a.Cout = Cout;
   a.ntiles = (long long)B * H * (Wd / 32);
+  a.mask = mask;
   long long blocks = 0;
-  int rc = conv1_blocks(a.ntiles, &blocks, "cy_conv1_3x3_fwd");
+  int rc = conv1_blocks(a.ntiles, &blocks, who);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-#define CY_CONV1_LAUNCH(NT_)                                                                  \
-  do {                                                                                         \
-    if (scale) conv1_fwd_kernel<NT_, true, true><<<(unsigned)blocks, 256, 0, s>>>(a);          \
-    else if (Y) conv1_fwd_kernel<NT_, false, true><<<(unsigned)blocks, 256, 0, s>>>(a);        \
-    else conv1_fwd_kernel<NT_, false, false><<<(unsigned)blocks, 256, 0, s>>>(a);              \
+#define CY_CONV1_LAUNCH(NT_)                                                                             \
+  do {                                                                                                    \
+    if (mask) conv1_fwd_kernel<NT_, true, true, false, true><<<(unsigned)blocks, 256, 0, s>>>(a);         \
+    else if (scale) conv1_fwd_kernel<NT_, true, true><<<(unsigned)blocks, 256, 0, s>>>(a);                \
+    else if (Y) conv1_fwd_kernel<NT_, false, true><<<(unsigned)blocks, 256, 0, s>>>(a);                   \
+    else conv1_fwd_kernel<NT_, false, false><<<(unsigned)blocks, 256, 0, s>>>(a);                         \
   } while (0)
   if (Cout == 128) CY_CONV1_LAUNCH(4);
   else if (Cout == 64) CY_CONV1_LAUNCH(2);
   else CY_CONV1_LAUNCH(1);
 #undef CY_CONV1_LAUNCH
-  CY_LAUNCH_CHECK("cy_conv1_3x3_fwd");
+  CY_LAUNCH_CHECK(who);
   return 0;
+}
+
+extern "C" int cy_conv1_3x3_fwd(const float* X, const float* W, const float* bias, float* Y, double* stats,
+                                const float* scale, const float* shift, float slope, int B, int H, int Wd, int Cout,
+                                void* stream) {
+  return conv1_fwd_impl("cy_conv1_3x3_fwd", X, W, bias, Y, stats, scale, shift, slope, nullptr, B, H, Wd, Cout, stream);
+}
+
+// bytes of the sign mask of a [B][H][W][Cout] activation: one bit per element
+extern "C" long long cy_conv1_signmask_bytes(int B, int H, int Wd, int Cout) {
+  if (B <= 0 || H <= 0 || Wd <= 0 || Wd % 32 || !(Cout == 32 || Cout == 64 || Cout == 128)) return -1;
+  return (long long)B * H * Wd * (Cout / 8);
+}
+
+// the activation pass of the first block (scale / shift mandatory) that also leaves the sign of y = z * scale + shift of every
+// element in `mask` (cy_conv1_signmask_bytes bytes) for cy_conv1_bn_bwd_onepass_mask; mask NULL: cy_conv1_3x3_fwd's own launch
+extern "C" int cy_conv1_3x3_fwd_act_mask(const float* X, const float* W, const float* bias, float* Y, const float* scale,
+                                         const float* shift, float slope, void* mask, int B, int H, int Wd, int Cout, void* stream) {
+  CY_REQUIRE(Y && scale && shift, "cy_conv1_3x3_fwd_act_mask: bad arguments");
+  CY_REQUIRE((((uintptr_t)Y | (uintptr_t)mask) & 15) == 0, "cy_conv1_3x3_fwd_act_mask: operands must be 16-byte aligned");
+  return conv1_fwd_impl("cy_conv1_3x3_fwd_act_mask", X, W, bias, Y, nullptr, scale, shift, slope, mask, B, H, Wd, Cout, stream);
 }
 
 // the activation pass of the first block with a bf16 output (Y: bf16 [B][H][W][Cout]); scale / shift are mandatory
@@ -1035,7 +1148,7 @@ extern "C" int cy_conv1_3x3_fwd_act_bf16(const float* X, const float* W, const f
   CY_REQUIRE(Cout == 32 || Cout == 64 || Cout == 128, "cy_conv1_3x3_fwd_act_bf16: Cout=%d must be 32, 64 or 128", Cout);
   CY_REQUIRE((long long)3 * H * Wd < (1ll << 30), "cy_conv1_3x3_fwd_act_bf16: image too large for 32-bit offsets");
   Conv1Args a;
-  a.X = X; a.W = W; a.bias = bias; a.Y = (float*)Y; a.stats = nullptr;
+  a.X = X; a.W = W; a.bias = bias; a.Y = (float*)Y; a.stats = nullptr; a.mask = nullptr;
   a.scale = scale; a.shift = shift; a.slope = slope;
   a.B = B; a.H = H; a.Wd = Wd; a.Cout = Cout;
   a.ntiles = (long long)B * H * (Wd / 32);

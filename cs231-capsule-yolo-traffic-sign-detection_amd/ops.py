@@ -131,6 +131,7 @@ STATS_COPIES = 16       # CY_STATS_COPIES of include/capsyolo_hip.h: BatchNorm s
 USE_CONV1_MOMENTS = True  # ... whose BatchNorm statistics come from the 28 x 28 moment matrix of the input patches (csrc/conv1_moments.hip)
 FUSE_BN_BWD_APPLY_BF16 = True   # bf16 path: BatchNorm-backward pass 2 inside the weight gradient (cy_conv_wgrad_bf16_bn) where the gradient arrives premasked
 USE_CONV1_ONEPASS = True  # ... and whose backward then needs ONE pass over the gradient (cy_conv1_bn_bwd_onepass)
+CONV1_SIGNMASK = True     # ... which takes lrelu'(y) from one bit per element that the activation pass stored (cy_conv1_bn_bwd_onepass_mask: no z recomputed)
 CONV1_MOMENTS_MIN_PIXELS = 1 << 18   # ... from this many pixels on: below, its three launches cost more than the one recompute pass saves
 USE_CONV1_BWD = True     # ... and the backward of its whole conv -> BatchNorm -> LeakyReLU block without z / dz in memory
 USE_CONV1 = True         # 3 -> {32, 64, 128} channels, 3x3, NCHW image (the backbones' first layer): dedicated store-bound kernels
@@ -166,7 +167,8 @@ ConvPlan = collections.namedtuple('ConvPlan', [
     'conv1',                   # a first-layer shape (csrc/conv1.hip: 3 -> {32, 64, 128} channels, 3x3 s1 p1, NCHW image)
     'conv1_bwd',               # ... whose training block runs without z / dz in memory
     'conv1_moments',           # ... taking its statistics from the moment matrix of the input patches
-    'conv1_onepass'])          # ... and, behind those statistics, its backward in one pass over the gradient
+    'conv1_onepass',           # ... and, behind those statistics, its backward in one pass over the gradient
+    'conv1_signmask'])         # ... that reads the sign of y from the forward's bit mask instead of recomputing z (fp32 block)
 _WINO3_DGRAD = ('conv_wino_dgrad', 'conv_wino4_dgrad')
 
 
@@ -215,9 +217,11 @@ def conv_plan(in_shape, cout, k, stride, pad, nchw=False, relu=False, lrelu=Fals
             wgrad, in_affine = 'conv_wino2_wgrad', not relu
     dgrad_bn_fuse = bool(FUSE_BN_BWD_REDUCE and dgrad is not None and dgrad not in _WINO3_DGRAD and Cin % 4 == 0)
     conv1_bwd = bool(conv1 and USE_CONV1_BWD)
+    conv1_moments = bool(conv1_bwd and USE_CONV1_MOMENTS and B * Hi * Wi >= CONV1_MOMENTS_MIN_PIXELS)
+    conv1_onepass = bool(conv1 and USE_CONV1_ONEPASS)
     return ConvPlan(fwd, dgrad, wgrad, in_affine, dgrad_bn_fuse, dgrad_bn_fuse and dgrad in ('conv_wino2_dgrad', 'conv_wino42_dgrad'),
-                    wgrad_bn, wgrad_bn4, conv1, conv1_bwd,
-                    bool(conv1_bwd and USE_CONV1_MOMENTS and B * Hi * Wi >= CONV1_MOMENTS_MIN_PIXELS), bool(conv1 and USE_CONV1_ONEPASS))
+                    wgrad_bn, wgrad_bn4, conv1, conv1_bwd, conv1_moments, conv1_onepass,
+                    bool(CONV1_SIGNMASK and conv1_moments and conv1_onepass))
 
 
 def _winograd(x, weight, bias, stats, transpose, f4, tag, out_slope=1.0):
@@ -242,14 +246,21 @@ def _winograd(x, weight, bias, stats, transpose, f4, tag, out_slope=1.0):
     return y
 
 
-def conv1_affine_act(x, weight, bias, scale, shift, slope, tag='conv', out_bf16=False):
+def conv1_affine_act(x, weight, bias, scale, shift, slope, tag='conv', out_bf16=False, mask=None):
     """lrelu((conv(x) + bias) * scale + shift) in one pass of the first-layer kernel (the second pass of its conv ->
     BatchNorm -> LeakyReLU block: recomputing the layer costs less than reading its 2.8 GB output back).
-    out_bf16: the activation is written as bf16 (the bf16 path's second block reads it as such)."""
+    out_bf16: the activation is written as bf16 (the bf16 path's second block reads it as such).
+    mask: uint8 tensor of cy_conv1_signmask_bytes bytes that receives one bit per element, y > 0 (fp32 output only)."""
     B, _, Hi, Wi = x.shape
     Cout = weight.shape[0]
     with timer.range('conv1_fwd_act/' + tag):
-        if out_bf16:
+        if mask is not None:
+            if out_bf16:
+                raise _lib.HipExtensionError('conv1_affine_act: the sign mask belongs to the fp32 activation pass')
+            out = _empty((B, Hi, Wi, Cout), x)
+            call('cy_conv1_3x3_fwd_act_mask', _ptr(x), _ptr(weight.contiguous()), _ptr(bias), _ptr(out), _ptr(scale), _ptr(shift),
+                 float(slope), _ptr(mask), B, Hi, Wi, Cout, _stream())
+        elif out_bf16:
             out = torch.empty((B, Hi, Wi, Cout), dtype=torch.bfloat16, device=x.device)
             call('cy_conv1_3x3_fwd_act_bf16', _ptr(x), _ptr(weight.contiguous()), _ptr(bias), _ptr(out), _ptr(scale), _ptr(shift),
                  float(slope), B, Hi, Wi, Cout, _stream())
@@ -529,7 +540,7 @@ class _ConvBlock(torch.autograd.Function):
         plan = conv_plan(x.shape, N, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in)
         # the first block (csrc/conv1.hip): z is never written -- this pass only takes the statistics, the activation
         # pass and both backward passes recompute the convolution
-        ctx.conv1_m2 = None
+        ctx.conv1_m2 = ctx.conv1_mask = None
         ctx.conv1_fused = bool(plan.conv1_bwd and bn.training and not cfg.defer_act and not x.requires_grad and 0.0 <= slope <= 1.0)
         if bn.training:
             stats = zero_pool.take((STATS_COPIES, N, 2), torch.float64, x.device)
@@ -579,7 +590,11 @@ class _ConvBlock(torch.autograd.Function):
             ctx.holder = cfg.out_holder = {'mean': mean, 'invstd': invstd, 'red': None} if ctx.bn_train else None
             return z, scale, shift
         if plan.conv1 and 0.0 <= slope <= 1.0:
-            return conv1_affine_act(x, weight, bias, scale, shift, slope, cfg.name, cfg.out_bf16)
+            if plan.conv1_signmask and ctx.conv1_m2 is not None and not cfg.out_bf16 and _sync_world()[0] is None:
+                # the training forward of the fp32 first block: the one-pass backward will want the sign of y and nothing else of z
+                Bx, _, Hx, Wx = x.shape
+                ctx.conv1_mask = torch.empty((query('cy_conv1_signmask_bytes', Bx, Hx, Wx, N),), dtype=torch.uint8, device=x.device)
+            return conv1_affine_act(x, weight, bias, scale, shift, slope, cfg.name, cfg.out_bf16, ctx.conv1_mask)
         out = torch.empty_like(z)
         call('cy_affine_act', _ptr(z), _ptr(out), _ptr(scale), _ptr(shift), slope, P, N, st)
         return _leave(out, cfg, st)
@@ -632,9 +647,14 @@ class _ConvBlock(torch.autograd.Function):
                 if plan.conv1_onepass and ctx.conv1_m2 is not None and _sync_world()[0] is None:
                     # one pass over da: sum d and the weight gradient OF d; the rest follows from the forward's patch moments
                     with timer.range('conv1_bn_bwd_onepass/' + cfg.name):
-                        call('cy_conv1_bn_bwd_onepass_bf16' if da_bf16 else 'cy_conv1_bn_bwd_onepass', _ptr(x), _ptr(weight),
-                             _ptr(bias_t), _ptr(da), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), slope,
-                             _ptr(ctx.conv1_m2), _ptr(redc), _ptr(dW), _ptr(dgamma), _ptr(dbeta), None, _ptr(ws), B, Hi, Wi, N, st)
+                        if ctx.conv1_mask is not None and not da_bf16 and da.data_ptr() % 16 == 0:
+                            call('cy_conv1_bn_bwd_onepass_mask', _ptr(x), _ptr(weight), _ptr(bias_t), _ptr(da), _ptr(ctx.conv1_mask),
+                                 _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), slope, _ptr(ctx.conv1_m2), _ptr(redc), _ptr(dW),
+                                 _ptr(dgamma), _ptr(dbeta), None, _ptr(ws), B, Hi, Wi, N, st)
+                        else:
+                            call('cy_conv1_bn_bwd_onepass_bf16' if da_bf16 else 'cy_conv1_bn_bwd_onepass', _ptr(x), _ptr(weight),
+                                 _ptr(bias_t), _ptr(da), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), slope,
+                                 _ptr(ctx.conv1_m2), _ptr(redc), _ptr(dW), _ptr(dgamma), _ptr(dbeta), None, _ptr(ws), B, Hi, Wi, N, st)
                     return None, dW, dbias, dgamma, dbeta, None, None, None
                 with timer.range('conv1_bn_bwd_reduce/' + cfg.name):
                     call('cy_conv1_bn_bwd_reduce_bf16' if da_bf16 else 'cy_conv1_bn_bwd_reduce', _ptr(x), _ptr(weight), _ptr(bias_t), _ptr(da), _ptr(scale), _ptr(shift),

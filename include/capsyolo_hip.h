@@ -126,6 +126,24 @@ int cy_conv1_bn_bwd_onepass_bf16(const float* X, const float* W, const float* bi
                                  const float* shift, const float* mean, const float* invstd, float slope, const double* M2,
                                  double* redc, float* dW, float* dgamma, float* dbeta, double* red_out, float* ws, int B, int H,
                                  int Wd, int Cout, void* stream);
+/* The fp32 one-pass backward WITHOUT the recomputation of z: that pass needs of z only the sign of y = z * scale + shift, which the
+ * activation pass of the forward has in registers.  cy_conv1_3x3_fwd_act_mask is the activation pass of cy_conv1_3x3_fwd (scale /
+ * shift mandatory, the same Y to the byte) that also stores one bit per element, y > 0, in mask (cy_conv1_signmask_bytes bytes =
+ * B H W Cout / 8; mask NULL: exactly cy_conv1_3x3_fwd's launch); cy_conv1_bn_bwd_onepass_mask is cy_conv1_bn_bwd_onepass reading
+ * those bits instead of the image taps and the weights.  Layout: per 32-pixel tile (global tile number) and lane of the wave one
+ * word of 16 Cout / 32 bits, mask[tile][lane] -- two 32-bit words for Cout = 128, one for 64, a 16-bit word for 32; the lane's
+ * elements e = (Cout / 32) r + nt (accumulator row r, channel tile nt) fill the words from the top bit down.  The bit is y > 0
+ * of y = fma(conv + bias, scale, shift), operation for operation what cy_conv1_bn_bwd_onepass recomputes, so the two backward
+ * entry points give the same results to the bit.  (The stored activation comes from fma(conv, scale, bias * scale + shift): with
+ * a bias, an element whose y lies within rounding of zero can be stored with the other sign than its bit.)  Y, dA and mask
+ * 16-byte aligned. */
+long long cy_conv1_signmask_bytes(int B, int H, int Wd, int Cout);
+int cy_conv1_3x3_fwd_act_mask(const float* X, const float* W, const float* bias, float* Y, const float* scale,
+                              const float* shift, float slope, void* mask, int B, int H, int Wd, int Cout, void* stream);
+int cy_conv1_bn_bwd_onepass_mask(const float* X, const float* W, const float* bias, const float* dA, const void* mask,
+                                 const float* scale, const float* shift, const float* mean, const float* invstd, float slope,
+                                 const double* M2, double* redc, float* dW, float* dgamma, float* dbeta, double* red_out,
+                                 float* ws, int B, int H, int Wd, int Cout, void* stream);
 
 /* number of floats of a packed-weight buffer for (K = TH*TW*Cin, N) */
 long long cy_conv_packed_floats(int K, int N);
