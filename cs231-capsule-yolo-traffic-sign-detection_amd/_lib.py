@@ -133,6 +133,8 @@ _SIGS = {
     'cy_combine_scores': [_P, _P, _P, _P, _I, _P, C.c_double, _I, _I, _I, _I, _P, _P, _P, _P],
     'cy_yolo_decode_boxes_conf': [_P, _P, C.c_double, C.c_double, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P],
     'cy_confusion_sweep': [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P],
+    'cy_boxes_crop_resize_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P],
+    'cy_pack_detections': [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     'cy_draw_boxes_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _I, _P, _P, _P],
     'cy_paste_resize_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _I, _L, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P],
     'cy_gather_jitter_u8': [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P],

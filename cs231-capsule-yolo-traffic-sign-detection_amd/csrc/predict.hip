@@ -6,18 +6,14 @@
 //   yolo_decode_conf_kernel   utils.y_to_boxes_vec (utils.py:288-334) that also returns each box's confidence
 //   confusion_sweep_kernel    metrics.single_img_confusion for every (group, confidence threshold, IoU threshold) at once
 #include "common.h"
+#include "crop_pixel.h"
 
 // the double arithmetic below restates numpy expressions operation by operation: no fused multiply-add
 #pragma clang fp contract(off)
 
 namespace {
 
-struct __attribute__((packed, aligned(4))) float3s { float x, y, z; };
-
-// One thread per output pixel.  A crop is resized as a stand-alone image with the half-pixel convention of cv2's
-// INTER_LINEAR: source coordinate s = (o + 0.5) * n_in / n_out - 0.5, rows floor(s) and floor(s) + 1 clamped into the crop.
-// The coordinate is kept as the exact fraction ((2 o + 1) n_in - n_out) / (2 n_out), so the only rounding of the weight is
-// the final division; the interpolation itself is fp32 (cv2's 11-bit fixed-point weights are not reproduced).
+// One thread per output pixel; the pixel itself is cyi_crop_pixel (crop_pixel.h, shared with serve.hip).
 __global__ __launch_bounds__(256) void crop_resize_u8_kernel(const unsigned char* __restrict__ imgs, const long long* __restrict__ img_off,
                                                              const int* __restrict__ img_hw, const int* __restrict__ box_img,
                                                              const int* __restrict__ rect, long long total, int n_images, long long imgs_bytes, int OH, int OW,
@@ -29,7 +25,7 @@ __global__ __launch_bounds__(256) void crop_resize_u8_kernel(const unsigned char
   const int oy = (int)(q % OH);
   const long long b = q / OH;
   const int img = box_img[b];
-  float r = 0.f, g = 0.f, bl = 0.f;
+  float v[3] = {0.f, 0.f, 0.f};
   bool ok = img >= 0 && img < n_images;
   int y0 = 0, y1 = 0, x0 = 0, x1 = 0, W = 0;
   if (ok) {
@@ -42,36 +38,9 @@ __global__ __launch_bounds__(256) void crop_resize_u8_kernel(const unsigned char
   if (!ok) {
     if (ox == 0 && oy == 0) atomicAdd(err, 1);       // one count per bad box; its output is zero-filled
   } else {
-    const int ch = y1 - y0, cw = x1 - x0;
-    const long long ny = (long long)(2 * oy + 1) * ch - OH, nx = (long long)(2 * ox + 1) * cw - OW;
-    // floor division (the numerator is negative for the first outputs of an upscale)
-    long long ry = ny / (2 * OH), rx = nx / (2 * OW);
-    if (ny < 0 && ry * 2 * OH != ny) --ry;
-    if (nx < 0 && rx * 2 * OW != nx) --rx;
-    const float fy = (float)(ny - ry * 2 * OH) / (float)(2 * OH), fx = (float)(nx - rx * 2 * OW) / (float)(2 * OW);
-    const int ra = (int)min(max(ry, 0ll), (long long)ch - 1), rb = (int)min(max(ry + 1, 0ll), (long long)ch - 1);
-    const int ca = (int)min(max(rx, 0ll), (long long)cw - 1), cb = (int)min(max(rx + 1, 0ll), (long long)cw - 1);
-    const unsigned char* base = imgs + img_off[img];
-    const unsigned char* paa = base + ((long long)(y0 + ra) * W + (x0 + ca)) * 3;
-    const unsigned char* pab = base + ((long long)(y0 + ra) * W + (x0 + cb)) * 3;
-    const unsigned char* pba = base + ((long long)(y0 + rb) * W + (x0 + ca)) * 3;
-    const unsigned char* pbb = base + ((long long)(y0 + rb) * W + (x0 + cb)) * 3;
-    float v[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float aa = (float)paa[c], ab = (float)pab[c], ba = (float)pba[c], bb = (float)pbb[c];
-      const float top = aa + fx * (ab - aa), bot = ba + fx * (bb - ba);
-      v[c] = (top + fy * (bot - top) + shift) * scale;
-    }
-    r = v[0]; g = v[1]; bl = v[2];
+    cyi_crop_pixel(imgs + img_off[img], W, y0, y1, x0, x1, oy, ox, OH, OW, shift, scale, v);
   }
-  if (to_nchw) {
-    const long long plane = (long long)OH * OW, o = b * 3 * plane + (long long)oy * OW + ox;
-    out[o] = r; out[o + plane] = g; out[o + 2 * plane] = bl;
-  } else {
-    float3s px; px.x = r; px.y = g; px.z = bl;
-    *(float3s*)(out + 3 * i) = px;                     // one 12-byte store
-  }
+  cyi_store_pixel(out, i, b, oy, ox, OH, OW, to_nchw, v[0], v[1], v[2]);
 }
 
 // combine_y_hat, step 1: the cell of every box, in the reference's order of operations (resize_box_xy -> xy_to_cwh ->

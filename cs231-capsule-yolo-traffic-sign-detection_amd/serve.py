@@ -1,0 +1,209 @@
+"""Streaming sign detector: camera frames in, labelled boxes out, with no host hop between the two networks.
+
+predict_fns.dark_class_pred scores a whole test set and crosses to the host in the middle of every chunk (box count, decoded boxes
+to numpy for utils.crop_rectangles, rectangles up again, the crop kernel's error word).  `SignDetector` runs the same chain --
+resize -> detector -> decode -> crops -> classifier -> arg-max -- for a FIXED number of box slots, `max_boxes`: the box list stays in
+device memory (`cy_boxes_crop_resize_u8` reads the count there and computes the rectangles itself), the classifier always sees
+`max_boxes` crops (dead slots are zero crops; in eval mode every sample is independent, so they cannot affect the live ones), and
+`cy_pack_detections` writes everything the host wants into ONE record buffer: one copy to the host and one event wait per call.
+Every launch has a shape that depends on the frame shape and `max_boxes` alone, so with graph=True the steps between the frame
+upload and the record download are captured once per frame shape in a HIP graph and replayed.
+
+Bad boxes (a corner that is not finite, an empty rectangle after clipping) do not raise as they do in utils.crop_rectangles: a
+serving loop must not die on one degenerate box.  They come back with class -1 and are counted in `Detections.bad`.
+"""
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import HipExtensionError, call
+
+# the record buffer of cy_pack_detections (include/capsyolo_hip.h): cy_detections_header_t, then max_boxes cy_detection_t
+HEADER_DTYPE = np.dtype([('total', '<i4'), ('kept', '<i4'), ('crop_err', '<i4'), ('resize_err', '<i4')])
+RECORD_DTYPE = np.dtype([('xy', '<f8', (4,)), ('image', '<i4'), ('cls', '<i4'), ('conf', '<f4'), ('score', '<f4')])
+assert HEADER_DTYPE.itemsize == 16 and RECORD_DTYPE.itemsize == 48
+
+
+def record_bytes(max_boxes):
+    return HEADER_DTYPE.itemsize + RECORD_DTYPE.itemsize * int(max_boxes)
+
+
+def unpack_record(buf, max_boxes):
+    """(header, records) views of a record buffer (a uint8 array of record_bytes(max_boxes) bytes)."""
+    buf = np.asarray(buf, dtype=np.uint8).reshape(-1)
+    if buf.size != record_bytes(max_boxes):
+        raise ValueError('a record of %d slots has %d bytes, got %d' % (max_boxes, record_bytes(max_boxes), buf.size))
+    return buf[:HEADER_DTYPE.itemsize].view(HEADER_DTYPE)[0], buf[HEADER_DTYPE.itemsize:].view(RECORD_DTYPE)
+
+
+class Detections(object):
+    """What one `SignDetector.detect` call found.  n boxes are kept of `total` over the threshold (`truncated`: total > max_boxes,
+    the first max_boxes in the decode kernel's order, which is np.argwhere's, are kept); bad = {'boxes': kept boxes without a crop
+    (class -1), 'frames': frames the resize refused}; image_indices int64 [n], boxes_xy float64 [n, 4] = (x1, y1, x2, y2) in frame
+    pixels, conf float32 [n], classes int64 [n], class_scores float32 [n]; record: the raw bytes all of it was read from."""
+
+    def __init__(self, record, max_boxes):
+        head, rec = unpack_record(record, max_boxes)
+        self.record = record
+        self.total, self.n = int(head['total']), int(head['kept'])
+        self.truncated = self.total > max_boxes
+        self.bad = {'boxes': int(head['crop_err']), 'frames': int(head['resize_err'])}
+        rec = rec[:self.n]
+        self.image_indices = rec['image'].astype(np.int64)
+        self.boxes_xy = np.ascontiguousarray(rec['xy'], dtype=np.float64).reshape(-1, 4)
+        self.conf = np.ascontiguousarray(rec['conf'], dtype=np.float32)
+        self.classes = rec['cls'].astype(np.int64)
+        self.class_scores = np.ascontiguousarray(rec['score'], dtype=np.float32)
+
+
+class _State(object):
+    """Every buffer of the pipeline for frames of one shape (n, H, W): nothing is allocated per call."""
+
+    def __init__(self, n, H, W, side, ci, K, has_cls, dev):
+        nbytes = n * H * W * 3
+        self.n, self.H, self.W, self.nbytes = n, H, W, nbytes
+        self.staging = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        self.staging_np = self.staging.numpy().reshape(n, H, W, 3)
+        self.frames = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self.off = (torch.arange(n, dtype=torch.int64) * (H * W * 3)).to(dev)
+        self.hw32 = torch.tensor([[H, W]] * n, dtype=torch.int32).to(dev)
+        self.hw64 = torch.tensor([[H, W]] * n, dtype=torch.int64).to(dev)
+        # the whole-frame resize in front of the detector: frame i, rectangle (0, H, 0, W)
+        self.frame_idx = torch.arange(n, dtype=torch.int32).to(dev)
+        self.frame_rect = torch.tensor([[0, H, 0, W]] * n, dtype=torch.int32).to(dev)
+        self.words = torch.zeros(4, dtype=torch.int32, device=dev)         # box count, crop error word, resize error word, unused
+        self.x_dark = torch.zeros((n, 3, side, side), dtype=torch.float32, device=dev)
+        self.box_img = torch.zeros(K, dtype=torch.int32, device=dev)
+        self.box_xy = torch.zeros((K, 4), dtype=torch.float64, device=dev)
+        self.box_conf = torch.zeros(K, dtype=torch.float32, device=dev)
+        self.box_cls = torch.zeros(K, dtype=torch.int32, device=dev) if has_cls else None
+        self.rect = torch.zeros((K, 4), dtype=torch.int32, device=dev)
+        self.crops = torch.zeros((K, 3, ci, ci), dtype=torch.float32, device=dev)
+        self.record = torch.zeros(record_bytes(K), dtype=torch.uint8, device=dev)
+        self.record_host = torch.zeros(record_bytes(K), dtype=torch.uint8).pin_memory()
+        self.done = torch.cuda.Event()
+        self.graph, self.graph_key, self.keep = None, None, None
+
+
+class SignDetector(object):
+    """det = SignDetector(dark_model, dark_params, class_model, class_params, max_boxes=16, conf_th=0.5, graph=False)
+    res = det.detect(frames)
+
+    dark_model: a DarkNet on the device (dark_params: darknet_input, n_grid, n_classes, capsule_input); class_model: CapsuleNet, or
+    the plain-torch ConvNet, on capsule_input x capsule_input crops.  The caller restores the checkpoints; both models are put in
+    eval mode and everything runs under no_grad.  frames: one HWC uint8 array, or a list / an [n, H, W, 3] array of frames of ONE size.
+    The buffers (and with graph=True the captured graph) are built per frame shape (n, H, W) on first use and kept.  The steps run
+    on torch's current stream; the call returns after the record has arrived (one event wait)."""
+
+    def __init__(self, dark_model, dark_params, class_model, class_params, max_boxes=16, conf_th=0.5, graph=False):
+        if int(max_boxes) != max_boxes or max_boxes < 1:
+            raise ValueError('max_boxes must be an integer >= 1, got %r' % (max_boxes,))
+        if not torch.cuda.is_available():
+            raise HipExtensionError('SignDetector needs the GPU: there is no CPU path')
+        self.dark, self.dark_params, self.cls, self.class_params = dark_model, dark_params, class_model, class_params
+        self.K, self.conf_th, self.use_graph = int(max_boxes), float(conf_th), bool(graph)
+        self.side, self.ci = int(dark_params.darknet_input), int(dark_params.capsule_input)
+        self.g, self.C = int(dark_params.n_grid), int(dark_params.n_classes)
+        self.dev = next(dark_model.parameters()).device
+        if self.dev.type != 'cuda' or next(class_model.parameters()).device != self.dev:
+            raise ValueError('both models must be on the same GPU; the detector is on %s' % (self.dev,))
+        for m in (dark_model, class_model):
+            if m.training:          # (a switch of mode starts a new fold-cache epoch, which would rebuild other detectors' captures)
+                m.eval()
+        self._tensors = [t for m in (dark_model, class_model) for t in list(m.parameters()) + list(m.buffers())]
+        self.states = {}
+
+    # ------------------------------------------------------------------------------------------------ frames
+    @staticmethod
+    def _frames(frames):
+        if isinstance(frames, np.ndarray) and frames.ndim == 3:
+            frames = [frames]
+        arrs = [np.asarray(f) for f in frames]
+        if not arrs:
+            raise ValueError('no frames')
+        for k, a in enumerate(arrs):
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise ValueError('frame %d: expected a uint8 array [H, W, 3], got %s %s' % (k, a.dtype, a.shape))
+            if a.shape != arrs[0].shape:
+                raise ValueError('frame %d is %d x %d, frame 0 is %d x %d: one call takes frames of one size'
+                                 % (k, a.shape[0], a.shape[1], arrs[0].shape[0], arrs[0].shape[1]))
+        return arrs
+
+    def _state(self, n, H, W):
+        key = (n, H, W)
+        if key not in self.states:
+            self.states[key] = _State(n, H, W, self.side, self.ci, self.K, self.C > 0, self.dev)
+        return self.states[key]
+
+    # ------------------------------------------------------------------------------------------------ the device steps
+    def _device_steps(self, st):
+        """Steps 2-7: everything between the frame upload and the record download, on the current stream, with no host
+        synchronisation.  Returns the tensors whose memory the record was computed from (a capture keeps them)."""
+        stream = torch.cuda.current_stream().cuda_stream
+        K = self.K
+        w = st.words.data_ptr()
+        st.words.zero_()
+        call('cy_crop_resize_u8', st.frames.data_ptr(), st.off.data_ptr(), st.hw32.data_ptr(), st.n, st.nbytes, st.frame_idx.data_ptr(),
+             st.frame_rect.data_ptr(), st.n, self.side, self.side, 0.0, 1.0, 1, st.x_dark.data_ptr(), w + 8, stream)
+        y = self.dark(st.x_dark).data
+        if y.dim() != 4 or y.shape[0] != st.n or y.shape[1] != self.g or y.shape[2] != self.g:
+            raise ValueError('the detector returned %s for %d frames on a %d x %d grid' % (tuple(y.shape), st.n, self.g, self.g))
+        D = int(y.shape[3])
+        nb = int((D - self.C) / 5)
+        if nb < 1:          # what utils.decode_boxes_device refuses
+            raise ValueError('y has %d values per cell: no box left after %d class scores (utils.py:291-293)' % (D, self.C))
+        y = y.to(dtype=torch.float32).contiguous()
+        call('cy_yolo_decode_boxes_conf', y.data_ptr(), st.hw64.data_ptr(), float(self.side), float(self.side), st.n, self.g, nb, self.C,
+             self.conf_th, w, st.box_img.data_ptr(), st.box_xy.data_ptr(), st.box_cls.data_ptr() if self.C else None,
+             st.box_conf.data_ptr(), K, stream)
+        call('cy_boxes_crop_resize_u8', st.frames.data_ptr(), st.off.data_ptr(), st.hw32.data_ptr(), st.n, st.nbytes, w,
+             st.box_img.data_ptr(), st.box_xy.data_ptr(), K, self.ci, self.ci, -128.0, 1.0 / 128.0, 1, st.crops.data_ptr(),
+             st.rect.data_ptr(), w + 4, stream)
+        scores = self.cls(st.crops).data.reshape(K, -1).to(dtype=torch.float32).contiguous()
+        call('cy_pack_detections', scores.data_ptr(), int(scores.shape[1]), w, st.box_img.data_ptr(), st.box_xy.data_ptr(),
+             st.box_conf.data_ptr(), st.rect.data_ptr(), w + 4, w + 8, K, st.record.data_ptr(), stream)
+        return y, scores
+
+    def _weights_key(self):
+        # the capture holds the folded eval weights (ops.fold_eval_bn): they are stale once ops' parameter epoch or a tensor's
+        # version counter has moved (load_state_dict, an optimizer step, a switch of mode)
+        return (ops.PARAM_EPOCH,) + tuple(t._version for t in self._tensors)
+
+    def _capture(self, st):
+        """GraphedStep's recipe: one eager pass on a side stream (fold caches, one-time kernel attributes, MIOpen's choices exist
+        before the capture begins), then steps 2-7 captured on one stream."""
+        st.graph, st.keep = None, None
+        side = torch.cuda.Stream(device=self.dev)
+        side.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(side):
+            self._device_steps(st)
+        torch.cuda.current_stream(self.dev).wait_stream(side)
+        torch.cuda.synchronize(self.dev)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            st.keep = self._device_steps(st)
+        st.graph, st.graph_key = graph, self._weights_key()
+
+    # ------------------------------------------------------------------------------------------------ the call
+    def detect(self, frames):
+        arrs = self._frames(frames)
+        H, W = arrs[0].shape[0:2]
+        st = self._state(len(arrs), H, W)
+        if self.dark.training or self.cls.training:
+            self.dark.eval()
+            self.cls.eval()
+        with torch.no_grad():
+            # the staging buffer is free: the previous call on this state waited for its record, which is behind its upload
+            for k, a in enumerate(arrs):
+                np.copyto(st.staging_np[k], a)
+            st.frames.copy_(st.staging, non_blocking=True)
+            if self.use_graph:
+                if st.graph is None or st.graph_key != self._weights_key():
+                    self._capture(st)
+                st.graph.replay()
+            else:
+                self._device_steps(st)
+            st.record_host.copy_(st.record, non_blocking=True)
+            st.done.record(torch.cuda.current_stream(self.dev))
+        st.done.synchronize()
+        return Detections(st.record_host.numpy().copy(), self.K)

@@ -522,6 +522,43 @@ int cy_yolo_decode_boxes_conf(const float* y, const long long* image_hw, double 
 int cy_confusion_sweep(const int* gt_key, const double* gt_xy, const float* gt_conf, int n_gt, const int* pr_key,
                        const double* pr_xy, const float* pr_conf, int n_pr, int n_groups, int C, const double* conf_ths, int K,
                        const double* iou_ths, int T, int max_per_group, int* out, int* err, void* stream);
+/* ------------------------------------------------------------------ streaming detector (csrc/serve.hip)
+ * The glue of serve.SignDetector: frame -> detector -> crops -> classifier -> labelled boxes with the box list read from device
+ * memory, so nothing between the two networks crosses to the host and every launch has a shape that depends on K alone.
+ *
+ * The rectangle rule of utils.crop_rectangles fused with the crop + resize above, for K slots.  imgs / img_off / img_hw / n_images /
+ * imgs_bytes, OH, OW, shift, scale, to_nchw and out are those of the crop + resize entry point; count[1], box_img[K] and
+ * box_xy[K][4] = (x1, y1, x2, y2) are what the decode kernel wrote (at least K entries long; *count may exceed K).  Slot s is
+ * live iff s < min(*count, K).  A live slot's rectangle is taken in double: the corners truncated towards zero, x clipped to
+ * [0, w] and y to [0, h] of image box_img[s], rect_out[s] = (y0, y1, x0, x1) half-open; its pixels are bit for bit those of the
+ * crop + resize entry point for that rectangle.  A live slot with a corner that is not finite, an image index outside
+ * 0..n_images-1 or an empty rectangle is BAD: zero-filled, rect_out[s] = (0, 0, 0, 0), *err (caller-zeroed) += 1; nothing
+ * else happens (one degenerate box must not stop a serving loop).  A dead slot is zero-filled with a zero rectangle and is not
+ * counted.  rect_out[K][4] is written for every slot.  K = 0 is valid and launches nothing. */
+int cy_boxes_crop_resize_u8(const unsigned char* imgs, const long long* img_off, const int* img_hw, int n_images,
+                            long long imgs_bytes, const int* count, const int* box_img, const double* box_xy, int K, int OH,
+                            int OW, float shift, float scale, int to_nchw, float* out, int* rect_out, int* err, void* stream);
+/* One record buffer for the host, filled in one launch behind the classifier: `record` (8-byte aligned) holds one
+ * cy_detections_header_t followed by K cy_detection_t, 16 + 48 K bytes, little-endian like the device. */
+typedef struct {
+  int total;        /* boxes over the threshold as the decode kernel counted them (may exceed K) */
+  int kept;         /* min(total, K): the records 0..kept-1 are boxes, the others are zeros with cls = -1 */
+  int crop_err;     /* bad slots counted by the box crop kernel */
+  int resize_err;   /* error word of the whole-frame resize in front of the detector */
+} cy_detections_header_t;
+typedef struct {
+  double xy[4];     /* x1, y1, x2, y2 in pixels of the frame, as decoded */
+  int image;        /* frame of the call the box belongs to */
+  int cls;          /* arg-max of the slot's class scores: the first maximum wins and a NaN counts as the maximum (np.argmax);
+                       -1 for a bad slot (rect = (0, 0, 0, 0)) */
+  float conf;       /* the detector's confidence */
+  float score;      /* scores[slot][cls]; 0 for a bad slot */
+} cy_detection_t;
+/* scores[K][C]: the classifier's output for the K crops; count, box_img, box_xy as above, conf[K] from the decode kernel,
+ * rect[K][4] = the crop kernel's rect_out; crop_err / resize_err: the two error words (NULL: 0 is recorded). */
+int cy_pack_detections(const float* scores, int C, const int* count, const int* box_img, const double* box_xy,
+                       const float* conf, const int* rect, const int* crop_err, const int* resize_err, int K, void* record,
+                       void* stream);
 /* ------------------------------------------------------------------ box drawing (csrc/draw.hip)
  * plot.draw_boxes (plot.py:24-33) for n boxes in one launch, IN PLACE in a packed buffer of n_images HWC uint8 images described
  * as for cy_crop_resize_u8 (imgs / img_off / img_hw / imgs_bytes); the caller draws into a copy if it still needs the images.

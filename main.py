@@ -22,6 +22,11 @@ recog_pr / recog_acc / recog_auc to metric_output.txt (main.py:309-317, 349-356)
 without `--combine` has always exited with a message for the detectors, and callers rely on that.  It writes detect_AP /
 detect_acc to metric_output.txt and the images with the predictions in green and the ground truth in red, drawn on the device, to
 <model_dir>/output/<i>.ppm (see detect()).  The metric curves are not plotted.
+``--mode serve --model darknet_d|darknet_r --combine cnn|capsule --restore last|best [--synthetic N] [--graph] [--max_boxes K]``
+(new) restores both checkpoints once and pushes the test frames one at a time through the streaming detector
+(capsyolo_amd.serve.SignDetector: frame in, labelled boxes out, nothing crosses to the host between the two networks; ``--graph``
+replays a captured HIP graph per frame shape).  It writes one line per frame to <model_dir>/serve_output.txt and prints the
+latency percentiles (see serve()).
 ``--mode interpret --model capsule --restore last|best [--synthetic N] [--index I]`` is the reference's capsule_interpret.py:
 the 16 x 11 perturbation sweep of sample I's labelled capsule through the fused decoder kernel, written to <model_dir>/img/
 (see interpret()).
@@ -62,7 +67,7 @@ from capsyolo_amd.predict_fns import class_pred, class_scores_device, dark_class
 
 parser = argparse.ArgumentParser()
 parser.add_argument('--model', default='cnn', help=' | '.join(config.model_names))
-parser.add_argument('--mode', default='train', help='train | predict | detect | overfit | interpret')
+parser.add_argument('--mode', default='train', help='train | predict | detect | serve | overfit | interpret')
 parser.add_argument('--summary', default=True, help='if summarize model', action='store_true')
 parser.add_argument('--seed', type=int, default=0, help='random seed')
 parser.add_argument('--lr', type=float, default=1e-3, help='learning rate')
@@ -86,13 +91,16 @@ parser.add_argument('--n_epochs', type=int, default=0, help='override params.jso
 parser.add_argument('--batch_size', type=int, default=0, help='override params.json batch_size')
 parser.add_argument('--graph', action='store_true',
                     help='capture the training step (forward + loss + backward + Adam) once in a HIP graph and replay it per batch: '
-                         'for the launch-bound small models (capsule); single process only')
+                         'for the launch-bound small models (capsule); single process only.  --mode serve: capture the '
+                         'detector -> classifier chain once per frame shape')
 parser.add_argument('--augment', action='store_true',
                     help='--mode train of a detector: paste GTSRB signs over the raw frames on the device, fresh for every batch')
 parser.add_argument('--class_augment', action='store_true',
                     help='--mode train|overfit of a classifier (cnn | capsule): shift and lightness jitter per sample and epoch, '
                          'made on the device from the resident training set')
 parser.add_argument('--gtsrb', default=config.GTSRB, help='--augment: the GTSRB root whose Images/ are the signs to paste')
+parser.add_argument('--max_boxes', type=int, default=16,
+                    help='--mode serve: box slots per call (the classifier always runs on this many crops; further boxes are dropped)')
 parser.add_argument('--fix_ckpt_dir', action='store_true',
                     help='save checkpoints into model_dir (where --restore reads) instead of model_dir + str(train_frac)')
 
@@ -445,6 +453,17 @@ def predict_class(args, model, model_dir, data_dir, params):
     return metric_out
 
 
+def _combined_classifier(args, model_dir):
+    """The classifier behind --combine: (model, its directory, its params).  The directory is config.model_dir[--combine] or, with
+    --model_dir, the detector directory's sibling <model_dir>/../<name>."""
+    class_model_dir = config.model_dir[args.combine] if args.model_dir is None else \
+        os.path.join(os.path.dirname(os.path.abspath(model_dir)), args.combine)
+    class_args = argparse.Namespace(**dict(vars(args), model=args.combine))
+    class_params = load_params(class_model_dir, class_args)
+    class_model = model_loss_predict[args.combine][0](class_params).to(device=class_params.device)
+    return class_model, class_model_dir, class_params
+
+
 def predict(args, model, model_dir, data_dir, params):
     """main.py:293-356: `--model cnn|capsule` is the class-only branch (predict_class).  The combined branch,
     `--model darknet_d|darknet_r --combine cnn|capsule --restore last|best`, runs
@@ -461,11 +480,7 @@ def predict(args, model, model_dir, data_dir, params):
     if args.model not in ('darknet_d', 'darknet_r') or args.combine not in ('cnn', 'capsule'):
         raise SystemExit('predict mode runs --model cnn|capsule, or the combined chain --model darknet_d|darknet_r --combine '
                          'cnn|capsule; the detect-only branch of --model darknet_d|darknet_r is --mode detect')
-    class_model_dir = config.model_dir[args.combine] if args.model_dir is None else \
-        os.path.join(os.path.dirname(os.path.abspath(model_dir)), args.combine)
-    class_args = argparse.Namespace(**dict(vars(args), model=args.combine))
-    class_params = load_params(class_model_dir, class_args)
-    class_model = model_loss_predict[args.combine][0](class_params).to(device=class_params.device)
+    class_model, class_model_dir, class_params = _combined_classifier(args, model_dir)
     if args.synthetic:
         x = synth.raw_images(args.synthetic)
         y = synth.gtsdb_labels(args.synthetic, params.n_grid, 43)
@@ -525,6 +540,64 @@ def detect(args, model, model_dir, data_dir, params):
     return metric_out
 
 
+def check_serve(args):
+    """The refusals of --mode serve that need neither the data nor a device."""
+    if args.model not in ('darknet_d', 'darknet_r') or args.combine not in ('cnn', 'capsule'):
+        raise SystemExit('serve mode runs the two-stage chain: --model darknet_d|darknet_r --combine cnn|capsule')
+    if args.restore is None:
+        raise SystemExit('Must give restore file last/best')
+    if args.max_boxes < 1:
+        raise SystemExit('--max_boxes %d: at least one box slot' % args.max_boxes)
+
+
+def serve(args, model, model_dir, data_dir, params):
+    """`--mode serve`: both checkpoints are restored ONCE, then the frames (`--synthetic N`: synth.raw_images, frames of different
+    sizes; otherwise data_dir/test_images.npy as in predict mode) go through serve.SignDetector one at a time, each call returning
+    the frame's labelled boxes.  Per frame one line (size, boxes kept / found, the boxes' classes) is printed and written to
+    <model_dir>/serve_output.txt; at the end the totals and the latency p50 / p90 / max over the frames whose shape had been seen
+    before (the first frame of a shape also builds that shape's buffers and, with --graph, its capture) are printed.  Returns the
+    totals as a dict."""
+    import time
+    from capsyolo_amd.serve import SignDetector
+    check_serve(args)
+    if params.device != 'cuda':
+        raise SystemExit('serve mode runs on hand-written gfx950 kernels only; no GPU is visible')
+    class_model, class_model_dir, class_params = _combined_classifier(args, model_dir)
+    for m, d, p in ((model, model_dir, params), (class_model, class_model_dir, class_params)):
+        path = os.path.join(d, args.restore + '.pth.tar')
+        print("Restoring parameters from {}".format(path))
+        utils.load_checkpoint(path, m, p)
+    if args.synthetic:
+        frames = synth.raw_images(args.synthetic)
+    else:
+        frames = list(np.load(data_dir + '/test_images.npy', allow_pickle=True))
+    det = SignDetector(model, params, class_model, class_params, max_boxes=args.max_boxes, graph=args.graph)
+    seen, ms = set(), []
+    out = dict(frames=0, boxes=0, truncated=0, bad_boxes=0)
+    with open(os.path.join(model_dir, 'serve_output.txt'), 'w') as text_file:
+        for i, frame in enumerate(frames):
+            frame = np.asarray(frame)
+            t0 = time.perf_counter()
+            res = det.detect(frame)
+            dt = (time.perf_counter() - t0) * 1e3
+            if frame.shape in seen:
+                ms.append(dt)
+            seen.add(frame.shape)
+            line = 'frame {}: {}x{} | boxes: {} of {} | classes: {}'.format(i, frame.shape[0], frame.shape[1], res.n, res.total,
+                                                                          ' '.join(str(c) for c in res.classes))
+            print(line)
+            text_file.write(line + '\n')
+            out['frames'] += 1
+            out['boxes'] += res.n
+            out['truncated'] += int(res.truncated)
+            out['bad_boxes'] += res.bad['boxes']
+    lat = np.percentile(ms, [50, 90, 100]) if ms else [float('nan')] * 3
+    out.update(latency_frames=len(ms), p50_ms=float(lat[0]), p90_ms=float(lat[1]), max_ms=float(lat[2]))
+    print('frames: {} | boxes: {} | truncated frames: {} | bad boxes: {} | latency over {} frames of a seen shape: p50 {:.3f} ms, '
+          'p90 {:.3f} ms, max {:.3f} ms'.format(out['frames'], out['boxes'], out['truncated'], out['bad_boxes'], len(ms), *lat))
+    return out
+
+
 def interpret(args, model, model_dir, data_dir, params):
     """capsule_interpret.py:27-68 as a mode: restore the checkpoint, take sample --index of the eval set (data_dir/eval.p, or of
     `--synthetic N` samples), and write into <model_dir>/img/ the sample (orig.ppm), the 16 x 11 reconstructions <v>-<i>.ppm of its
@@ -569,6 +642,8 @@ def main(argv=None):
         sys.exit()
     if args.class_augment:
         check_class_augment(args)
+    if args.mode == 'serve':
+        check_serve(args)
     data_dir, model_dir = config.data_dir[args.model], config.model_dir[args.model]
     if args.model_dir is not None:
         model_dir = args.model_dir
@@ -620,6 +695,8 @@ def main(argv=None):
         return predict(args, model, model_dir, data_dir, params)
     if args.mode == 'detect':
         return detect(args, model, model_dir, data_dir, params)
+    if args.mode == 'serve':
+        return serve(args, model, model_dir, data_dir, params)
     if args.mode == 'interpret':
         return interpret(args, model, model_dir, data_dir, params)
 

@@ -1,0 +1,91 @@
+#!/usr/bin/env python
+"""Latency of one camera frame through detector + classifier: the existing two-stage chain against serve.SignDetector.
+
+    python tools/bench_serve.py [--reps 100] [--warmup 10] [--height 800] [--width 1360] [--max_boxes 16]
+
+Default-initialised DarkNet (448 x 448 input, 14 x 14 grid, 2 boxes, no classes) and CapsuleNet (43 classes, 32 x 32 crops), one
+synthetic frame of the GTSDB size, a confidence threshold chosen between two of the detector's own confidences so that 1..max_boxes
+boxes pass.  Prints one JSON line with the median wall milliseconds per frame (host clock around the call, a device synchronisation at
+the end of every call, `reps` calls after `warmup`) of
+  chain_ms   predict_fns._detect_and_crop + the classifier's forward + np.argmax on one frame: the chain of dark_class_pred as it
+             stands, without its checkpoint restores (upload, host hops for the box count / rectangles / error word included)
+  eager_ms   SignDetector.detect, graph=False
+  graph_ms   SignDetector.detect, graph=True (one replay per frame)
+and the box count, so that the three are seen to do the same work."""
+import argparse
+import json
+import os
+import sys
+import time
+import types
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import capsyolo_amd  # noqa: E402,F401
+from capsyolo_amd import models, predict_fns, serve, synth  # noqa: E402
+
+
+def _median_ms(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ms)), float(np.min(ms))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=100)
+    ap.add_argument('--warmup', type=int, default=10)
+    ap.add_argument('--height', type=int, default=800)
+    ap.add_argument('--width', type=int, default=1360)
+    ap.add_argument('--max_boxes', type=int, default=16)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_serve needs a GPU')
+    if a.reps < 50:
+        raise SystemExit('--reps %d: a median over fewer than 50 calls is not reported' % a.reps)
+    K = a.max_boxes
+    dp = types.SimpleNamespace(model='darknet_d', n_classes=0, n_grid=14, n_boxes=2, darknet_input=448, capsule_input=32, dropout=0.0,
+                               device='cuda')
+    cp = types.SimpleNamespace(model='capsule', n_classes=43, device='cuda')
+    torch.manual_seed(0)
+    dark, caps = models.DarkNet(dp).cuda().eval(), models.CapsuleNet(cp).cuda().eval()
+    side = max(a.height, a.width)
+    frame = np.ascontiguousarray(synth.raw_images(1, seed=7, min_side=side, max_side=side)[0][:a.height, :a.width])
+
+    with torch.no_grad():
+        y = dark(predict_fns.PackedImages([frame]).resize(448, to_nchw=True)).data
+    conf = np.unique(y[..., 0::5].cpu().numpy())[::-1].astype(np.float64)
+    k = min(K // 2, len(conf) - 1)
+    conf_th = float(conf[k - 1] + conf[k]) / 2 if k >= 1 else float(conf[0]) - 1e-3
+
+    def chain():
+        _, crops, idx, xy = predict_fns._detect_and_crop([frame], dark, dp, conf_th, 1, 32, -128.0, 1.0 / 128.0, True)
+        with torch.no_grad():
+            scores = caps(crops).data.reshape(len(idx), -1)
+        return idx, xy, np.argmax(scores.cpu().numpy(), axis=1)
+
+    n_chain = len(chain()[0])
+    if not 1 <= n_chain <= K:
+        raise SystemExit('the threshold %.9g lets %d boxes through, wanted 1..%d' % (conf_th, n_chain, K))
+    chain_ms, chain_min = _median_ms(chain, a.reps, a.warmup)
+    out = {'frame': [a.height, a.width], 'max_boxes': K, 'boxes': n_chain, 'reps': a.reps, 'chain_ms': chain_ms, 'chain_min_ms': chain_min}
+    for key, graph in (('eager', False), ('graph', True)):
+        det = serve.SignDetector(dark, dp, caps, cp, max_boxes=K, conf_th=conf_th, graph=graph)
+        res = det.detect(frame)
+        if res.n != n_chain or res.bad['boxes']:
+            raise SystemExit('SignDetector (graph=%s) kept %d boxes (%d bad), the chain %d' % (graph, res.n, res.bad['boxes'], n_chain))
+        out[key + '_ms'], out[key + '_min_ms'] = _median_ms(lambda: det.detect(frame), a.reps, a.warmup)
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
