@@ -6,6 +6,7 @@
 //   yolo_decode_conf_kernel   utils.y_to_boxes_vec (utils.py:288-334) that also returns each box's confidence
 //   confusion_sweep_kernel    metrics.single_img_confusion for every (group, confidence threshold, IoU threshold) at once
 #include "common.h"
+#include "box_iou.h"
 #include "crop_pixel.h"
 
 // the double arithmetic below restates numpy expressions operation by operation: no fused multiply-add
@@ -138,15 +139,6 @@ __device__ __forceinline__ int lower_bound_key(const int* __restrict__ key, int 
   int lo = 0, hi = n;
   while (lo < hi) { const int mid = (lo + hi) >> 1; if (key[mid] < v) lo = mid + 1; else hi = mid; }
   return lo;
-}
-
-// IoU of metrics.calc_iou_individual (metrics.py:121-133) with its early-out; a = ground truth, p = prediction
-__device__ __forceinline__ double box_iou(const double* a, const double* p) {
-  const double x1t = a[0], y1t = a[1], x2t = a[2], y2t = a[3];
-  const double x1p = p[0], y1p = p[1], x2p = p[2], y2p = p[3];
-  if (x2t < x1p || x2p < x1t || y2t < y1p || y2p < y1t) return 0.0;
-  const double inter = (fmin(x2t, x2p) - fmax(x1t, x1p)) * (fmin(y2t, y2p) - fmax(y1t, y1p));
-  return inter / ((x2t - x1t) * (y2t - y1t) + (x2p - x1p) * (y2p - y1p) - inter);
 }
 
 // The whole threshold sweep of detect_and_recog_mAP / detect_AP in one launch.  The reference decodes both arrays again for

@@ -120,20 +120,26 @@ def _chunk_size(n, batch_size):
     return max(int(batch_size) if batch_size else n, 1)
 
 
-def _detect_and_crop(images, model, params, conf_th, batch_size, crop_side, shift, scale, to_nchw, drawer=None):
+def _detect_and_crop(images, model, params, conf_th, batch_size, crop_side, shift, scale, to_nchw, drawer=None, nms=None):
     """Chunks of `batch_size` images: upload -> resize -> eval forward -> decode with the images' own sizes -> rectangles ->
     crops, all but the rectangle rule (a few integers per box, in double on the host) on the device.
     Returns (y_hat device [B,g,g,D], crops device, image_indices int64 numpy, boxes_xy float64 numpy).  drawer (optional):
     called as drawer(lo, packed, image_indices, boxes_xy, classes) with every chunk's boxes (indices inside the chunk, classes an
-    int64 numpy array or None) while its packed images are on the device."""
+    int64 numpy array or None) while its packed images are on the device.  nms (optional): (iou_th, class_aware); every chunk's
+    y_hat goes through utils.nms_y_hat_device with the chunk's image sizes before the decode, so the boxes, the crops, what the
+    drawer sees and the returned y_hat are those of the survivors; one line says how many boxes over conf_th that removed."""
     n = len(images)
     bs = _chunk_size(n, batch_size)
     y_hats, crops, idxs, xys = [], [], [], []
+    before = 0
     model.eval()
     with torch.no_grad():
         for lo in range(0, n, bs):
             packed = PackedImages(images[lo:lo + bs], params.device)
             y_hat = model(packed.resize(int(params.darknet_input), to_nchw=True)).data
+            if nms is not None:
+                before += utils.decode_boxes_device(y_hat, params, packed.hw, conf_th)[0]
+                y_hat = utils.nms_y_hat_device(y_hat, params, nms[0], nms[1], 0, packed.hw)
             nbox, idx, xy, cls = utils.decode_boxes_device(y_hat, params, packed.hw, conf_th)
             idx_np, xy_np = idx.cpu().numpy().astype(np.int64), xy.cpu().numpy()
             if drawer is not None:
@@ -146,17 +152,39 @@ def _detect_and_crop(images, model, params, conf_th, batch_size, crop_side, shif
             y_hats.append(y_hat)
             idxs.append(idx_np + lo)
             xys.append(xy_np)
+    if nms is not None:
+        after = sum(len(i) for i in idxs)
+        print('nms (iou > {}{}): {} of {} boxes over {} suppressed'.format(nms[0], ', per class' if nms[1] else '', before - after, before,
+                                                                           conf_th))
     return torch.cat(y_hats, 0), torch.cat(crops, 0), np.concatenate(idxs), np.concatenate(xys, 0)
 
 
-def dark_pred(images, model, model_dir, params, restore_file, is_end=True, conf_th=0.5, y=None, batch_size=32, draw=False):
+def _nms_option(nms_iou, nms_class_aware, params):
+    """None, or the checked (iou_th, class_aware) that _detect_and_crop takes."""
+    if nms_iou is None:
+        if nms_class_aware:
+            raise ValueError('nms_class_aware needs nms_iou')
+        return None
+    if not (0.0 <= float(nms_iou) <= 1.0):
+        raise ValueError('nms_iou must be in [0, 1], got %r' % (nms_iou,))
+    if nms_class_aware and int(params.n_classes) == 0:
+        raise ValueError('nms_class_aware needs a detector with class scores (params.n_classes > 0)')
+    return float(nms_iou), bool(nms_class_aware)
+
+
+def dark_pred(images, model, model_dir, params, restore_file, is_end=True, conf_th=0.5, y=None, batch_size=32, draw=False, nms_iou=None,
+              nms_class_aware=False):
     """predict_fns.py:10-58.  images: list of HWC uint8 arrays of different sizes.  is_end=True: (y_hat, None), or with draw=True
     (new, optional) (y_hat, images): the reference's second value, copies of the images with the boxes over conf_th in green,
     labelled with the detector's argmax class when params.n_classes > 0, and, when the labels y [n, g, g, 5 + C] are given, the
     ground-truth boxes in red on top (predict_fns.py:46-51; decoded like the predictions, so from float32 values).  Both sets
     are drawn in one launch per chunk, ground truth last (draw.draw_boxes_device).  Without draw, y is not read.
     is_end=False: (y_hat, crops float32 numpy [n_boxes, ci, ci, 3] on the raw 0..255 scale like the reference,
-    image_indices [n_boxes], boxes_xy [n_boxes, 4] in pixels of the original images)."""
+    image_indices [n_boxes], boxes_xy [n_boxes, 4] in pixels of the original images).
+    nms_iou (new, optional): non-maximum suppression at this IoU (utils.nms_y_hat_device; nms_class_aware: per arg-max class of the
+    detector) before decode, crops and drawing; the returned y_hat has the confidence of every suppressed box set to 0.  None: no
+    suppression, the reference's behaviour."""
+    nms = _nms_option(nms_iou, nms_class_aware, params)
     _restore(model, model_dir, params, restore_file)
     ci = int(params.capsule_input)
     drawn = []
@@ -172,25 +200,28 @@ def dark_pred(images, model, model_dir, params, restore_file, is_end=True, conf_
             colors = np.concatenate([colors, np.tile(np.array(box_draw.RED, dtype=np.uint8), (len(idx) - len(colors), 1))])
         drawn.extend(box_draw.unpack_images(box_draw.draw_boxes_device(packed, idx, xy, colors, cls), packed))
     want = bool(draw) and is_end
-    y_hat, crops, idx, xy = _detect_and_crop(images, model, params, conf_th, batch_size, ci, 0.0, 1.0, False, drawer if want else None)
+    y_hat, crops, idx, xy = _detect_and_crop(images, model, params, conf_th, batch_size, ci, 0.0, 1.0, False, drawer if want else None, nms)
     if is_end:
         return y_hat.cpu().numpy(), (drawn if want else None)
     return y_hat.cpu().numpy(), crops.cpu().numpy(), idx, xy
 
 
 def dark_class_pred(images, dark_model, dark_model_dir, dark_params, class_model, class_model_dir, class_params, restore_file,
-                    batch_size=32, conf_th=0.5, draw=False):
+                    batch_size=32, conf_th=0.5, draw=False, nms_iou=None, nms_class_aware=False):
     """predict_fns.py:75-82: detector -> crop of every box -> classifier -> utils.combine_y_hat.  Returns (y_hat float64 numpy
     [B, g, g, D + n_classes], None), or with draw=True (new, optional) (y_hat, images): the reference's second value, copies of
     the images with every box in green, labelled with the CLASSIFIER's argmax (predict_fns.py:80).  The classifier runs after the
     last detection chunk, so drawing walks the chunks a second time (upload, draw, download) and holds one chunk's images at a
     time; y_hat does not depend on it.  The crops are produced
     already centred ((v - 128) / 128, utils.center_rgb) in the classifier's NCHW layout and never leave the device.  No box over
-    conf_th (new, optional; the reference's dark_pred default 0.5) is a valid outcome: the class part stays zero."""
+    conf_th (new, optional; the reference's dark_pred default 0.5) is a valid outcome: the class part stays zero.
+    nms_iou / nms_class_aware (new, optional): as in dark_pred -- the detector's y_hat is suppressed before the decode, so only the
+    survivors are cropped, classified, combined and drawn, and the detector part of the returned y_hat is the masked one."""
+    nms = _nms_option(nms_iou, nms_class_aware, dark_params)
     _restore(dark_model, dark_model_dir, dark_params, restore_file)
     _restore(class_model, class_model_dir, class_params, restore_file)
     ci = int(dark_params.capsule_input)
-    dark_y_hat, crops, idx, xy = _detect_and_crop(images, dark_model, dark_params, conf_th, batch_size, ci, -128.0, 1.0 / 128.0, True)
+    dark_y_hat, crops, idx, xy = _detect_and_crop(images, dark_model, dark_params, conf_th, batch_size, ci, -128.0, 1.0 / 128.0, True, None, nms)
     n = int(crops.shape[0])
     n_classes = int(class_params.n_classes)
     class_model.eval()

@@ -40,7 +40,10 @@ class Detections(object):
     """What one `SignDetector.detect` call found.  n boxes are kept of `total` over the threshold (`truncated`: total > max_boxes,
     the first max_boxes in the decode kernel's order, which is np.argwhere's, are kept); bad = {'boxes': kept boxes without a crop
     (class -1), 'frames': frames the resize refused}; image_indices int64 [n], boxes_xy float64 [n, 4] = (x1, y1, x2, y2) in frame
-    pixels, conf float32 [n], classes int64 [n], class_scores float32 [n]; record: the raw bytes all of it was read from."""
+    pixels, conf float32 [n], classes int64 [n], class_scores float32 [n]; record: the raw bytes all of it was read from.
+    From a detector built with nms_iou the record has the same layout, but `total` is the number of boxes that survived the
+    suppression step (all boxes over the threshold take part in it, however many), and the boxes come image ascending and inside an
+    image confidence descending: a truncated result then holds the most confident survivors of the first images."""
 
     def __init__(self, record, max_boxes):
         head, rec = unpack_record(record, max_boxes)
@@ -83,25 +86,56 @@ class _State(object):
         self.record_host = torch.zeros(record_bytes(K), dtype=torch.uint8).pin_memory()
         self.done = torch.cuda.Event()
         self.graph, self.graph_key, self.keep = None, None, None
+        self.cand = None        # with nms_iou: the candidate list in front of the suppression step (_Candidates, built on first use)
+
+
+class _Candidates(object):
+    """The decode kernel's whole output for one frame shape, cap = n g^2 n_boxes entries, and what `cy_nms_boxes` needs beside it."""
+
+    def __init__(self, cap, n, K, has_cls, dev):
+        self.cap = cap
+        self.img = torch.zeros(cap, dtype=torch.int32, device=dev)
+        self.xy = torch.zeros((cap, 4), dtype=torch.float64, device=dev)
+        self.conf = torch.zeros(cap, dtype=torch.float32, device=dev)
+        self.cls = torch.zeros(cap, dtype=torch.int32, device=dev) if has_cls else None
+        self.keep = torch.zeros(cap, dtype=torch.int32, device=dev)
+        self.src = torch.zeros(K, dtype=torch.int32, device=dev)            # the survivors' positions in the list
+        self.words = torch.zeros(2 + n, dtype=torch.int32, device=dev)      # candidate count, error word, per-image scratch
 
 
 class SignDetector(object):
-    """det = SignDetector(dark_model, dark_params, class_model, class_params, max_boxes=16, conf_th=0.5, graph=False)
+    """det = SignDetector(dark_model, dark_params, class_model, class_params, max_boxes=16, conf_th=0.5, graph=False,
+                        nms_iou=None, nms_class_aware=False, per_frame=0)
     res = det.detect(frames)
 
     dark_model: a DarkNet on the device (dark_params: darknet_input, n_grid, n_classes, capsule_input); class_model: CapsuleNet, or
     the plain-torch ConvNet, on capsule_input x capsule_input crops.  The caller restores the checkpoints; both models are put in
     eval mode and everything runs under no_grad.  frames: one HWC uint8 array, or a list / an [n, H, W, 3] array of frames of ONE size.
     The buffers (and with graph=True the captured graph) are built per frame shape (n, H, W) on first use and kept.  The steps run
-    on torch's current stream; the call returns after the record has arrived (one event wait)."""
+    on torch's current stream; the call returns after the record has arrived (one event wait).
+    nms_iou (optional): non-maximum suppression between the decode and the crops (`cy_nms_boxes`, the rule is in
+    include/capsyolo_hip.h): ALL boxes over conf_th are decoded, and the max_boxes slots take the survivors, most confident first,
+    at most per_frame of a frame (0: no cap); nms_class_aware suppresses only inside the detector's own arg-max class and needs a
+    detector with class scores.  None: no such step, the first max_boxes boxes in decode order as before."""
 
-    def __init__(self, dark_model, dark_params, class_model, class_params, max_boxes=16, conf_th=0.5, graph=False):
+    def __init__(self, dark_model, dark_params, class_model, class_params, max_boxes=16, conf_th=0.5, graph=False, nms_iou=None,
+                 nms_class_aware=False, per_frame=0):
         if int(max_boxes) != max_boxes or max_boxes < 1:
             raise ValueError('max_boxes must be an integer >= 1, got %r' % (max_boxes,))
+        if nms_iou is not None and not (0.0 <= float(nms_iou) <= 1.0):
+            raise ValueError('nms_iou must be in [0, 1], got %r' % (nms_iou,))
+        if int(per_frame) != per_frame or per_frame < 0:
+            raise ValueError('per_frame must be an integer >= 0, got %r' % (per_frame,))
+        if nms_iou is None and (nms_class_aware or per_frame):
+            raise ValueError('nms_class_aware and per_frame belong to the suppression step: give nms_iou')
+        if nms_class_aware and int(dark_params.n_classes) == 0:
+            raise ValueError('nms_class_aware needs a detector with class scores (n_classes > 0)')
         if not torch.cuda.is_available():
             raise HipExtensionError('SignDetector needs the GPU: there is no CPU path')
         self.dark, self.dark_params, self.cls, self.class_params = dark_model, dark_params, class_model, class_params
         self.K, self.conf_th, self.use_graph = int(max_boxes), float(conf_th), bool(graph)
+        self.nms_iou = None if nms_iou is None else float(nms_iou)
+        self.nms_class_aware, self.per_frame = bool(nms_class_aware), int(per_frame)
         self.side, self.ci = int(dark_params.darknet_input), int(dark_params.capsule_input)
         self.g, self.C = int(dark_params.n_grid), int(dark_params.n_classes)
         self.dev = next(dark_model.parameters()).device
@@ -153,9 +187,26 @@ class SignDetector(object):
         if nb < 1:          # what utils.decode_boxes_device refuses
             raise ValueError('y has %d values per cell: no box left after %d class scores (utils.py:291-293)' % (D, self.C))
         y = y.to(dtype=torch.float32).contiguous()
-        call('cy_yolo_decode_boxes_conf', y.data_ptr(), st.hw64.data_ptr(), float(self.side), float(self.side), st.n, self.g, nb, self.C,
-             self.conf_th, w, st.box_img.data_ptr(), st.box_xy.data_ptr(), st.box_cls.data_ptr() if self.C else None,
-             st.box_conf.data_ptr(), K, stream)
+        if self.nms_iou is None:
+            call('cy_yolo_decode_boxes_conf', y.data_ptr(), st.hw64.data_ptr(), float(self.side), float(self.side), st.n, self.g, nb, self.C,
+                 self.conf_th, w, st.box_img.data_ptr(), st.box_xy.data_ptr(), st.box_cls.data_ptr() if self.C else None,
+                 st.box_conf.data_ptr(), K, stream)
+        else:
+            # every box over the threshold into the candidate list, the survivors into the K slots, their number into the count word
+            per_image = self.g * self.g * nb
+            if st.cand is None or st.cand.cap != st.n * per_image:          # (first use: the eager pass in front of a capture)
+                st.cand = _Candidates(st.n * per_image, st.n, K, self.C > 0, self.dev)
+            c = st.cand
+            c.words.zero_()
+            cw = c.words.data_ptr()
+            call('cy_yolo_decode_boxes_conf', y.data_ptr(), st.hw64.data_ptr(), float(self.side), float(self.side), st.n, self.g, nb, self.C,
+                 self.conf_th, cw, c.img.data_ptr(), c.xy.data_ptr(), c.cls.data_ptr() if self.C else None, c.conf.data_ptr(), c.cap,
+                 stream)
+            # (the error word cannot fire: an image has at most per_image candidates, and that is the capacity asked for)
+            call('cy_nms_boxes', cw, c.img.data_ptr(), c.xy.data_ptr(), c.conf.data_ptr(), c.cls.data_ptr() if self.C else None, c.cap,
+                 st.n, self.nms_iou, int(self.nms_class_aware), self.per_frame, per_image, c.keep.data_ptr(), K, st.box_img.data_ptr(),
+                 st.box_xy.data_ptr(), st.box_conf.data_ptr(), st.box_cls.data_ptr() if self.C else None, c.src.data_ptr(), w, cw + 8,
+                 cw + 4, stream)
         call('cy_boxes_crop_resize_u8', st.frames.data_ptr(), st.off.data_ptr(), st.hw32.data_ptr(), st.n, st.nbytes, w,
              st.box_img.data_ptr(), st.box_xy.data_ptr(), K, self.ci, self.ci, -128.0, 1.0 / 128.0, 1, st.crops.data_ptr(),
              st.rect.data_ptr(), w + 4, stream)

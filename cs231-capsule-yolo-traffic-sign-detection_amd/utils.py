@@ -109,6 +109,108 @@ def decode_boxes_device(y, params, image_hw=None, conf_th=0.5, with_conf=False):
     return n, idx[:n], xy[:n], (cls[:n] if C else None)
 
 
+def _nms_call(count, idx, xy, conf, cls, n_cap, n_images, iou_th, class_aware, per_image, max_per_image, K):
+    """`cy_nms_boxes` on a device list (count: int32 [1] device tensor): (keep int32 [n_cap], out_img, out_xy, out_conf, out_cls | None,
+    out_src, words int32 [2] = (survivors, error word)), all on the device, nothing read back."""
+    from ._lib import call
+    dev = idx.device
+    keep = torch.zeros(max(n_cap, 1), dtype=torch.int32, device=dev)
+    out_img = torch.zeros(max(K, 1), dtype=torch.int32, device=dev)
+    out_xy = torch.zeros((max(K, 1), 4), dtype=torch.float64, device=dev)
+    out_conf = torch.zeros(max(K, 1), dtype=torch.float32, device=dev)
+    out_cls = torch.zeros(max(K, 1), dtype=torch.int32, device=dev) if cls is not None else None
+    out_src = torch.zeros(max(K, 1), dtype=torch.int32, device=dev)
+    words = torch.zeros(2 + n_images, dtype=torch.int32, device=dev)       # survivors, error word, per-image scratch
+    call('cy_nms_boxes', count.data_ptr(), idx.data_ptr(), xy.data_ptr(), conf.data_ptr(), cls.data_ptr() if cls is not None else None,
+         int(n_cap), int(n_images), float(iou_th), int(bool(class_aware)), int(per_image), int(max_per_image), keep.data_ptr(), int(K),
+         out_img.data_ptr(), out_xy.data_ptr(), out_conf.data_ptr(), out_cls.data_ptr() if cls is not None else None,
+         out_src.data_ptr(), words.data_ptr(), words.data_ptr() + 8, words.data_ptr() + 4, torch.cuda.current_stream().cuda_stream)
+    return keep[:n_cap], out_img[:K], out_xy[:K], out_conf[:K], (out_cls[:K] if cls is not None else None), out_src[:K], words[:2]
+
+
+def _check_nms_args(iou_th, per_image):
+    if not (0.0 <= float(iou_th) <= 1.0):
+        raise ValueError('iou_th must be in [0, 1], got %r' % (iou_th,))
+    if int(per_image) != per_image or per_image < 0:
+        raise ValueError('per_image must be an integer >= 0, got %r' % (per_image,))
+
+
+def nms_boxes_device(image_indices, boxes_xy, conf, classes=None, iou_th=0.45, class_aware=False, per_image=0, n_images=None,
+                     max_out=None):
+    """Greedy confidence-ordered non-maximum suppression of a decoded box list on the device (`cy_nms_boxes`; the rule is in
+    include/capsyolo_hip.h).  image_indices [n] ascending, boxes_xy [n, 4] = (x1, y1, x2, y2), conf [n], classes [n] or None: arrays
+    or tensors, e.g. what decode_boxes_device(..., with_conf=True) returned.  n_images: default max(image_indices) + 1; max_out:
+    output slots, default n.  Returns (n_kept, idx int32, xy float64, conf float32, cls int32 | None, src int32, keep int32 [n]) as
+    device tensors: the survivors, image ascending and inside an image confidence descending (src: their positions in the input;
+    min(n_kept, max_out) of them are returned), and the keep mask in input order.  The one-shot form: it reads the count back."""
+    from ._lib import query
+    _check_nms_args(iou_th, per_image)
+    if class_aware and classes is None:
+        raise ValueError('class_aware suppression needs the classes')
+
+    def dev_t(a, dtype):
+        return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).to(device='cuda', dtype=dtype).contiguous()
+    idx = dev_t(image_indices, torch.int32).reshape(-1)
+    xy = dev_t(boxes_xy, torch.float64).reshape(-1, 4)
+    cf = dev_t(conf, torch.float32).reshape(-1)
+    cls = dev_t(classes, torch.int32).reshape(-1) if classes is not None else None
+    n = int(idx.numel())
+    if int(xy.shape[0]) != n or int(cf.numel()) != n or (cls is not None and int(cls.numel()) != n):
+        raise ValueError('nms_boxes_device: %d image indices, %d boxes, %d confidences%s'
+                         % (n, xy.shape[0], cf.numel(), '' if cls is None else ', %d classes' % cls.numel()))
+    K = n if max_out is None else int(max_out)
+    if max_out is not None and K < 1:   # (the entry point launches nothing for no slots, so there would be no mask either)
+        raise ValueError('max_out must be >= 1, got %r' % (max_out,))
+    if n_images is None:
+        n_images = int(idx.max().item()) + 1 if n else 1
+    if n == 0:
+        empty = torch.zeros(0, dtype=torch.int32, device=idx.device)
+        return (0, empty, torch.zeros((0, 4), dtype=torch.float64, device=idx.device), torch.zeros(0, dtype=torch.float32, device=idx.device),
+                (empty.clone() if cls is not None else None), empty.clone(), torch.zeros(n, dtype=torch.int32, device=idx.device))
+    count = torch.full((1,), n, dtype=torch.int32, device=idx.device)
+    cap = min(n, int(query('cy_nms_max_per_image')))
+    keep, o_img, o_xy, o_conf, o_cls, o_src, words = _nms_call(count, idx, xy, cf, cls, n, n_images, iou_th, class_aware, per_image, cap, K)
+    n_kept, err = (int(v) for v in words.cpu().numpy())
+    if err:
+        raise ValueError('nms_boxes_device: %d image(s) have more than %d boxes, the most one block holds' % (err >> 20, cap))
+    m = min(n_kept, K)
+    return n_kept, o_img[:m], o_xy[:m], o_conf[:m], (o_cls[:m] if cls is not None else None), o_src[:m], keep
+
+
+def nms_y_hat_device(y_hat, params, iou_th=0.45, class_aware=False, per_image=0, image_hw=None):
+    """A float32 device copy of the detector output y_hat [B, g, g, 5 nb + C] in which the confidence of every box that non-maximum
+    suppression removes is 0.0; every other value keeps its bits.  The candidates are all boxes with a confidence > 0, decoded with
+    image_hw like decode_boxes_device does it, suppressed per image by `cy_nms_boxes`.  Greedy suppression in descending confidence
+    is prefix-consistent -- whether a box survives depends on the boxes of at least its confidence alone -- so decoding the result
+    at ANY threshold t >= 0 gives exactly the boxes that suppression of the boxes over t keeps: one masked y_hat serves the decode
+    at 0.5 behind the crops and the drawing and every threshold of the metric sweeps.  class_aware uses the detector's own arg-max
+    class and needs params.n_classes > 0."""
+    _check_nms_args(iou_th, per_image)
+    C = int(params.n_classes)
+    if class_aware and C == 0:
+        raise ValueError('class_aware suppression needs a detector with class scores (params.n_classes > 0)')
+    yt = torch.as_tensor(np.asarray(y_hat) if not torch.is_tensor(y_hat) else y_hat).to(device='cuda', dtype=torch.float32).contiguous()
+    out = yt.clone()
+    batch, g, _, D = yt.shape
+    n, idx, xy, cls, conf = decode_boxes_device(yt, params, image_hw, 0.0, with_conf=True)
+    if n == 0:
+        return out
+    nb = int((D - C) / 5)
+    confs = out[..., 0:5 * nb:5]                      # a view [B, g, g, nb] of the copy
+    # the decode kernel walks (image, row, column, box) in this order and takes a box iff its float32 confidence > 0.0f: the
+    # same comparison in the same order, so entry k of the list is row k of `where`
+    where = torch.nonzero(confs > 0.0)
+    if int(where.shape[0]) != n:
+        raise AssertionError('nms_y_hat_device: the decode kernel found %d boxes, the comparison %d' % (n, where.shape[0]))
+    count = torch.full((1,), n, dtype=torch.int32, device=yt.device)
+    keep, _, _, _, _, _, words = _nms_call(count, idx.contiguous(), xy.contiguous(), conf.contiguous(),
+                                           cls.contiguous() if class_aware else None, n, batch, iou_th, class_aware, per_image,
+                                           g * g * nb, 1)
+    dead = where[keep == 0]
+    confs[dead[:, 0], dead[:, 1], dead[:, 2], dead[:, 3]] = 0.0
+    return out
+
+
 def y_to_boxes_vec(y, params, image_hw=None, conf_th=0.5):
     """utils.py:288-334 on the device (`cy_yolo_decode_boxes`): y is the network output / ground truth as a numpy
     array or a tensor, image_hw an optional (batch, 2) array of (height, width).  Returns (image_indices, xy, classes)

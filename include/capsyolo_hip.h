@@ -559,6 +559,28 @@ typedef struct {
 int cy_pack_detections(const float* scores, int C, const int* count, const int* box_img, const double* box_xy,
                        const float* conf, const int* rect, const int* crop_err, const int* resize_err, int K, void* record,
                        void* stream);
+/* ------------------------------------------------------------------ non-maximum suppression (csrc/nms.hip)
+ * Greedy confidence-ordered suppression of a decoded box list, per image, with no host synchronisation: two launches whose shapes
+ * depend on n_images alone (the list length is read from device memory), so the step captures into a HIP graph.  The reference has
+ * no such step; tests/nms_ref.py restates the rule in numpy.
+ * Input: the list as cy_yolo_decode_boxes_conf writes it -- count_in[1] (the live length is min(*count_in, n_cap)), box_img[n_cap]
+ * ascending, box_xy[n_cap][4] = (x1, y1, x2, y2), conf[n_cap], cls[n_cap] or NULL.
+ * Rule: inside an image the boxes are visited by confidence descending, ties to the lower list index (a NaN confidence behind
+ * every number).  A box is kept unless an already kept box of its image (class_aware: and of its class) has IoU > iou_th with it,
+ * strictly; the IoU is the double-precision one of cy_confusion_sweep (csrc/box_iou.h), and a NaN IoU suppresses nothing.  A
+ * malformed box (a corner that is not finite, x1 > x2 or y1 > y2) is kept and suppresses nothing: the crop stage counts it as bad,
+ * as without this step.  per_image > 0: only the first per_image survivors of an image stay (0: no cap).
+ * Output: keep[n_cap] in list order, 1 or 0 (0 past the live length and for an image index outside 0..n_images-1); the survivors,
+ * image ascending and inside an image confidence descending, as copies of their list entries in out_img / out_xy / out_conf /
+ * out_cls (written iff cls is given) / out_src (the index in the list), K slots each; *count_out = the survivors (may exceed K:
+ * only the first K are written); the slots at and behind min(*count_out, K) are zero-filled.  ws[n_images]: scratch.
+ * max_per_image: boxes of one image that fit in LDS (48 bytes each, at most cy_nms_max_per_image() = 3413 in 160 KiB; up to 1024
+ * stay inside the 48 KiB a launch gets without opting in).  An image with more live boxes adds 2^20 to *err (caller-zeroed) and
+ * all of its boxes get keep = 0.  K = 0 or n_cap = 0 is valid and launches nothing. */
+int cy_nms_max_per_image(void);
+int cy_nms_boxes(const int* count_in, const int* box_img, const double* box_xy, const float* conf, const int* cls, int n_cap,
+                 int n_images, double iou_th, int class_aware, int per_image, int max_per_image, int* keep, int K, int* out_img,
+                 double* out_xy, float* out_conf, int* out_cls, int* out_src, int* count_out, int* ws, int* err, void* stream);
 /* ------------------------------------------------------------------ box drawing (csrc/draw.hip)
  * plot.draw_boxes (plot.py:24-33) for n boxes in one launch, IN PLACE in a packed buffer of n_images HWC uint8 images described
  * as for cy_crop_resize_u8 (imgs / img_off / img_hw / imgs_bytes); the caller draws into a copy if it still needs the images.

@@ -27,6 +27,10 @@ detect_acc to metric_output.txt and the images with the predictions in green and
 (capsyolo_amd.serve.SignDetector: frame in, labelled boxes out, nothing crosses to the host between the two networks; ``--graph``
 replays a captured HIP graph per frame shape).  It writes one line per frame to <model_dir>/serve_output.txt and prints the
 latency percentiles (see serve()).
+``--nms IOU [--nms_class_aware]`` (new; with --mode detect, --mode predict --combine and --mode serve) runs greedy non-maximum
+suppression over the detector's boxes on the device (`cy_nms_boxes`) before they are cropped, drawn or scored: the metric files
+then hold the metrics of the suppressed predictions, and one line says how many boxes over 0.5 the step removed.  The reference
+has no such step, so the default is none.  ``--per_frame N`` (serve only) keeps at most the N most confident survivors of a frame.
 ``--mode interpret --model capsule --restore last|best [--synthetic N] [--index I]`` is the reference's capsule_interpret.py:
 the 16 x 11 perturbation sweep of sample I's labelled capsule through the fused decoder kernel, written to <model_dir>/img/
 (see interpret()).
@@ -101,6 +105,13 @@ parser.add_argument('--class_augment', action='store_true',
 parser.add_argument('--gtsrb', default=config.GTSRB, help='--augment: the GTSRB root whose Images/ are the signs to paste')
 parser.add_argument('--max_boxes', type=int, default=16,
                     help='--mode serve: box slots per call (the classifier always runs on this many crops; further boxes are dropped)')
+parser.add_argument('--nms', type=float, default=None, metavar='IOU',
+                    help='--mode detect | predict --combine | serve: non-maximum suppression of the detector\'s boxes at this IoU '
+                         '(in [0, 1]) before crops, drawing and metrics; default: none')
+parser.add_argument('--nms_class_aware', action='store_true',
+                    help='--nms: a box is suppressed only by a box of the same detector class (a detector with class scores: darknet_r)')
+parser.add_argument('--per_frame', type=int, default=0, metavar='N',
+                    help='--mode serve --nms: at most N boxes of a frame survive, the most confident ones (0: no cap)')
 parser.add_argument('--fix_ckpt_dir', action='store_true',
                     help='save checkpoints into model_dir (where --restore reads) instead of model_dir + str(train_frac)')
 
@@ -490,7 +501,8 @@ def predict(args, model, model_dir, data_dir, params):
             _, y = pickle.load(f)
         x = list(np.load(data_dir + '/test_images.npy', allow_pickle=True))
     y_hat, output = dark_class_pred(x, model, model_dir, params, class_model, class_model_dir, class_params, args.restore,
-                                    batch_size=params.batch_size, draw=args.draw)
+                                    batch_size=params.batch_size, draw=args.draw, nms_iou=args.nms,
+                                    nms_class_aware=args.nms_class_aware)
     metric_out = {name: fn(y, y_hat, params) for name, fn in combine_metrics.items()}
     with open(os.path.join(model_dir, 'combine-{}_metric_output.txt'.format(args.combine)), 'w') as text_file:
         for k, v in metric_out.items():
@@ -530,7 +542,8 @@ def detect(args, model, model_dir, data_dir, params):
         with open(data_dir + config.te_d, 'rb') as f:
             _, y = pickle.load(f)
         x = list(np.load(data_dir + '/test_images.npy', allow_pickle=True))
-    y_hat, output = dark_pred(x, model, model_dir, params, args.restore, y=y, batch_size=params.batch_size, draw=True)
+    y_hat, output = dark_pred(x, model, model_dir, params, args.restore, y=y, batch_size=params.batch_size, draw=True, nms_iou=args.nms,
+                              nms_class_aware=args.nms_class_aware)
     metric_out = metrics.detect_report(y, y_hat, params)
     with open(os.path.join(model_dir, 'metric_output.txt'), 'w') as text_file:
         for k, v in metric_out.items():
@@ -538,6 +551,24 @@ def detect(args, model, model_dir, data_dir, params):
             print("{}:{}, ".format(k, v))
     _write_output_images(model_dir, output)
     return metric_out
+
+
+def check_nms(args):
+    """The refusals of --nms / --nms_class_aware / --per_frame that need neither the data nor a device."""
+    if args.nms is None:
+        if args.nms_class_aware:
+            raise SystemExit('--nms_class_aware belongs to the suppression step: give --nms IOU')
+        if args.per_frame:
+            raise SystemExit('--per_frame belongs to the suppression step: give --nms IOU')
+        return
+    if not (0.0 <= args.nms <= 1.0):
+        raise SystemExit('--nms %r: the IoU threshold must be in [0, 1]' % (args.nms,))
+    if not (args.mode in ('detect', 'serve') or (args.mode == 'predict' and args.combine is not None)):
+        raise SystemExit('--nms suppresses detector boxes: --mode detect, --mode predict with --combine, or --mode serve')
+    if args.per_frame < 0:
+        raise SystemExit('--per_frame %d: at least 0' % args.per_frame)
+    if args.per_frame and args.mode != 'serve':
+        raise SystemExit('--per_frame caps the boxes of a frame of --mode serve')
 
 
 def check_serve(args):
@@ -571,7 +602,8 @@ def serve(args, model, model_dir, data_dir, params):
         frames = synth.raw_images(args.synthetic)
     else:
         frames = list(np.load(data_dir + '/test_images.npy', allow_pickle=True))
-    det = SignDetector(model, params, class_model, class_params, max_boxes=args.max_boxes, graph=args.graph)
+    det = SignDetector(model, params, class_model, class_params, max_boxes=args.max_boxes, graph=args.graph, nms_iou=args.nms,
+                       nms_class_aware=args.nms_class_aware, per_frame=args.per_frame)
     seen, ms = set(), []
     out = dict(frames=0, boxes=0, truncated=0, bad_boxes=0)
     with open(os.path.join(model_dir, 'serve_output.txt'), 'w') as text_file:
@@ -644,10 +676,13 @@ def main(argv=None):
         check_class_augment(args)
     if args.mode == 'serve':
         check_serve(args)
+    check_nms(args)
     data_dir, model_dir = config.data_dir[args.model], config.model_dir[args.model]
     if args.model_dir is not None:
         model_dir = args.model_dir
     params = load_params(model_dir, args)
+    if args.nms_class_aware and int(getattr(params, 'n_classes', 0)) == 0:
+        raise SystemExit('--nms_class_aware needs a detector with class scores (n_classes > 0 in %s/params.json)' % model_dir)
     params.rank, params.world, local_rank = dp.init_from_env()
     if params.world > 1 and params.batch_size % params.world:
         raise SystemExit('data parallel: batch_size %d is not divisible by the %d ranks' % (params.batch_size, params.world))

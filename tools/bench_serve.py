@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Latency of one camera frame through detector + classifier: the existing two-stage chain against serve.SignDetector.
 
-    python tools/bench_serve.py [--reps 100] [--warmup 10] [--height 800] [--width 1360] [--max_boxes 16]
+    python tools/bench_serve.py [--reps 100] [--warmup 10] [--height 800] [--width 1360] [--max_boxes 16] [--nms IOU]
 
 Default-initialised DarkNet (448 x 448 input, 14 x 14 grid, 2 boxes, no classes) and CapsuleNet (43 classes, 32 x 32 crops), one
 synthetic frame of the GTSDB size, a confidence threshold chosen between two of the detector's own confidences so that 1..max_boxes
@@ -11,7 +11,9 @@ the end of every call, `reps` calls after `warmup`) of
              stands, without its checkpoint restores (upload, host hops for the box count / rectangles / error word included)
   eager_ms   SignDetector.detect, graph=False
   graph_ms   SignDetector.detect, graph=True (one replay per frame)
-and the box count, so that the three are seen to do the same work."""
+and the box count, so that the three are seen to do the same work.  With --nms IOU the same process then measures the detector with
+the suppression step at that IoU (nms_iou=IOU: all boxes over the threshold decoded, `cy_nms_boxes`, the survivors into the slots) as
+nms_eager_ms / nms_graph_ms, with nms_boxes survivors of nms_candidates, next to the three figures without it."""
 import argparse
 import json
 import os
@@ -47,6 +49,7 @@ def main():
     ap.add_argument('--height', type=int, default=800)
     ap.add_argument('--width', type=int, default=1360)
     ap.add_argument('--max_boxes', type=int, default=16)
+    ap.add_argument('--nms', type=float, default=None, help='also measure SignDetector with non-maximum suppression at this IoU')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_serve needs a GPU')
@@ -84,6 +87,14 @@ def main():
         if res.n != n_chain or res.bad['boxes']:
             raise SystemExit('SignDetector (graph=%s) kept %d boxes (%d bad), the chain %d' % (graph, res.n, res.bad['boxes'], n_chain))
         out[key + '_ms'], out[key + '_min_ms'] = _median_ms(lambda: det.detect(frame), a.reps, a.warmup)
+    if a.nms is not None:
+        for key, graph in (('nms_eager', False), ('nms_graph', True)):
+            det = serve.SignDetector(dark, dp, caps, cp, max_boxes=K, conf_th=conf_th, graph=graph, nms_iou=a.nms)
+            res = det.detect(frame)
+            if not 1 <= res.total <= n_chain or res.bad['boxes']:
+                raise SystemExit('SignDetector (nms, graph=%s) kept %d boxes (%d bad) of the chain\'s %d' % (graph, res.total, res.bad['boxes'], n_chain))
+            out[key + '_ms'], out[key + '_min_ms'] = _median_ms(lambda: det.detect(frame), a.reps, a.warmup)
+        out.update(nms_iou=a.nms, nms_candidates=n_chain, nms_boxes=res.total)
     print(json.dumps(out))
 
 
