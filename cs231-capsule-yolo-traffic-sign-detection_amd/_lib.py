@@ -136,6 +136,7 @@ _SIGS = {
     'cy_boxes_crop_resize_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P],
     'cy_pack_detections': [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     'cy_nms_boxes': [_P, _P, _P, _P, _P, _I, _I, C.c_double, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    'cy_track_update': [_P, _P, _P, _P, _P, _I, _I, _I, C.c_double, _I, _I, _F, _I, _P, _P, _P],
     'cy_draw_boxes_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _I, _P, _P, _P],
     'cy_paste_resize_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _I, _L, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P],
     'cy_gather_jitter_u8': [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P],
@@ -192,6 +193,8 @@ _RET = {
     'cy_rank_ws_ints': (_L, [_I, _I]),
     'cy_paste_resize_max_pastes': (_I, []),
     'cy_nms_max_per_image': (_I, []),
+    'cy_track_max_pairs': (_I, []),
+    'cy_track_state_bytes': (_L, [_I, _I]),
     'cy_conv_gemm_bf16_plan': (_I, [C.POINTER(ConvGemm), _I, _I, C.POINTER(C.c_int)]),
     'cy_routing_plan': (_I, [C.POINTER(RoutingFwd), _I, _I, C.POINTER(_L), _I]),
 }

@@ -11,12 +11,16 @@ upload and the record download are captured once per frame shape in a HIP graph 
 
 Bad boxes (a corner that is not finite, an empty rectangle after clipping) do not raise as they do in utils.crop_rectangles: a
 serving loop must not die on one degenerate box.  They come back with class -1 and are counted in `Detections.bad`.
+
+`SignTracker` (optional, `SignDetector(..., tracker=)`) joins the boxes of successive frames of ONE camera into tracks: one more
+launch behind `cy_pack_detections` (`cy_track_update`, the rule is in include/capsyolo_hip.h), whose state stays in device memory and
+whose record travels beside the detections' record under the same event wait.  `Detections.tracks` is then a `Tracks`.
 """
 import numpy as np
 import torch
 
 from . import ops
-from ._lib import HipExtensionError, call
+from ._lib import HipExtensionError, call, query
 
 # the record buffer of cy_pack_detections (include/capsyolo_hip.h): cy_detections_header_t, then max_boxes cy_detection_t
 HEADER_DTYPE = np.dtype([('total', '<i4'), ('kept', '<i4'), ('crop_err', '<i4'), ('resize_err', '<i4')])
@@ -36,6 +40,113 @@ def unpack_record(buf, max_boxes):
     return buf[:HEADER_DTYPE.itemsize].view(HEADER_DTYPE)[0], buf[HEADER_DTYPE.itemsize:].view(RECORD_DTYPE)
 
 
+# the record buffer of cy_track_update: cy_tracks_header_t, then max_tracks cy_track_t, then det_track int32 [max_boxes]
+TRACKS_HEADER_DTYPE = np.dtype([('frame', '<i4'), ('live', '<i4'), ('confirmed', '<i4'), ('births', '<i4'), ('deaths', '<i4'),
+                                ('dropped', '<i4'), ('next_id', '<i4'), ('err', '<i4')])
+TRACK_DTYPE = np.dtype([('xy', '<f8', (4,)), ('id', '<i4'), ('cls', '<i4'), ('age', '<i4'), ('hits', '<i4'), ('misses', '<i4'),
+                        ('det', '<i4'), ('conf', '<f4'), ('score', '<f4')])
+assert TRACKS_HEADER_DTYPE.itemsize == 32 and TRACK_DTYPE.itemsize == 64
+
+
+def tracks_record_bytes(max_tracks, max_boxes):
+    return TRACKS_HEADER_DTYPE.itemsize + TRACK_DTYPE.itemsize * int(max_tracks) + 4 * int(max_boxes)
+
+
+def unpack_tracks(buf, max_tracks, max_boxes):
+    """(header, tracks, det_track) views of a tracker's record buffer (a uint8 array of tracks_record_bytes(...) bytes)."""
+    buf = np.asarray(buf, dtype=np.uint8).reshape(-1)
+    want = tracks_record_bytes(max_tracks, max_boxes)
+    if buf.size != want:
+        raise ValueError('a record of %d tracks and %d box slots has %d bytes, got %d' % (max_tracks, max_boxes, want, buf.size))
+    a, b = TRACKS_HEADER_DTYPE.itemsize, TRACKS_HEADER_DTYPE.itemsize + TRACK_DTYPE.itemsize * int(max_tracks)
+    return buf[:a].view(TRACKS_HEADER_DTYPE)[0], buf[a:b].view(TRACK_DTYPE), buf[b:].view('<i4')
+
+
+class Tracks(object):
+    """The tracks after one frame.  frame: frames since the tracker's reset, this one included; live: tracks alive; births / deaths /
+    dropped: tracks born and freed in this frame, detections that found no free slot in it.  Per live track, in slot order: ids int64
+    [live] (from 1, never reused), boxes_xy float64 [live, 4], classes int64 (arg-max of the class evidence summed over the track's
+    detections), class_scores float32 (that sum), conf float32 (of the last matched detection), age / hits / misses int64, det int64
+    (this frame's detection slot, -1: none), confirmed bool (hits >= the tracker's min_hits), slots int64 (the track's slot).
+    det_track int64 [max_boxes]: per detection slot the id of its track, 0 for none -- it labels `Detections`' boxes.  record: the
+    raw bytes."""
+
+    def __init__(self, record, max_tracks, max_boxes, min_hits):
+        head, trk, det_track = unpack_tracks(record, max_tracks, max_boxes)
+        self.record = record
+        self.frame, self.live = int(head['frame']), int(head['live'])
+        self.births, self.deaths, self.dropped = int(head['births']), int(head['deaths']), int(head['dropped'])
+        self.slots = np.flatnonzero(trk['id'] != 0).astype(np.int64)
+        trk = trk[self.slots]
+        self.ids = trk['id'].astype(np.int64)
+        self.boxes_xy = np.ascontiguousarray(trk['xy'], dtype=np.float64).reshape(-1, 4)
+        self.classes = trk['cls'].astype(np.int64)
+        self.class_scores = np.ascontiguousarray(trk['score'], dtype=np.float32)
+        self.conf = np.ascontiguousarray(trk['conf'], dtype=np.float32)
+        self.age, self.hits, self.misses = (trk[k].astype(np.int64) for k in ('age', 'hits', 'misses'))
+        self.det = trk['det'].astype(np.int64)
+        self.confirmed = self.hits >= int(min_hits)
+        self.det_track = det_track.astype(np.int64)
+
+
+class SignTracker(object):
+    """trk = SignTracker(n_classes, max_boxes, max_tracks=32, iou_th=0.3, max_misses=2, min_hits=2, decay=0.9, motion=True, device=None)
+
+    The tracks of one camera for `SignDetector(..., tracker=trk)`: n_classes and max_boxes are the classifier's classes and the
+    detector's box slots.  A detection joins the track whose predicted box (with motion: the last box moved on by the last step)
+    overlaps it most, at IoU > iou_th, greedily; a track without a detection for more than max_misses frames in a row ends; a
+    detection without a track starts one, while one of the max_tracks slots is free; a track counts as confirmed from min_hits
+    detections on; its class is the arg-max of sum_k decay^k * (class scores k detections ago).  Owns the state and record buffers on
+    the device and a pinned host record; reset() empties the tracks (stream-ordered, ids start again at 1)."""
+
+    def __init__(self, n_classes, max_boxes, max_tracks=32, iou_th=0.3, max_misses=2, min_hits=2, decay=0.9, motion=True, device=None):
+        for name, v, lo in (('n_classes', n_classes, 1), ('max_boxes', max_boxes, 1), ('max_tracks', max_tracks, 1),
+                            ('max_misses', max_misses, 0), ('min_hits', min_hits, 1)):
+            if isinstance(v, bool) or int(v) != v or v < lo:
+                raise ValueError('%s must be an integer >= %d, got %r' % (name, lo, v))
+        if max_tracks > 256:
+            raise ValueError('max_tracks must be at most 256, got %r' % (max_tracks,))
+        pairs = query('cy_track_max_pairs')
+        if int(max_boxes) * int(max_tracks) > pairs:
+            raise ValueError('max_boxes x max_tracks = %d x %d pairs, the tracker holds %d' % (max_boxes, max_tracks, pairs))
+        if not (0.0 <= float(iou_th) <= 1.0):
+            raise ValueError('iou_th must be in [0, 1], got %r' % (iou_th,))
+        if not (0.0 <= float(decay) <= 1.0):
+            raise ValueError('decay must be in [0, 1], got %r' % (decay,))
+        self.C, self.K, self.T = int(n_classes), int(max_boxes), int(max_tracks)
+        self.n_classes, self.max_boxes, self.max_tracks = self.C, self.K, self.T
+        self.iou_th, self.max_misses, self.min_hits = float(iou_th), int(max_misses), int(min_hits)
+        self.decay, self.motion = float(decay), bool(motion)
+        if not torch.cuda.is_available():
+            raise HipExtensionError('SignTracker needs the GPU: there is no CPU path')
+        self.dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.dev.type != 'cuda':
+            raise ValueError('the tracker lives on a GPU, got device %s' % (self.dev,))
+        if self.dev.index is None:
+            self.dev = torch.device('cuda', torch.cuda.current_device())
+        self.state = torch.zeros(int(query('cy_track_state_bytes', self.T, self.C)), dtype=torch.uint8, device=self.dev)
+        nbytes = tracks_record_bytes(self.T, self.K)
+        self.record = torch.zeros(nbytes, dtype=torch.uint8, device=self.dev)
+        self.record_host = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+
+    def reset(self):
+        """No tracks, frame 0, ids from 1 again: the all-zero state, ordered on the current stream like the launches."""
+        self.state.zero_()
+
+    def launch(self, count, box_xy, conf, rect, scores, stream):
+        """One frame: device pointers to count[1], box_xy[K][4] (double), conf[K], rect[K][4] (int32), scores[K][C] (float32)."""
+        call('cy_track_update', count, box_xy, conf, rect, scores, self.K, self.C, self.T, self.iou_th, self.max_misses, self.min_hits,
+             self.decay, int(self.motion), self.state.data_ptr(), self.record.data_ptr(), stream)
+
+    def tracks(self, record=None):
+        """`Tracks` of record bytes (default: a copy of the host record as it stands)."""
+        return Tracks(self.record_host.numpy().copy() if record is None else record, self.T, self.K, self.min_hits)
+
+    def fetch(self):
+        """The device record as `Tracks` (a blocking copy on the current stream: for tools and tests, not for the serving loop)."""
+        return self.tracks(self.record.cpu().numpy())
+
+
 class Detections(object):
     """What one `SignDetector.detect` call found.  n boxes are kept of `total` over the threshold (`truncated`: total > max_boxes,
     the first max_boxes in the decode kernel's order, which is np.argwhere's, are kept); bad = {'boxes': kept boxes without a crop
@@ -43,7 +154,8 @@ class Detections(object):
     pixels, conf float32 [n], classes int64 [n], class_scores float32 [n]; record: the raw bytes all of it was read from.
     From a detector built with nms_iou the record has the same layout, but `total` is the number of boxes that survived the
     suppression step (all boxes over the threshold take part in it, however many), and the boxes come image ascending and inside an
-    image confidence descending: a truncated result then holds the most confident survivors of the first images."""
+    image confidence descending: a truncated result then holds the most confident survivors of the first images.
+    tracks: the `Tracks` after this frame from a detector with a tracker, else None."""
 
     def __init__(self, record, max_boxes):
         head, rec = unpack_record(record, max_boxes)
@@ -57,6 +169,7 @@ class Detections(object):
         self.conf = np.ascontiguousarray(rec['conf'], dtype=np.float32)
         self.classes = rec['cls'].astype(np.int64)
         self.class_scores = np.ascontiguousarray(rec['score'], dtype=np.float32)
+        self.tracks = None
 
 
 class _State(object):
@@ -105,7 +218,7 @@ class _Candidates(object):
 
 class SignDetector(object):
     """det = SignDetector(dark_model, dark_params, class_model, class_params, max_boxes=16, conf_th=0.5, graph=False,
-                        nms_iou=None, nms_class_aware=False, per_frame=0)
+                        nms_iou=None, nms_class_aware=False, per_frame=0, tracker=None)
     res = det.detect(frames)
 
     dark_model: a DarkNet on the device (dark_params: darknet_input, n_grid, n_classes, capsule_input); class_model: CapsuleNet, or
@@ -116,10 +229,13 @@ class SignDetector(object):
     nms_iou (optional): non-maximum suppression between the decode and the crops (`cy_nms_boxes`, the rule is in
     include/capsyolo_hip.h): ALL boxes over conf_th are decoded, and the max_boxes slots take the survivors, most confident first,
     at most per_frame of a frame (0: no cap); nms_class_aware suppresses only inside the detector's own arg-max class and needs a
-    detector with class scores.  None: no such step, the first max_boxes boxes in decode order as before."""
+    detector with class scores.  None: no such step, the first max_boxes boxes in decode order as before.
+    tracker (optional): a `SignTracker` for the classifier's classes and max_boxes slots on the detector's device.  Every call is then
+    ONE frame of the tracker's camera: `cy_track_update` runs behind the pack step on the same stream (with graph=True inside every
+    frame shape's graph, all on the tracker's one state), and the result carries `.tracks`.  The detections' record does not change."""
 
     def __init__(self, dark_model, dark_params, class_model, class_params, max_boxes=16, conf_th=0.5, graph=False, nms_iou=None,
-                 nms_class_aware=False, per_frame=0):
+                 nms_class_aware=False, per_frame=0, tracker=None):
         if int(max_boxes) != max_boxes or max_boxes < 1:
             raise ValueError('max_boxes must be an integer >= 1, got %r' % (max_boxes,))
         if nms_iou is not None and not (0.0 <= float(nms_iou) <= 1.0):
@@ -130,6 +246,13 @@ class SignDetector(object):
             raise ValueError('nms_class_aware and per_frame belong to the suppression step: give nms_iou')
         if nms_class_aware and int(dark_params.n_classes) == 0:
             raise ValueError('nms_class_aware needs a detector with class scores (n_classes > 0)')
+        if tracker is not None:
+            if not isinstance(tracker, SignTracker):
+                raise ValueError('tracker must be a SignTracker, got %r' % (type(tracker).__name__,))
+            if tracker.max_boxes != int(max_boxes):
+                raise ValueError('the tracker was built for max_boxes=%d, the detector has %d' % (tracker.max_boxes, max_boxes))
+            if tracker.n_classes != int(class_params.n_classes):
+                raise ValueError('the tracker was built for n_classes=%d, the classifier has %d' % (tracker.n_classes, class_params.n_classes))
         if not torch.cuda.is_available():
             raise HipExtensionError('SignDetector needs the GPU: there is no CPU path')
         self.dark, self.dark_params, self.cls, self.class_params = dark_model, dark_params, class_model, class_params
@@ -141,6 +264,9 @@ class SignDetector(object):
         self.dev = next(dark_model.parameters()).device
         if self.dev.type != 'cuda' or next(class_model.parameters()).device != self.dev:
             raise ValueError('both models must be on the same GPU; the detector is on %s' % (self.dev,))
+        if tracker is not None and tracker.dev != self.dev:
+            raise ValueError('the tracker is on %s, the detector on %s' % (tracker.dev, self.dev))
+        self.tracker = tracker
         for m in (dark_model, class_model):
             if m.training:          # (a switch of mode starts a new fold-cache epoch, which would rebuild other detectors' captures)
                 m.eval()
@@ -213,6 +339,10 @@ class SignDetector(object):
         scores = self.cls(st.crops).data.reshape(K, -1).to(dtype=torch.float32).contiguous()
         call('cy_pack_detections', scores.data_ptr(), int(scores.shape[1]), w, st.box_img.data_ptr(), st.box_xy.data_ptr(),
              st.box_conf.data_ptr(), st.rect.data_ptr(), w + 4, w + 8, K, st.record.data_ptr(), stream)
+        if self.tracker is not None:
+            if int(scores.shape[1]) != self.tracker.n_classes:
+                raise ValueError('the classifier returned %d scores per crop, the tracker was built for %d' % (scores.shape[1], self.tracker.n_classes))
+            self.tracker.launch(w, st.box_xy.data_ptr(), st.box_conf.data_ptr(), st.rect.data_ptr(), scores.data_ptr(), stream)
         return y, scores
 
     def _weights_key(self):
@@ -222,12 +352,16 @@ class SignDetector(object):
 
     def _capture(self, st):
         """GraphedStep's recipe: one eager pass on a side stream (fold caches, one-time kernel attributes, MIOpen's choices exist
-        before the capture begins), then steps 2-7 captured on one stream."""
+        before the capture begins), then steps 2-7 captured on one stream.  The eager pass must not count as a frame: the tracker's
+        state is put back behind it."""
         st.graph, st.keep = None, None
         side = torch.cuda.Stream(device=self.dev)
         side.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(side):
+            tracks = None if self.tracker is None else self.tracker.state.clone()
             self._device_steps(st)
+            if tracks is not None:
+                self.tracker.state.copy_(tracks)
         torch.cuda.current_stream(self.dev).wait_stream(side)
         torch.cuda.synchronize(self.dev)
         graph = torch.cuda.CUDAGraph()
@@ -238,6 +372,8 @@ class SignDetector(object):
     # ------------------------------------------------------------------------------------------------ the call
     def detect(self, frames):
         arrs = self._frames(frames)
+        if self.tracker is not None and len(arrs) != 1:
+            raise ValueError('a tracker follows one camera: one frame per call, got %d' % len(arrs))
         H, W = arrs[0].shape[0:2]
         st = self._state(len(arrs), H, W)
         if self.dark.training or self.cls.training:
@@ -255,6 +391,11 @@ class SignDetector(object):
             else:
                 self._device_steps(st)
             st.record_host.copy_(st.record, non_blocking=True)
+            if self.tracker is not None:
+                self.tracker.record_host.copy_(self.tracker.record, non_blocking=True)
             st.done.record(torch.cuda.current_stream(self.dev))
         st.done.synchronize()
-        return Detections(st.record_host.numpy().copy(), self.K)
+        res = Detections(st.record_host.numpy().copy(), self.K)
+        if self.tracker is not None:
+            res.tracks = self.tracker.tracks()
+        return res

@@ -46,6 +46,34 @@ def raw_images(n, seed=1234, first=0, min_side=48, max_side=160):
     return out
 
 
+def sign_sequence(n, H=120, W=160, seed=1234, n_signs=3):
+    """n uint8 HWC frames of ONE size from one camera: the background of raw_images (gradient plus noise, the same in every frame)
+    and n_signs signs that drift at a constant velocity of up to 3 pixels a frame and grow by a pixel every other frame -- what a
+    tracker has to follow.  A sign is a noise patch of 12 .. 20 pixels per side at frame 0, nearest-neighbour scaled to its size in
+    the frame and clipped at the border.  The sequence depends only on (n_signs, H, W, seed); a longer one begins with the shorter."""
+    rng = np.random.default_rng([seed, 17])
+    ramp = np.add.outer(np.linspace(0, 96, H), np.linspace(0, 96, W))[:, :, None]
+    back = np.clip(ramp + rng.integers(0, 64, (H, W, 3)), 0, 255).astype(np.uint8)
+    signs = []
+    for _ in range(n_signs):
+        side = int(rng.integers(12, 21))
+        signs.append(dict(patch=rng.integers(0, 256, (side, side, 3), dtype=np.uint8), side=side,
+                          pos=rng.uniform([0.0, 0.0], [W - side, H - side]), vel=rng.uniform(-3.0, 3.0, 2)))
+    out = []
+    for i in range(n):
+        frame = back.copy()
+        for s in signs:
+            side = s['side'] + i // 2
+            x0, y0 = (int(v) for v in np.floor(s['pos'] + i * s['vel']))
+            ys, xs = np.arange(y0, y0 + side), np.arange(x0, x0 + side)
+            ky, kx = (ys >= 0) & (ys < H), (xs >= 0) & (xs < W)
+            if ky.any() and kx.any():
+                src = (np.arange(side) * s['side']) // side
+                frame[np.ix_(ys[ky], xs[kx])] = s['patch'][np.ix_(src[ky], src[kx])]
+        out.append(frame)
+    return out
+
+
 def raw_boxes(images, n_classes=43, seed=1234, first=0):
     """Per image a float64 [k, 5] array (x1, y1, x2, y2, class), k = 1..3, the shape of the gt.txt rows of a GTSDB frame: boxes of
     8 .. a third of the shorter side, wholly inside the image, with fractional corners (so the truncation of the paste plan is

@@ -581,6 +581,67 @@ int cy_nms_max_per_image(void);
 int cy_nms_boxes(const int* count_in, const int* box_img, const double* box_xy, const float* conf, const int* cls, int n_cap,
                  int n_images, double iou_th, int class_aware, int per_image, int max_per_image, int* keep, int K, int* out_img,
                  double* out_xy, float* out_conf, int* out_cls, int* out_src, int* count_out, int* ws, int* err, void* stream);
+/* ------------------------------------------------------------------ sign tracks (csrc/track.hip)
+ * The step behind cy_pack_detections in serve.SignDetector: the frame's boxes are joined to the tracks of the frames before, so a
+ * sign keeps an id, its class is voted over everything seen so far, and a box seen once is told from a sign.  One launch of one
+ * workgroup per frame, no host synchronisation, the tracks live in `state` in device memory: the step captures into a HIP graph.
+ * The reference has no such step; tests/track_ref.py restates the rule in numpy.
+ * Input: count[1], box_xy[K][4], conf[K], rect[K][4] (the crop kernel's rect_out) and scores[K][C] exactly as cy_pack_detections
+ * reads them.  All arithmetic on boxes is double, all arithmetic on class evidence is float, neither is contracted.
+ * Rule, per call (= per frame):
+ *  1. The live detections are the slots s < min(max(*count, 0), K) whose rect is not all zero (a bad slot, class -1 in the
+ *     detections' record, takes no part).  The live tracks are the slots with id != 0.
+ *  2. Track t predicts p_t = xy_t + vel_t per corner with motion = 1, xy_t with motion = 0; vel is zero from birth to the first match.
+ *  3. A pair (t, s) is a candidate iff box_iou(p_t, det_s) > iou_th, strictly (csrc/box_iou.h, the IoU of cy_nms_boxes and
+ *     cy_confusion_sweep, bit for bit); a NaN IoU is no candidate.
+ *  4. Greedy assignment: repeatedly the candidate with the largest IoU among those whose track and detection are both still free
+ *     is taken; ties go to the lower track slot, then to the lower detection slot.  At most min(K, T) rounds.
+ *  5. A matched track takes, in this order: vel = det - xy (the stored box, not the predicted one; kept with motion = 0, where it
+ *     is unused); xy = det, conf = conf[s], hits += 1, misses = 0, det = s; evidence[c] = decay * evidence[c] + scores[s][c] for
+ *     every class, two rounded float operations.
+ *  6. An unmatched live track: misses += 1, det = -1, with motion = 1 xy = xy + vel (it coasts); if then misses > max_misses the
+ *     slot is freed (all its fields zero) and counted in deaths.
+ *  7. Every unmatched live detection, in slot order, is born into the lowest free slot (slots freed in step 6 of this call are
+ *     free): id = ++next_id (ids start at 1 and are never reused), hits = 1, misses = 0, vel = 0, evidence = scores[s], det = s.
+ *     With no free slot the detection is counted in dropped and belongs to no track.
+ *  8. age += 1 for every live track (a track born in this call ends it with age 1).  cls = the arg-max of evidence under the rule
+ *     of cy_pack_detections (the first maximum wins, a NaN counts as the maximum), score = evidence[cls].  A track is confirmed
+ *     iff hits >= min_hits.
+ *  9. frame += 1.
+ * Record (8-byte aligned, 32 + 64 T + 4 K bytes, little-endian like the device): one cy_tracks_header_t, T cy_track_t in slot
+ * order (a free slot is all zero), then det_track int[K]: the id of the track detection slot s belongs to after this call, 0 for none.
+ * State (8-byte aligned, cy_track_state_bytes(T, C) bytes, 0 for T < 1 or C < 1): opaque; all zero is the valid empty state (no
+ * track, frame 0, no id handed out), so a reset is a stream-ordered zero fill (cy_zero_bytes).  The class evidence lives there, in
+ * global memory: C is not capped by LDS.
+ * Limits, refused before any launch: 1 <= T <= 256; K >= 1; K * T <= cy_track_max_pairs() = 4096 (the candidate table, 8 bytes a
+ * pair, stays inside the 48 KiB of LDS a launch gets without opting in); C >= 1; iou_th in [0, 1]; max_misses >= 0; min_hits >= 1;
+ * decay in [0, 1]; motion 0 or 1. */
+typedef struct {
+  int frame;        /* calls since the empty state, this one included */
+  int live;         /* tracks with id != 0 after this call */
+  int confirmed;    /* of those, tracks with hits >= min_hits */
+  int births;       /* tracks born in this call */
+  int deaths;       /* tracks freed in this call */
+  int dropped;      /* unmatched live detections of this call that found no free slot */
+  int next_id;      /* the last id handed out */
+  int err;          /* 0 (reserved) */
+} cy_tracks_header_t;
+typedef struct {
+  double xy[4];     /* x1, y1, x2, y2: the last matched detection, or with motion = 1 the box coasted from it */
+  int id;           /* 0: a free slot, every field zero */
+  int cls;          /* arg-max of the class evidence */
+  int age;          /* calls since birth, the one of the birth included */
+  int hits;         /* calls with a matched detection, the birth included */
+  int misses;       /* calls without one since the last match */
+  int det;          /* the detection slot matched or born from in this call, -1 for a live track without one */
+  float conf;       /* the detector's confidence of the last matched detection */
+  float score;      /* evidence[cls] */
+} cy_track_t;
+int cy_track_max_pairs(void);
+long long cy_track_state_bytes(int max_tracks, int n_classes);
+int cy_track_update(const int* count, const double* box_xy, const float* conf, const int* rect, const float* scores, int K, int C,
+                    int max_tracks, double iou_th, int max_misses, int min_hits, float decay, int motion, void* state, void* record,
+                    void* stream);
 /* ------------------------------------------------------------------ box drawing (csrc/draw.hip)
  * plot.draw_boxes (plot.py:24-33) for n boxes in one launch, IN PLACE in a packed buffer of n_images HWC uint8 images described
  * as for cy_crop_resize_u8 (imgs / img_off / img_hw / imgs_bytes); the caller draws into a copy if it still needs the images.

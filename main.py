@@ -31,6 +31,9 @@ latency percentiles (see serve()).
 suppression over the detector's boxes on the device (`cy_nms_boxes`) before they are cropped, drawn or scored: the metric files
 then hold the metrics of the suppressed predictions, and one line says how many boxes over 0.5 the step removed.  The reference
 has no such step, so the default is none.  ``--per_frame N`` (serve only) keeps at most the N most confident survivors of a frame.
+``--mode serve ... --track [--max_tracks N --track_iou X --max_misses M --min_hits H --track_decay D --no_motion]`` (new) follows the
+boxes from frame to frame on the device (`cy_track_update` behind serve.SignTracker): track ids, classes voted over a track's frames,
+hit counts; one line per frame goes to <model_dir>/tracks_output.txt, serve_output.txt stays as it is.
 ``--mode interpret --model capsule --restore last|best [--synthetic N] [--index I]`` is the reference's capsule_interpret.py:
 the 16 x 11 perturbation sweep of sample I's labelled capsule through the fused decoder kernel, written to <model_dir>/img/
 (see interpret()).
@@ -112,6 +115,18 @@ parser.add_argument('--nms_class_aware', action='store_true',
                     help='--nms: a box is suppressed only by a box of the same detector class (a detector with class scores: darknet_r)')
 parser.add_argument('--per_frame', type=int, default=0, metavar='N',
                     help='--mode serve --nms: at most N boxes of a frame survive, the most confident ones (0: no cap)')
+parser.add_argument('--track', action='store_true',
+                    help='--mode serve: join the boxes of successive frames into tracks on the device (ids, voted classes, hit counts); '
+                         'one line per frame goes to <model_dir>/tracks_output.txt')
+parser.add_argument('--max_tracks', type=int, default=None, metavar='N', help='--track: track slots (default 32, at most 256)')
+parser.add_argument('--track_iou', type=float, default=None, metavar='X',
+                    help='--track: a box joins a track at an IoU above this with its predicted box (default 0.3)')
+parser.add_argument('--max_misses', type=int, default=None, metavar='M',
+                    help='--track: a track ends after more than M frames in a row without a box (default 2)')
+parser.add_argument('--min_hits', type=int, default=None, metavar='H', help='--track: a track is reported as confirmed from H boxes on (default 2)')
+parser.add_argument('--track_decay', type=float, default=None, metavar='D',
+                    help='--track: weight in [0, 1] of the older class scores in a track\'s class vote (default 0.9)')
+parser.add_argument('--no_motion', action='store_true', help='--track: match against a track\'s last box, not against the box moved on by its last step')
 parser.add_argument('--fix_ckpt_dir', action='store_true',
                     help='save checkpoints into model_dir (where --restore reads) instead of model_dir + str(train_frac)')
 
@@ -571,6 +586,37 @@ def check_nms(args):
         raise SystemExit('--per_frame caps the boxes of a frame of --mode serve')
 
 
+TRACK_DEFAULTS = dict(max_tracks=32, track_iou=0.3, max_misses=2, min_hits=2, track_decay=0.9)
+
+
+def check_track(args):
+    """The refusals of --track and its options that need neither the data nor a device."""
+    given = ['--' + k for k in TRACK_DEFAULTS if getattr(args, k) is not None] + (['--no_motion'] if args.no_motion else [])
+    if not args.track:
+        if given:
+            raise SystemExit('%s belongs to the tracker: give --track' % given[0])
+        return
+    if args.mode != 'serve':
+        raise SystemExit('--track follows the boxes of --mode serve from frame to frame')
+    for k, v in TRACK_DEFAULTS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v)
+    if not 1 <= args.max_tracks <= 256:
+        raise SystemExit('--max_tracks %d: 1 to 256 track slots' % args.max_tracks)
+    from capsyolo_amd._lib import query
+    pairs = query('cy_track_max_pairs')          # (host arithmetic of the library: no device)
+    if args.max_boxes >= 1 and args.max_boxes * args.max_tracks > pairs:
+        raise SystemExit('--max_boxes %d x --max_tracks %d: the tracker holds %d pairs' % (args.max_boxes, args.max_tracks, pairs))
+    if not (0.0 <= args.track_iou <= 1.0):
+        raise SystemExit('--track_iou %r: the IoU threshold must be in [0, 1]' % (args.track_iou,))
+    if args.max_misses < 0:
+        raise SystemExit('--max_misses %d: at least 0' % args.max_misses)
+    if args.min_hits < 1:
+        raise SystemExit('--min_hits %d: at least 1' % args.min_hits)
+    if not (0.0 <= args.track_decay <= 1.0):
+        raise SystemExit('--track_decay %r: the weight must be in [0, 1]' % (args.track_decay,))
+
+
 def check_serve(args):
     """The refusals of --mode serve that need neither the data nor a device."""
     if args.model not in ('darknet_d', 'darknet_r') or args.combine not in ('cnn', 'capsule'):
@@ -587,10 +633,16 @@ def serve(args, model, model_dir, data_dir, params):
     the frame's labelled boxes.  Per frame one line (size, boxes kept / found, the boxes' classes) is printed and written to
     <model_dir>/serve_output.txt; at the end the totals and the latency p50 / p90 / max over the frames whose shape had been seen
     before (the first frame of a shape also builds that shape's buffers and, with --graph, its capture) are printed.  Returns the
-    totals as a dict."""
+    totals as a dict.
+    `--track`: a serve.SignTracker follows the boxes from frame to frame (`--synthetic N`: the N frames are synth.sign_sequence, one
+    size, signs drifting over one background); per frame a second line `frame i: live L | confirmed: id/cls/hits ...` (the confirmed
+    tracks in slot order) goes to <model_dir>/tracks_output.txt, and the totals gain tracks_born and tracks_confirmed (ids handed out,
+    ids that were confirmed at some frame).  serve_output.txt is what it is without the option."""
+    import contextlib
     import time
-    from capsyolo_amd.serve import SignDetector
+    from capsyolo_amd.serve import SignDetector, SignTracker
     check_serve(args)
+    check_track(args)
     if params.device != 'cuda':
         raise SystemExit('serve mode runs on hand-written gfx950 kernels only; no GPU is visible')
     class_model, class_model_dir, class_params = _combined_classifier(args, model_dir)
@@ -599,14 +651,21 @@ def serve(args, model, model_dir, data_dir, params):
         print("Restoring parameters from {}".format(path))
         utils.load_checkpoint(path, m, p)
     if args.synthetic:
-        frames = synth.raw_images(args.synthetic)
+        frames = synth.sign_sequence(args.synthetic) if args.track else synth.raw_images(args.synthetic)
     else:
         frames = list(np.load(data_dir + '/test_images.npy', allow_pickle=True))
+    tracker = None
+    if args.track:
+        tracker = SignTracker(int(class_params.n_classes), args.max_boxes, max_tracks=args.max_tracks, iou_th=args.track_iou,
+                              max_misses=args.max_misses, min_hits=args.min_hits, decay=args.track_decay, motion=not args.no_motion)
     det = SignDetector(model, params, class_model, class_params, max_boxes=args.max_boxes, graph=args.graph, nms_iou=args.nms,
-                       nms_class_aware=args.nms_class_aware, per_frame=args.per_frame)
+                       nms_class_aware=args.nms_class_aware, per_frame=args.per_frame, tracker=tracker)
     seen, ms = set(), []
     out = dict(frames=0, boxes=0, truncated=0, bad_boxes=0)
-    with open(os.path.join(model_dir, 'serve_output.txt'), 'w') as text_file:
+    confirmed_ids, tracks_born = set(), 0
+    with contextlib.ExitStack() as files:
+        text_file = files.enter_context(open(os.path.join(model_dir, 'serve_output.txt'), 'w'))
+        tracks_file = files.enter_context(open(os.path.join(model_dir, 'tracks_output.txt'), 'w')) if args.track else None
         for i, frame in enumerate(frames):
             frame = np.asarray(frame)
             t0 = time.perf_counter()
@@ -623,8 +682,19 @@ def serve(args, model, model_dir, data_dir, params):
             out['boxes'] += res.n
             out['truncated'] += int(res.truncated)
             out['bad_boxes'] += res.bad['boxes']
+            if tracks_file is not None:
+                tr = res.tracks
+                line = 'frame {}: live {} | confirmed:{}'.format(i, tr.live, ''.join(
+                    ' {}/{}/{}'.format(tr.ids[k], tr.classes[k], tr.hits[k]) for k in np.flatnonzero(tr.confirmed)))
+                print(line)
+                tracks_file.write(line + '\n')
+                confirmed_ids.update(int(v) for v in tr.ids[tr.confirmed])
+                tracks_born += tr.births
     lat = np.percentile(ms, [50, 90, 100]) if ms else [float('nan')] * 3
     out.update(latency_frames=len(ms), p50_ms=float(lat[0]), p90_ms=float(lat[1]), max_ms=float(lat[2]))
+    if args.track:
+        out.update(tracks_born=tracks_born, tracks_confirmed=len(confirmed_ids))
+        print('tracks born: {} | confirmed: {}'.format(out['tracks_born'], out['tracks_confirmed']))
     print('frames: {} | boxes: {} | truncated frames: {} | bad boxes: {} | latency over {} frames of a seen shape: p50 {:.3f} ms, '
           'p90 {:.3f} ms, max {:.3f} ms'.format(out['frames'], out['boxes'], out['truncated'], out['bad_boxes'], len(ms), *lat))
     return out
@@ -677,6 +747,7 @@ def main(argv=None):
     if args.mode == 'serve':
         check_serve(args)
     check_nms(args)
+    check_track(args)
     data_dir, model_dir = config.data_dir[args.model], config.model_dir[args.model]
     if args.model_dir is not None:
         model_dir = args.model_dir

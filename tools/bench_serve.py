@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Latency of one camera frame through detector + classifier: the existing two-stage chain against serve.SignDetector.
 
-    python tools/bench_serve.py [--reps 100] [--warmup 10] [--height 800] [--width 1360] [--max_boxes 16] [--nms IOU]
+    python tools/bench_serve.py [--reps 100] [--warmup 10] [--height 800] [--width 1360] [--max_boxes 16] [--nms IOU] [--track]
 
 Default-initialised DarkNet (448 x 448 input, 14 x 14 grid, 2 boxes, no classes) and CapsuleNet (43 classes, 32 x 32 crops), one
 synthetic frame of the GTSDB size, a confidence threshold chosen between two of the detector's own confidences so that 1..max_boxes
@@ -13,7 +13,11 @@ the end of every call, `reps` calls after `warmup`) of
   graph_ms   SignDetector.detect, graph=True (one replay per frame)
 and the box count, so that the three are seen to do the same work.  With --nms IOU the same process then measures the detector with
 the suppression step at that IoU (nms_iou=IOU: all boxes over the threshold decoded, `cy_nms_boxes`, the survivors into the slots) as
-nms_eager_ms / nms_graph_ms, with nms_boxes survivors of nms_candidates, next to the three figures without it."""
+nms_eager_ms / nms_graph_ms, with nms_boxes survivors of nms_candidates, next to the three figures without it.  With --track the same
+process then measures the detector with a serve.SignTracker attached (32 tracks, `cy_track_update` behind the pack step) against the
+detector without one, the two ALTERNATING twice so that the spread between two measurements of the same code is seen next to the
+difference: track_eager / track_graph hold `plain_ms` and `track_ms` (two medians each), `plain_p50_p90` and `track_p50_p90` (the
+percentiles over all the calls of a kind) and the live tracks at the end."""
 import argparse
 import json
 import os
@@ -42,6 +46,19 @@ def _median_ms(fn, reps, warmup):
     return float(np.median(ms)), float(np.min(ms))
 
 
+def _all_ms(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return ms
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=100)
@@ -50,6 +67,7 @@ def main():
     ap.add_argument('--width', type=int, default=1360)
     ap.add_argument('--max_boxes', type=int, default=16)
     ap.add_argument('--nms', type=float, default=None, help='also measure SignDetector with non-maximum suppression at this IoU')
+    ap.add_argument('--track', action='store_true', help='also measure SignDetector with a SignTracker attached, alternating with the plain one')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_serve needs a GPU')
@@ -95,6 +113,26 @@ def main():
                 raise SystemExit('SignDetector (nms, graph=%s) kept %d boxes (%d bad) of the chain\'s %d' % (graph, res.total, res.bad['boxes'], n_chain))
             out[key + '_ms'], out[key + '_min_ms'] = _median_ms(lambda: det.detect(frame), a.reps, a.warmup)
         out.update(nms_iou=a.nms, nms_candidates=n_chain, nms_boxes=res.total)
+    if a.track:
+        for key, graph in (('track_eager', False), ('track_graph', True)):
+            trk = serve.SignTracker(43, K)
+            dets = {'plain': serve.SignDetector(dark, dp, caps, cp, max_boxes=K, conf_th=conf_th, graph=graph),
+                    'track': serve.SignDetector(dark, dp, caps, cp, max_boxes=K, conf_th=conf_th, graph=graph, tracker=trk)}
+            res = dets['track'].detect(frame)
+            if res.n != n_chain or res.bad['boxes'] or res.tracks.live != n_chain:
+                raise SystemExit('SignDetector (tracker, graph=%s) kept %d boxes, %d tracks, the chain %d' % (graph, res.n, res.tracks.live, n_chain))
+            med, calls = {'plain': [], 'track': []}, {'plain': [], 'track': []}
+            for _ in range(2):
+                for name in ('plain', 'track'):
+                    ms = _all_ms(lambda: dets[name].detect(frame), a.reps, a.warmup)
+                    med[name].append(float(np.median(ms)))
+                    calls[name].extend(ms)
+            live = dets['track'].detect(frame).tracks
+            if live.live != n_chain or (live.hits < 2 * (a.reps + a.warmup)).any():
+                raise SystemExit('the tracker lost its tracks: %d live, hits %s' % (live.live, live.hits.tolist()))
+            out[key] = {'plain_ms': med['plain'], 'track_ms': med['track'], 'tracks': live.live,
+                        'plain_p50_p90': [float(v) for v in np.percentile(calls['plain'], [50, 90])],
+                        'track_p50_p90': [float(v) for v in np.percentile(calls['track'], [50, 90])]}
     print(json.dumps(out))
 
 
