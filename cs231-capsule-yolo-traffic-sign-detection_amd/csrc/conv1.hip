@@ -915,37 +915,52 @@ static int conv1_bn_check(const char* who, const float* X, const float* W, const
   return 0;
 }
 
+// The one launcher of the BatchNorm-backward passes over dA (conv1_bn_bwd_kernel<NT, PASS>, or conv1_bn_bwd_bf16mm_kernel for a bf16
+// gradient): PASS 0 sums (cy_conv1_bn_bwd_reduce), 1 forms dz and the weight gradient (cy_conv1_bn_bwd_wgrad), 2 is the one-pass
+// form (cy_conv1_bn_bwd_onepass), which with the forward's sign mask runs as PASS 3.  pass_ok / pass_msg: the pass's own argument
+// check, made behind the one all passes share; red_out, red_in / count, slabs and mask are the Conv1BnArgs fields of those names
+// (count 0: no red_in).  *blocks: the grid, which the pass's finish kernel wants.
+template <int PASS>
+static int conv1_bn_bwd_launch(const char* who, bool pass_ok, const char* pass_msg, const float* X, const float* W, const float* bias,
+                               const void* dA, bool da_bf16, const float* scale, const float* shift, const float* mean,
+                               const float* invstd, float slope, double* red_out, const double* red_in, long long count, float* slabs,
+                               const void* mask, int B, int H, int Wd, int Cout, hipStream_t s, long long* blocks) {
+  int rc = conv1_bn_check(who, X, W, (const float*)dA, scale, shift, mean, invstd, slope, B, H, Wd, Cout);
+  if (rc) return rc;
+  CY_REQUIRE(pass_ok, pass_msg, who);
+  Conv1BnArgs a;
+  a.X = X; a.W = W; a.bias = bias; a.dA = (const float*)dA; a.scale = scale; a.shift = shift; a.mean = mean; a.invstd = invstd;
+  a.slope = slope; a.red_out = red_out; a.red_in = red_in; a.inv_count = count > 0 ? 1.0 / (double)count : 0.0; a.slabs = slabs;
+  a.mask = mask; a.B = B; a.H = H; a.Wd = Wd; a.Cout = Cout; a.ntiles = (long long)B * H * (Wd / 32);
+  rc = conv1_blocks(a.ntiles, blocks, who);
+  if (rc) return rc;
+  constexpr int MASKED = PASS == 2 ? 3 : PASS;   // (passes 0 and 1 take no mask)
+#ifdef CY_C1_F32MM
+#define CY_CONV1_BN_BF16(NT_) conv1_bn_bwd_kernel<NT_, PASS, true>
+#else
+#define CY_CONV1_BN_BF16(NT_) conv1_bn_bwd_bf16mm_kernel<NT_, PASS>
+#endif
+#define CY_CONV1_BN_LAUNCH(NT_)                                                                         \
+  do {                                                                                                   \
+    if (PASS == 2 && mask) conv1_bn_bwd_kernel<NT_, MASKED><<<(unsigned)*blocks, 256, 0, s>>>(a);        \
+    else if (da_bf16) CY_CONV1_BN_BF16(NT_)<<<(unsigned)*blocks, 256, 0, s>>>(a);                        \
+    else conv1_bn_bwd_kernel<NT_, PASS><<<(unsigned)*blocks, 256, 0, s>>>(a);                            \
+  } while (0)
+  if (Cout == 128) CY_CONV1_BN_LAUNCH(4);
+  else if (Cout == 64) CY_CONV1_BN_LAUNCH(2);
+  else CY_CONV1_BN_LAUNCH(1);
+#undef CY_CONV1_BN_LAUNCH
+#undef CY_CONV1_BN_BF16
+  CY_LAUNCH_CHECK(who);
+  return 0;
+}
+
 static int conv1_bn_bwd_reduce_impl(const char* who, const float* X, const float* W, const float* bias, const void* dA,
                                     bool da_bf16, const float* scale, const float* shift, const float* mean, const float* invstd,
                                     float slope, double* red, int B, int H, int Wd, int Cout, void* stream) {
-  int rc = conv1_bn_check(who, X, W, (const float*)dA, scale, shift, mean, invstd, slope, B, H, Wd, Cout);
-  if (rc) return rc;
-  CY_REQUIRE(red != nullptr, "%s: red is NULL", who);
-  Conv1BnArgs a;
-  a.X = X; a.W = W; a.bias = bias; a.dA = (const float*)dA; a.scale = scale; a.shift = shift; a.mean = mean; a.invstd = invstd;
-  a.slope = slope; a.red_out = red; a.red_in = nullptr; a.inv_count = 0.0; a.slabs = nullptr; a.mask = nullptr;
-  a.B = B; a.H = H; a.Wd = Wd; a.Cout = Cout; a.ntiles = (long long)B * H * (Wd / 32);
   long long blocks = 0;
-  rc = conv1_blocks(a.ntiles, &blocks, who);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if (da_bf16) {
-#ifdef CY_C1_F32MM
-    if (Cout == 128) conv1_bn_bwd_kernel<4, 0, true><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else if (Cout == 64) conv1_bn_bwd_kernel<2, 0, true><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else conv1_bn_bwd_kernel<1, 0, true><<<(unsigned)blocks, 256, 0, s>>>(a);
-#else
-    if (Cout == 128) conv1_bn_bwd_bf16mm_kernel<4, 0><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else if (Cout == 64) conv1_bn_bwd_bf16mm_kernel<2, 0><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else conv1_bn_bwd_bf16mm_kernel<1, 0><<<(unsigned)blocks, 256, 0, s>>>(a);
-#endif
-  } else {
-    if (Cout == 128) conv1_bn_bwd_kernel<4, 0><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else if (Cout == 64) conv1_bn_bwd_kernel<2, 0><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else conv1_bn_bwd_kernel<1, 0><<<(unsigned)blocks, 256, 0, s>>>(a);
-  }
-  CY_LAUNCH_CHECK(who);
-  return 0;
+  return conv1_bn_bwd_launch<0>(who, red != nullptr, "%s: red is NULL", X, W, bias, dA, da_bf16, scale, shift, mean, invstd, slope,
+                                red, nullptr, 0, nullptr, nullptr, B, H, Wd, Cout, (hipStream_t)stream, &blocks);
 }
 extern "C" int cy_conv1_bn_bwd_reduce(const float* X, const float* W, const float* bias, const float* dA, const float* scale,
                                       const float* shift, const float* mean, const float* invstd, float slope, double* red,
@@ -965,38 +980,11 @@ static int conv1_bn_bwd_onepass_impl(const char* who, const float* X, const floa
                                      const float* scale, const float* shift, const float* mean, const float* invstd, float slope,
                                      const double* M2, double* redc, float* dW, float* dgamma, float* dbeta, double* red_out,
                                      float* ws, int B, int H, int Wd, int Cout, void* stream, const void* mask = nullptr) {
-  int rc = conv1_bn_check(who, X, W, (const float*)dA, scale, shift, mean, invstd, slope, B, H, Wd, Cout);
-  if (rc) return rc;
-  CY_REQUIRE(M2 && redc && dW && dgamma && dbeta && ws, "%s: NULL argument", who);
-  Conv1BnArgs a;
-  a.mask = mask;
-  a.X = X; a.W = W; a.bias = bias; a.dA = (const float*)dA; a.scale = scale; a.shift = shift; a.mean = mean; a.invstd = invstd;
-  a.slope = slope; a.red_out = redc; a.red_in = nullptr; a.inv_count = 0.0; a.slabs = ws;
-  a.B = B; a.H = H; a.Wd = Wd; a.Cout = Cout; a.ntiles = (long long)B * H * (Wd / 32);
-  long long blocks = 0;
-  rc = conv1_blocks(a.ntiles, &blocks, who);
-  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (mask != nullptr) {
-    if (Cout == 128) conv1_bn_bwd_kernel<4, 3><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else if (Cout == 64) conv1_bn_bwd_kernel<2, 3><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else conv1_bn_bwd_kernel<1, 3><<<(unsigned)blocks, 256, 0, s>>>(a);
-  } else if (da_bf16) {
-#ifdef CY_C1_F32MM
-    if (Cout == 128) conv1_bn_bwd_kernel<4, 2, true><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else if (Cout == 64) conv1_bn_bwd_kernel<2, 2, true><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else conv1_bn_bwd_kernel<1, 2, true><<<(unsigned)blocks, 256, 0, s>>>(a);
-#else
-    if (Cout == 128) conv1_bn_bwd_bf16mm_kernel<4, 2><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else if (Cout == 64) conv1_bn_bwd_bf16mm_kernel<2, 2><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else conv1_bn_bwd_bf16mm_kernel<1, 2><<<(unsigned)blocks, 256, 0, s>>>(a);
-#endif
-  } else {
-    if (Cout == 128) conv1_bn_bwd_kernel<4, 2><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else if (Cout == 64) conv1_bn_bwd_kernel<2, 2><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else conv1_bn_bwd_kernel<1, 2><<<(unsigned)blocks, 256, 0, s>>>(a);
-  }
-  CY_LAUNCH_CHECK(who);
+  long long blocks = 0;
+  int rc = conv1_bn_bwd_launch<2>(who, M2 && redc && dW && dgamma && dbeta && ws, "%s: NULL argument", X, W, bias, dA, da_bf16,
+                                  scale, shift, mean, invstd, slope, redc, nullptr, 0, ws, mask, B, H, Wd, Cout, s, &blocks);
+  if (rc) return rc;
   conv1_bn_bwd_finish_kernel<<<Cout, 256, 0, s>>>(ws, (int)(blocks * 4), redc, M2, W, bias, scale, mean, invstd, dW, dgamma, dbeta,
                                                   red_out, Cout);
   CY_LAUNCH_CHECK(who);
@@ -1036,33 +1024,11 @@ static int conv1_bn_bwd_wgrad_impl(const char* who, bool da_bf16, const float* X
                                      const float* shift, const float* mean, const float* invstd, float slope,
                                      const double* red, long long count, float* dW, float* ws, int B, int H, int Wd,
                                      int Cout, void* stream) {
-  int rc = conv1_bn_check(who, X, W, (const float*)dA, scale, shift, mean, invstd, slope, B, H, Wd, Cout);
-  if (rc) return rc;
-  CY_REQUIRE(red && dW && ws && count > 0, "cy_conv1_bn_bwd_wgrad: bad arguments");
-  Conv1BnArgs a;
-  a.X = X; a.W = W; a.bias = bias; a.dA = (const float*)dA; a.scale = scale; a.shift = shift; a.mean = mean; a.invstd = invstd;
-  a.slope = slope; a.red_out = nullptr; a.red_in = red; a.inv_count = 1.0 / (double)count; a.slabs = ws; a.mask = nullptr;
-  a.B = B; a.H = H; a.Wd = Wd; a.Cout = Cout; a.ntiles = (long long)B * H * (Wd / 32);
-  long long blocks = 0;
-  rc = conv1_blocks(a.ntiles, &blocks, who);
-  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (da_bf16) {
-#ifdef CY_C1_F32MM
-    if (Cout == 128) conv1_bn_bwd_kernel<4, 1, true><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else if (Cout == 64) conv1_bn_bwd_kernel<2, 1, true><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else conv1_bn_bwd_kernel<1, 1, true><<<(unsigned)blocks, 256, 0, s>>>(a);
-#else
-    if (Cout == 128) conv1_bn_bwd_bf16mm_kernel<4, 1><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else if (Cout == 64) conv1_bn_bwd_bf16mm_kernel<2, 1><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else conv1_bn_bwd_bf16mm_kernel<1, 1><<<(unsigned)blocks, 256, 0, s>>>(a);
-#endif
-  } else {
-    if (Cout == 128) conv1_bn_bwd_kernel<4, 1><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else if (Cout == 64) conv1_bn_bwd_kernel<2, 1><<<(unsigned)blocks, 256, 0, s>>>(a);
-    else conv1_bn_bwd_kernel<1, 1><<<(unsigned)blocks, 256, 0, s>>>(a);
-  }
-  CY_LAUNCH_CHECK(who);
+  long long blocks = 0;
+  int rc = conv1_bn_bwd_launch<1>(who, red && dW && ws && count > 0, "cy_conv1_bn_bwd_wgrad: bad arguments", X, W, bias, dA, da_bf16,
+                                  scale, shift, mean, invstd, slope, nullptr, red, count, ws, nullptr, B, H, Wd, Cout, s, &blocks);
+  if (rc) return rc;
   conv1_wgrad_finish_kernel<<<Cout, 256, 0, s>>>(ws, dW, (int)(blocks * 4), Cout);
   CY_LAUNCH_CHECK(who);
   return 0;

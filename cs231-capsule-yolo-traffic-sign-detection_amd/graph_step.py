@@ -11,6 +11,8 @@ step lives in device memory: the batch (static input buffers, filled by `copy_` 
 (step count -> bias corrections, a scheduler's learning rate: `optim.Adam.graph_hyper`, six floats refreshed before the replay).
 Single process only: the data-parallel gradient all-reduce stays on the eager path.
 """
+import gc
+
 import torch
 
 from . import ops
@@ -73,6 +75,7 @@ class GraphedStep(object):
         optimizer.graph_tables = self._tables
         try:
             optimizer.zero_grad(set_to_none=True)
+            gc.collect()      # no dead cycle with pinned buffers or events is finalised inside the capture (serve.SignDetector._capture)
             with torch.cuda.graph(self.graph):
                 self.y_hat, self.loss = forward_loss(model, *self.static)
                 self.loss.backward()

@@ -94,7 +94,7 @@ class FusedBackbone(nn.Sequential):
                                                  'for conv -> BatchNorm -> LeakyReLU blocks only' % (nm, type(m).__name__))
         convs = [i for i, m in enumerate(mods) if isinstance(m, HipConv2d)]
         first = True
-        holder = None                            # producer block -> consumer block: what the fused BatchNorm-backward sums need
+        h = None                                 # ops.BnHandover, producer block -> consumer block: what the fused BatchNorm-backward sums need
         for n, i in enumerate(convs):
             m = mods[i]
             bn, act, _ = self._triple(mods, i)
@@ -114,9 +114,7 @@ class FusedBackbone(nn.Sequential):
             cfg = ops.ConvBlockCfg(m.k, m.stride, m.padding, False, bn, slope, names[i])
             cfg.in_f32 = (n == 1) and x.dtype == torch.float32   # (a first block without BatchNorm hands over fp32)
             cfg.out_f32 = (n == len(convs) - 1)
-            cfg.in_holder, cfg.out_holder = holder, {}
-            holder = cfg.out_holder
-            x = ops.conv_block_bf16(x, m.weight, m.bias, bn.weight, bn.bias, cfg)
+            x, h = ops.conv_block_bf16(x, m.weight, m.bias, bn.weight, bn.bias, cfg, h)
         return x
 
     def forward(self, x, nchw_in=True):
@@ -126,7 +124,7 @@ class FusedBackbone(nn.Sequential):
             return self._forward_bf16(x, nchw_in)
         names, mods = zip(*self.named_children())
         i = 0
-        lazy = None                               # (scale, shift, slope) of a producer that deferred its activation
+        h = None                                  # the ops.BnHandover of a producer that deferred its activation
         while i < len(mods):
             m = mods[i]
             if isinstance(m, HipConv2d):
@@ -149,19 +147,16 @@ class FusedBackbone(nn.Sequential):
                 if (self.training and bn is not None and bn.training and nxt < len(mods) and isinstance(mods[nxt], HipMaxPool2)
                         and not nchw_in):
                     pool = defer = ops.pool_fusable(m.weight.shape[0], ho, wo, slope)
-                cfg = ops.ConvBlockCfg(m.k, m.stride, m.padding, nchw_in, bn, slope, names[i], defer_act=defer,
-                                       in_slope=lazy[2] if lazy is not None else None)
-                cfg.in_holder = lazy[3] if lazy is not None else None
+                cfg = ops.ConvBlockCfg(m.k, m.stride, m.padding, nchw_in, bn, slope, names[i], defer_act=defer)
                 out = ops.conv_block(x, m.weight, m.bias, bn.weight if bn is not None else None,
-                                     bn.bias if bn is not None else None, cfg,
-                                     lazy[0] if lazy is not None else None, lazy[1] if lazy is not None else None)
+                                     bn.bias if bn is not None else None, cfg, h)
                 if pool:
-                    x, lazy = ops.affine_act_maxpool(out[0], out[1], out[2], slope, cfg.out_holder), None
+                    x, h = ops.affine_act_maxpool(*out), None
                     nxt += 1                                  # the max-pool module is done
                 elif defer:
-                    x, lazy = out[0], (out[1], out[2], slope, cfg.out_holder)
+                    x, h = out
                 else:
-                    x, lazy = out, None
+                    x, h = out, None
                 nchw_in = False
                 i = nxt
             elif isinstance(m, nn.Dropout):

@@ -466,18 +466,37 @@ def fold_eval_bn(weight, bias, gamma, beta, bn):
 
 
 class ConvBlockCfg(object):
-    """Static description of one conv (+BatchNorm) (+activation) block."""
+    """Static description of one conv (+BatchNorm) (+activation) block: no forward or backward writes to it, so one cfg may
+    serve any number of steps.  What travels between two blocks of one step is a BnHandover, not an attribute here."""
 
-    def __init__(self, k, stride, pad, nchw_in=False, bn=None, slope=None, name='conv', defer_act=False, in_slope=None):
+    def __init__(self, k, stride, pad, nchw_in=False, bn=None, slope=None, name='conv', defer_act=False):
         self.k, self.stride, self.pad, self.nchw_in, self.name = k, stride, pad, nchw_in, name
-        self.defer_act = defer_act   # return (z, scale, shift): the consumer applies BatchNorm + LeakyReLU on its loads
-        self.in_slope = in_slope     # not None: x is the producer's raw output, in_scale / in_shift come with it
-        self.in_holder = None        # the producer's hand-over dict (mean, invstd; this block's backward fills 'red')
-        self.out_holder = None       # this block's own hand-over dict, for its consumer (set by a deferring forward / the bf16 walk)
+        self.defer_act = defer_act   # return (z, BnHandover): the consumer applies BatchNorm + LeakyReLU on its loads
         self.out_bf16 = False        # fp32 first block of the bf16 backbone: the activation leaves as bf16, the gradient arrives as bf16
         self.in_f32 = self.out_f32 = False   # bf16 block: x comes from an fp32 producer / the activation leaves for an fp32 consumer
         self.bn = bn            # module with running_mean / running_var / momentum / eps / training, or None
         self.slope = slope      # None: no activation; 0.0: ReLU; else LeakyReLU slope
+
+
+class BnHandover(object):
+    """What a conv -> BatchNorm -> LeakyReLU block (the PRODUCER) hands to the block that reads its output (the CONSUMER).
+    scale / shift / slope let the consumer of a raw output z apply the activation on its loads; mean / invstd (None in eval
+    mode) and, on the bf16 path, z let its input-gradient kernel also sum the producer's BatchNorm backward.  The consumer's
+    backward GIVES those sums: give_red(red [C][2] double, premasked = its gradient already carries the activation's
+    derivative).  The producer's backward, which runs afterwards, TAKES them exactly once: take_red() -> (red, premasked),
+    or None when nobody gave any (it then sums for itself); after a take the object is empty again."""
+    __slots__ = ('z', 'scale', 'shift', 'mean', 'invstd', 'slope', '_red')
+
+    def __init__(self, scale, shift, mean, invstd, slope, z=None):
+        self.z, self.scale, self.shift, self.mean, self.invstd, self.slope = z, scale, shift, mean, invstd, float(slope)
+        self._red = None
+
+    def give_red(self, red, premasked):
+        self._red = (red, bool(premasked))
+
+    def take_red(self):
+        got, self._red = self._red, None
+        return got
 
 
 SYNC_BN = False     # data parallel only: BatchNorm statistics (forward sums, backward sums) summed over all ranks, so
@@ -511,63 +530,193 @@ def _leave(out, cfg, st):
     return ob
 
 
-class _ConvBlock(torch.autograd.Function):
-    """conv -> [BatchNorm (batch statistics from the conv epilogue)] -> [Leaky]ReLU, saving only x and z."""
+def _sync_red(red, N, st):
+    """The BatchNorm-backward sums red [N][2] of this rank -> of the global batch (data parallel under SYNC_BN; else as they are)."""
+    dist, world = _sync_world()
+    if dist is not None:
+        # global sums / world: the apply kernel divides by the LOCAL pixel count, which then gives the global
+        # means; dgamma / dbeta come out as (global sum) / world, what the gradient all-reduce MEAN expects
+        red = red.contiguous()
+        call('cy_bn_red_fold', _ptr(red), 1, 1.0 / world, _ptr(red), None, None, N, st)    # in place: sum of the pre-scaled = mean
+        dist.all_reduce(red)
+    return red
+
+
+def _grad_f32(da, cfg, keep_bf16=False):
+    """The gradient that reached a block's output, as fp32 (keep_bf16: only the first-layer kernels read a bf16 gradient)."""
+    if da is None:
+        raise _lib.HipExtensionError('conv block %s: no gradient reached its output' % cfg.name)
+    if da.dtype == torch.bfloat16 and cfg.out_bf16:
+        if keep_bf16:
+            return da.contiguous()
+        daf = torch.empty(da.shape, dtype=torch.float32, device=da.device)
+        call('cy_cast_bf16_f32', _ptr(da.contiguous()), _ptr(daf), da.numel(), _stream())
+        return daf
+    return _f32(da, 'grad')
+
+
+def _input_grad(ctx, dz, x, weight, plan, st):
+    """dx of a block whose input wants one; as the CONSUMER of ctx.hin, the input-gradient kernel's epilogue also sums the
+    producer's BatchNorm backward where the plan has that form, and the sums are given to the hand-over."""
+    if not ctx.needs_input_grad[0]:
+        return None
+    if plan.dgrad is None:
+        raise _lib.HipExtensionError('input gradient of an NCHW-input convolution is not implemented')
+    cfg, h, fuse = ctx.cfg, ctx.hin, None
+    if plan.dgrad_bn_fuse and h is not None and h.mean is not None:
+        bred = zero_pool.take((STATS_COPIES, x.shape[3], 2), torch.float64, x.device)
+        fuse = (x, h.scale, h.shift, h.mean, h.invstd, h.slope, bred)
+    dx = conv_dgrad(dz, weight, tuple(x.shape), cfg.k, cfg.stride, cfg.pad, cfg.name, fuse, plan)
+    if fuse is not None:
+        red = _empty((x.shape[3], 2), x, torch.float64)
+        call('cy_bn_red_fold', _ptr(bred), STATS_COPIES, 1.0, _ptr(red), None, None, x.shape[3], st)
+        h.give_red(red, plan.dgrad_premasks)
+    return dx
+
+
+class _ConvBlockNoBn(torch.autograd.Function):
+    """conv -> [[Leaky]ReLU], saving x and z."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, cfg, in_scale=None, in_shift=None):
+    def forward(ctx, x, weight, bias, cfg, hin):
+        x, weight = _f32(x, 'conv input'), _f32(weight, 'conv weight')
+        if cfg.defer_act:
+            raise _lib.HipExtensionError('defer_act needs a BatchNorm block')
+        N = weight.shape[0]
+        ctx.cfg, ctx.has_bias, ctx.hin = cfg, bias is not None, hin
+        ctx.in_affine = None if hin is None else (hin.scale, hin.shift, hin.slope)      # x is the raw output of a deferring producer
+        ctx.set_materialize_grads(False)
+        relu = cfg.slope is not None and cfg.slope == 0.0
+        z = conv_forward(x, weight, bias, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, None, relu, cfg.name, ctx.in_affine)
+        out = z
+        if cfg.slope is not None and not relu:
+            out = torch.empty_like(z)
+            call('cy_affine_act', _ptr(z), _ptr(out), None, None, float(cfg.slope), z.numel() // N, N, _stream())
+        ctx.save_for_backward(x, weight, z)
+        return out
+
+    @staticmethod
+    def backward(ctx, da):
+        cfg = ctx.cfg
+        dz = da = _grad_f32(da, cfg)
+        st = _stream()
+        x, weight, z = ctx.saved_tensors
+        N = weight.shape[0]
+        plan = conv_plan(x.shape, N, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in)
+        if cfg.slope is not None:
+            dz = torch.empty_like(z)
+            call('cy_act_bwd', _ptr(z), _ptr(da), _ptr(dz), float(cfg.slope), z.numel(), st)
+        dbias = None
+        if ctx.has_bias:
+            dbias = _empty((N,), z)
+            call('cy_channel_sum', _ptr(dz), _ptr(dbias), z.numel() // N, N, st)
+        dW = conv_wgrad(x, dz, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, cfg.name, ctx.in_affine, plan)
+        return _input_grad(ctx, dz, x, weight, plan, st), dW, dbias, None, None
+
+
+class _Conv1TrainBlock(torch.autograd.Function):
+    """The first block (3 -> {32, 64, 128} channels, NCHW image; csrc/conv1.hip) in training mode: conv -> BatchNorm ->
+    LeakyReLU without z in memory.  The forward takes the statistics (from the moment matrix of the input patches, or from one
+    pass that computes the layer and keeps nothing) and then writes the activation; the backward passes recompute the
+    convolution and read only the gradient.  The image gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, cfg, plan):
+        x, weight = _f32(x, 'conv input'), _f32(weight, 'conv weight')
+        st = _stream()
+        N = weight.shape[0]
+        Bx, _, Hx, Wx = x.shape
+        ctx.cfg, ctx.has_bias, ctx.m2, ctx.mask = cfg, bias is not None, None, None
+        ctx.set_materialize_grads(False)
+        scale, shift, mean, invstd = (_empty((N,), x) for _ in range(4))
+        stats = zero_pool.take((STATS_COPIES, N, 2), torch.float64, x.device)
+        if plan.conv1_moments:
+            # sum z and sum z^2 from the moment matrix of the input patches: the layer is not computed for them
+            wsm = _empty((query('cy_conv1_3x3_stats_ws_floats', Bx, Hx),), x)
+            with timer.range('conv1_fwd_stats/' + cfg.name):
+                call('cy_conv1_3x3_stats', _ptr(x), _ptr(weight.contiguous()), _ptr(bias), _ptr(stats), _ptr(wsm),
+                     Bx, Hx, Wx, N, st)
+            off = query('cy_conv1_3x3_stats_m2_offset', Bx, Hx)
+            ctx.m2 = wsm[off:off + 2048]    # the double M2[32][32]: the one-pass backward reads it
+        else:
+            with timer.range('conv1_fwd_stats/' + cfg.name):
+                call('cy_conv1_3x3_fwd', _ptr(x), _ptr(weight.contiguous()), _ptr(bias), None, _ptr(stats), None, None,
+                     1.0, Bx, Hx, Wx, N, st)
+        _bn_finalize(stats, Bx * Hx * Wx, gamma, beta, cfg.bn, scale, shift, mean, invstd, N, st)
+        if plan.conv1_signmask and ctx.m2 is not None and not cfg.out_bf16 and _sync_world()[0] is None:
+            # the fp32 block: the one-pass backward will want the sign of y and nothing else of z
+            ctx.mask = torch.empty((query('cy_conv1_signmask_bytes', Bx, Hx, Wx, N),), dtype=torch.uint8, device=x.device)
+        ctx.save_for_backward(x, weight, bias, scale, shift, mean, invstd)
+        slope = 1.0 if cfg.slope is None else float(cfg.slope)
+        return conv1_affine_act(x, weight, bias, scale, shift, slope, cfg.name, cfg.out_bf16, ctx.mask)
+
+    @staticmethod
+    def backward(ctx, da):
+        cfg = ctx.cfg
+        da = _grad_f32(da, cfg, keep_bf16=True)
+        da_bf16 = da.dtype == torch.bfloat16
+        st = _stream()
+        x, weight, bias, scale, shift, mean, invstd = ctx.saved_tensors
+        N, slope = weight.shape[0], 1.0 if cfg.slope is None else float(cfg.slope)
+        B, _, Hi, Wi = x.shape
+        plan = conv_plan(x.shape, N, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in)
+        # both passes recompute z tile by tile and read only da; dz is formed in registers in the layout the weight-gradient
+        # MFMA consumes (csrc/conv1.hip)
+        redc = zero_pool.take((STATS_COPIES, N, 2), torch.float64, x.device)
+        dW, dbeta, dgamma = _empty(tuple(weight.shape), x), _empty((N,), x), _empty((N,), x)
+        ws = _empty((query('cy_conv1_bn_bwd_wgrad_ws_floats', B, Hi, Wi, N),), x)
+        common = (_ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), slope)
+        if plan.conv1_onepass and ctx.m2 is not None and _sync_world()[0] is None:
+            # one pass over da: sum d and the weight gradient OF d; the rest follows from the forward's patch moments
+            tail = (_ptr(ctx.m2), _ptr(redc), _ptr(dW), _ptr(dgamma), _ptr(dbeta), None, _ptr(ws), B, Hi, Wi, N, st)
+            with timer.range('conv1_bn_bwd_onepass/' + cfg.name):
+                if ctx.mask is not None and not da_bf16 and da.data_ptr() % 16 == 0:
+                    call('cy_conv1_bn_bwd_onepass_mask', _ptr(x), _ptr(weight), _ptr(bias), _ptr(da), _ptr(ctx.mask), *(common + tail))
+                else:
+                    call('cy_conv1_bn_bwd_onepass_bf16' if da_bf16 else 'cy_conv1_bn_bwd_onepass', _ptr(x), _ptr(weight),
+                         _ptr(bias), _ptr(da), *(common + tail))
+        else:
+            with timer.range('conv1_bn_bwd_reduce/' + cfg.name):
+                call('cy_conv1_bn_bwd_reduce_bf16' if da_bf16 else 'cy_conv1_bn_bwd_reduce', _ptr(x), _ptr(weight), _ptr(bias),
+                     _ptr(da), *(common + (_ptr(redc), B, Hi, Wi, N, st)))
+            red = _empty((N, 2), x, torch.float64)
+            dist, world = _sync_world()
+            # copies folded (and, data parallel, pre-scaled by 1 / world so that the all-reduce SUM is the mean)
+            call('cy_bn_red_fold', _ptr(redc), STATS_COPIES, 1.0 / world, _ptr(red), _ptr(dgamma), _ptr(dbeta), N, st)
+            if dist is not None:
+                dist.all_reduce(red)
+                call('cy_bn_red_fold', _ptr(red), 1, 1.0, None, _ptr(dgamma), _ptr(dbeta), N, st)
+            with timer.range('conv1_bn_bwd_wgrad/' + cfg.name):
+                call('cy_conv1_bn_bwd_wgrad_bf16' if da_bf16 else 'cy_conv1_bn_bwd_wgrad', _ptr(x), _ptr(weight), _ptr(bias),
+                     _ptr(da), *(common + (_ptr(red), B * Hi * Wi, _ptr(dW), _ptr(ws), B, Hi, Wi, N, st)))
+        dbias = _const_zeros(N, x) if ctx.has_bias else None     # in front of BatchNorm: analytically zero
+        return None, dW, dbias, dgamma, dbeta, None, None
+
+
+class _ConvBnBlock(torch.autograd.Function):
+    """conv -> BatchNorm (batch statistics from the conv epilogue) -> [Leaky]ReLU, saving only x and z: every BatchNorm block
+    that is not the first layer's training block.  hin: the hand-over of a producer whose raw output x is (the BatchNorm +
+    LeakyReLU of that block are applied on this block's loads).  cfg.defer_act: returns (z, BnHandover) and leaves the
+    activation to the consumer.  Eval mode runs on the running statistics -- folded into weights / bias where that is one
+    launch -- and has no backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, cfg, plan, hin):
         x, weight = _f32(x, 'conv input'), _f32(weight, 'conv weight')
         st = _stream()
         N = weight.shape[0]
         bn = cfg.bn
-        ctx.cfg, ctx.has_bias, ctx.bn_train = cfg, bias is not None, False
-        ctx.set_materialize_grads(False)      # the (scale, shift) side outputs never get a gradient: no zero tensors for them
-        ctx.holder = None
-        ctx.in_affine = ina = (in_scale, in_shift, float(cfg.in_slope)) if cfg.in_slope is not None else None
-        if bn is None:
-            if cfg.defer_act:
-                raise _lib.HipExtensionError('defer_act needs a BatchNorm block')
-            relu = cfg.slope is not None and cfg.slope == 0.0
-            z = conv_forward(x, weight, bias, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, None, relu, cfg.name, ina)
-            out = z
-            if cfg.slope is not None and not relu:
-                out = torch.empty_like(z)
-                call('cy_affine_act', _ptr(z), _ptr(out), None, None, float(cfg.slope), z.numel() // N, N, st)
-            ctx.save_for_backward(x, weight, z)
-            return out
+        ctx.cfg, ctx.has_bias, ctx.bn_train, ctx.hin, ctx.hout = cfg, bias is not None, bool(bn.training), hin, None
+        ctx.set_materialize_grads(False)      # the hand-over that leaves next to z is no tensor and gets no gradient
+        ctx.in_affine = ina = None if hin is None else (hin.scale, hin.shift, hin.slope)
         scale, shift, mean, invstd = (_empty((N,), x) for _ in range(4))
         slope = 1.0 if cfg.slope is None else float(cfg.slope)
-        plan = conv_plan(x.shape, N, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in)
-        # the first block (csrc/conv1.hip): z is never written -- this pass only takes the statistics, the activation
-        # pass and both backward passes recompute the convolution
-        ctx.conv1_m2 = ctx.conv1_mask = None
-        ctx.conv1_fused = bool(plan.conv1_bwd and bn.training and not cfg.defer_act and not x.requires_grad and 0.0 <= slope <= 1.0)
         if bn.training:
             stats = zero_pool.take((STATS_COPIES, N, 2), torch.float64, x.device)
-            if ctx.conv1_fused:
-                Bx, _, Hx, Wx = x.shape
-                if plan.conv1_moments:
-                    # sum z and sum z^2 from the moment matrix of the input patches: the layer is not computed for them
-                    wsm = _empty((query('cy_conv1_3x3_stats_ws_floats', Bx, Hx),), x)
-                    with timer.range('conv1_fwd_stats/' + cfg.name):
-                        call('cy_conv1_3x3_stats', _ptr(x), _ptr(weight.contiguous()), _ptr(bias), _ptr(stats), _ptr(wsm),
-                             Bx, Hx, Wx, N, st)
-                    off = query('cy_conv1_3x3_stats_m2_offset', Bx, Hx)
-                    ctx.conv1_m2 = wsm[off:off + 2048]        # the double M2[32][32]: the one-pass backward reads it
-                else:
-                    with timer.range('conv1_fwd_stats/' + cfg.name):
-                        call('cy_conv1_3x3_fwd', _ptr(x), _ptr(weight.contiguous()), _ptr(bias), None, _ptr(stats), None, None,
-                             1.0, Bx, Hx, Wx, N, st)
-                z = x.new_empty(0)
-                P = Bx * Hx * Wx
-            else:
-                z = conv_forward(x, weight, bias, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, stats, False, cfg.name, ina)
-                P = z.numel() // N
-            _bn_finalize(stats, P, gamma, beta, bn, scale, shift, mean, invstd, N, st)
-            ctx.bn_train = True
+            z = conv_forward(x, weight, bias, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, stats, False, cfg.name, ina)
+            _bn_finalize(stats, z.numel() // N, gamma, beta, bn, scale, shift, mean, invstd, N, st)
         else:
-            ctx.folded = bool(FOLD_EVAL_BN and not cfg.defer_act and ina is None and 0.0 <= slope <= 1.0)
-            if ctx.folded:
+            if FOLD_EVAL_BN and not cfg.defer_act and ina is None and 0.0 <= slope <= 1.0:
                 # eval mode (predict_fns.py:38-43, 65-69): ONE launch per block.  The first layer applies scale / shift in its
                 # own epilogue (its kernel takes them); every other layer runs on weights and bias with the BatchNorm folded in
                 ctx.save_for_backward()
@@ -578,159 +727,71 @@ class _ConvBlock(torch.autograd.Function):
                 Wf, bf = fold_eval_bn(weight, bias, gamma, beta, bn)
                 return _leave(conv_forward(x, Wf, bf, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, None, False, cfg.name, None, lrelu=slope), cfg, st)
             z = conv_forward(x, weight, bias, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, None, False, cfg.name, ina)
-            P = z.numel() // N
             call('cy_bn_eval_scale_shift', _ptr(gamma), _ptr(beta), _ptr(bn.running_mean), _ptr(bn.running_var),
                  float(bn.eps), _ptr(scale), _ptr(shift), N, st)
-        ctx.P = P
-        ctx.save_for_backward(x, weight, z, scale, shift, mean, invstd, gamma, *([bias] if bias is not None else []))
-        if cfg.defer_act:                     # the consumer block applies lrelu(z * scale + shift) on its loads
-            ctx.mark_non_differentiable(scale, shift)
-            # hand-over for the backward: the consumer's input-gradient kernel can also produce this block's
-            # BatchNorm-backward sums (it has z and the gradient in registers) and leaves them in holder['red']
-            ctx.holder = cfg.out_holder = {'mean': mean, 'invstd': invstd, 'red': None} if ctx.bn_train else None
-            return z, scale, shift
+        ctx.save_for_backward(x, weight, z, scale, shift, mean, invstd, gamma)
+        if cfg.defer_act:
+            # the consumer applies lrelu(z * scale + shift) on its loads; in training mode its input-gradient kernel can also
+            # sum this block's BatchNorm backward, for which it needs mean / invstd
+            ctx.hout = BnHandover(scale, shift, mean if ctx.bn_train else None, invstd if ctx.bn_train else None, slope)
+            return z, ctx.hout
         if plan.conv1 and 0.0 <= slope <= 1.0:
-            if plan.conv1_signmask and ctx.conv1_m2 is not None and not cfg.out_bf16 and _sync_world()[0] is None:
-                # the training forward of the fp32 first block: the one-pass backward will want the sign of y and nothing else of z
-                Bx, _, Hx, Wx = x.shape
-                ctx.conv1_mask = torch.empty((query('cy_conv1_signmask_bytes', Bx, Hx, Wx, N),), dtype=torch.uint8, device=x.device)
-            return conv1_affine_act(x, weight, bias, scale, shift, slope, cfg.name, cfg.out_bf16, ctx.conv1_mask)
+            return conv1_affine_act(x, weight, bias, scale, shift, slope, cfg.name, cfg.out_bf16)
         out = torch.empty_like(z)
-        call('cy_affine_act', _ptr(z), _ptr(out), _ptr(scale), _ptr(shift), slope, P, N, st)
+        call('cy_affine_act', _ptr(z), _ptr(out), _ptr(scale), _ptr(shift), slope, z.numel() // N, N, st)
         return _leave(out, cfg, st)
 
     @staticmethod
-    def backward(ctx, da, *unused):
+    def backward(ctx, da, _hout=None):
         cfg = ctx.cfg
-        if da is None:
-            raise _lib.HipExtensionError('conv block %s: no gradient reached its output' % cfg.name)
-        if getattr(ctx, 'folded', False):
+        da = _grad_f32(da, cfg)
+        if not ctx.bn_train:
             raise _lib.HipExtensionError('backward through an eval-mode BatchNorm block is not implemented')
-        da_bf16 = da.dtype == torch.bfloat16 and cfg.out_bf16
-        if da_bf16 and not (cfg.bn is not None and ctx.bn_train and ctx.conv1_fused):
-            daf = torch.empty(da.shape, dtype=torch.float32, device=da.device)   # only the first-layer kernels read a bf16 gradient
-            call('cy_cast_bf16_f32', _ptr(da.contiguous()), _ptr(daf), da.numel(), _stream())
-            da, da_bf16 = daf, False
-        if not da_bf16:
-            da = _f32(da, 'grad')
         st = _stream()
-        saved = ctx.saved_tensors
-        x, weight, z = saved[0], saved[1], saved[2]
+        x, weight, z, scale, shift, mean, invstd, gamma = ctx.saved_tensors
         N = weight.shape[0]
-        P = ctx.P if cfg.bn is not None else z.numel() // N
+        P = z.numel() // N
         plan = conv_plan(x.shape, N, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in)
-        dgamma = dbeta = dbias = dW = None
-        if cfg.bn is None:
-            if cfg.slope is not None:
-                dz = torch.empty_like(z)
-                call('cy_act_bwd', _ptr(z), _ptr(da), _ptr(dz), float(cfg.slope), z.numel(), st)
-            else:
-                dz = da
-            if ctx.has_bias:
-                dbias = _empty((N,), z)
-                call('cy_channel_sum', _ptr(dz), _ptr(dbias), P, N, st)
+        slope = 1.0 if cfg.slope is None else float(cfg.slope)
+        given = ctx.hout.take_red() if ctx.hout is not None else None
+        if given is not None:
+            # summed by the consumer block's input-gradient epilogues, whose stride-2 Winograd kernel (and the fused max-pool
+            # backward) has then also applied the activation's derivative to da already
+            red, premasked = given
+            if premasked:
+                slope = 1.0
         else:
-            if not ctx.bn_train:
-                raise _lib.HipExtensionError('backward through an eval-mode BatchNorm block is not implemented')
-            scale, shift, mean, invstd, gamma = saved[3:8]
-            slope = 1.0 if cfg.slope is None else float(cfg.slope)
-            if ctx.conv1_fused:
-                da = da.contiguous()
-                # the first block: both BatchNorm-backward passes recompute z tile by tile and read only da; dz is
-                # formed in registers in the layout the weight-gradient MFMA consumes (csrc/conv1.hip)
-                bias_t = saved[8] if ctx.has_bias else None
-                B, _, Hi, Wi = x.shape
-                redc = zero_pool.take((STATS_COPIES, N, 2), torch.float64, z.device)
-                dW, dbeta, dgamma = _empty(tuple(weight.shape), z), _empty((N,), z), _empty((N,), z)
-                ws = _empty((query('cy_conv1_bn_bwd_wgrad_ws_floats', B, Hi, Wi, N),), z)
-                dbias = _const_zeros(N, z) if ctx.has_bias else None
-                if plan.conv1_onepass and ctx.conv1_m2 is not None and _sync_world()[0] is None:
-                    # one pass over da: sum d and the weight gradient OF d; the rest follows from the forward's patch moments
-                    with timer.range('conv1_bn_bwd_onepass/' + cfg.name):
-                        if ctx.conv1_mask is not None and not da_bf16 and da.data_ptr() % 16 == 0:
-                            call('cy_conv1_bn_bwd_onepass_mask', _ptr(x), _ptr(weight), _ptr(bias_t), _ptr(da), _ptr(ctx.conv1_mask),
-                                 _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), slope, _ptr(ctx.conv1_m2), _ptr(redc), _ptr(dW),
-                                 _ptr(dgamma), _ptr(dbeta), None, _ptr(ws), B, Hi, Wi, N, st)
-                        else:
-                            call('cy_conv1_bn_bwd_onepass_bf16' if da_bf16 else 'cy_conv1_bn_bwd_onepass', _ptr(x), _ptr(weight),
-                                 _ptr(bias_t), _ptr(da), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), slope,
-                                 _ptr(ctx.conv1_m2), _ptr(redc), _ptr(dW), _ptr(dgamma), _ptr(dbeta), None, _ptr(ws), B, Hi, Wi, N, st)
-                    return None, dW, dbias, dgamma, dbeta, None, None, None
-                with timer.range('conv1_bn_bwd_reduce/' + cfg.name):
-                    call('cy_conv1_bn_bwd_reduce_bf16' if da_bf16 else 'cy_conv1_bn_bwd_reduce', _ptr(x), _ptr(weight), _ptr(bias_t), _ptr(da), _ptr(scale), _ptr(shift),
-                         _ptr(mean), _ptr(invstd), slope, _ptr(redc), B, Hi, Wi, N, st)
-                red = _empty((N, 2), z, torch.float64)
-                dist, world = _sync_world()
-                # copies folded (and, data parallel, pre-scaled by 1 / world so that the all-reduce SUM is the mean)
-                call('cy_bn_red_fold', _ptr(redc), STATS_COPIES, 1.0 / world, _ptr(red), _ptr(dgamma), _ptr(dbeta), N, st)
-                if dist is not None:
-                    dist.all_reduce(red)
-                    call('cy_bn_red_fold', _ptr(red), 1, 1.0, None, _ptr(dgamma), _ptr(dbeta), N, st)
-                with timer.range('conv1_bn_bwd_wgrad/' + cfg.name):
-                    call('cy_conv1_bn_bwd_wgrad_bf16' if da_bf16 else 'cy_conv1_bn_bwd_wgrad', _ptr(x), _ptr(weight), _ptr(bias_t), _ptr(da), _ptr(scale), _ptr(shift),
-                         _ptr(mean), _ptr(invstd), slope, _ptr(red), P, _ptr(dW), _ptr(ws), B, Hi, Wi, N, st)
-                return None, dW, dbias, dgamma, dbeta, None, None, None
-            premasked = False
-            if ctx.holder is not None and ctx.holder.get('red') is not None:
-                red = ctx.holder['red']        # summed by the consumer block's input-gradient epilogues
-                ctx.holder['red'] = None
-                # ... whose stride-2 Winograd kernel has then also applied the activation's derivative to da already
-                premasked = bool(ctx.holder.pop('premasked', False))
-                if premasked:
-                    slope = 1.0
+            red, premasked = _empty((N, 2), z, torch.float64), False
+            call('cy_bn_bwd_reduce', _ptr(z), _ptr(da), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), slope,
+                 _ptr(red), P, N, st)
+        red = _sync_red(red, N, st)
+        dz = torch.empty_like(z)
+        dgamma, dbeta = _empty((N,), z), _empty((N,), z)
+        # a bias in front of BatchNorm has an analytically zero gradient: sum(dz) == 0
+        dbias = _const_zeros(N, z) if ctx.has_bias else None
+        if plan.wgrad_bn and ctx.hin is None:
+            # pass 2 of the BatchNorm backward inside the Winograd weight-gradient kernel, which has every dz element in
+            # registers on its way to LDS anyway and writes it out for the input-gradient kernel
+            red = red.contiguous()
+            call('cy_bn_param_grad', _ptr(red), _ptr(dgamma), _ptr(dbeta), N, st)
+            B_, Hi, Wi, Cin = x.shape
+            dW = _empty(tuple(weight.shape), z)
+            if premasked and plan.wgrad_bn4:
+                ws = _empty((query('cy_wino4_wgrad_ws_floats', B_, Hi, Wi, Cin, N),), z)
+                with timer.range('conv_wino4_wgrad_bn/' + cfg.name):
+                    call('cy_conv3x3_winograd4_wgrad_bn', _ptr(x), _ptr(z), _ptr(da), _ptr(dz), _ptr(scale),
+                         _ptr(mean), _ptr(invstd), _ptr(red), P, _ptr(dW), _ptr(ws), B_, Hi, Wi, Cin, N, st)
             else:
-                red = _empty((N, 2), z, torch.float64)
-                call('cy_bn_bwd_reduce', _ptr(z), _ptr(da), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), slope,
-                     _ptr(red), P, N, st)
-            dist, world = _sync_world()
-            if dist is not None:
-                # global sums / world: the apply kernel divides by the LOCAL pixel count, which then gives the global
-                # means; dgamma / dbeta come out as (global sum) / world, what the gradient all-reduce MEAN expects
-                red = red.contiguous()
-                call('cy_bn_red_fold', _ptr(red), 1, 1.0 / world, _ptr(red), None, None, N, st)    # in place: sum of the pre-scaled = mean
-                dist.all_reduce(red)
-            dz = torch.empty_like(z)
-            dgamma, dbeta = _empty((N,), z), _empty((N,), z)
-            if ctx.has_bias:
-                # a bias in front of BatchNorm has an analytically zero gradient: sum(dz) == 0
-                dbias = _const_zeros(N, z)
-            if plan.wgrad_bn and ctx.in_affine is None:
-                # pass 2 of the BatchNorm backward inside the Winograd weight-gradient kernel, which has every dz element in
-                # registers on its way to LDS anyway and writes it out for the input-gradient kernel
-                red = red.contiguous()
-                call('cy_bn_param_grad', _ptr(red), _ptr(dgamma), _ptr(dbeta), N, st)
-                B_, Hi, Wi, Cin = x.shape
-                dW = _empty(tuple(weight.shape), z)
-                if premasked and plan.wgrad_bn4:
-                    ws = _empty((query('cy_wino4_wgrad_ws_floats', B_, Hi, Wi, Cin, N),), z)
-                    with timer.range('conv_wino4_wgrad_bn/' + cfg.name):
-                        call('cy_conv3x3_winograd4_wgrad_bn', _ptr(_f32(x, 'conv input')), _ptr(z), _ptr(da), _ptr(dz), _ptr(scale),
-                             _ptr(mean), _ptr(invstd), _ptr(red), P, _ptr(dW), _ptr(ws), B_, Hi, Wi, Cin, N, st)
-                else:
-                    ws = _empty((query('cy_wino_wgrad_ws_floats', B_, Cin, N),), z)
-                    with timer.range('conv_wino_wgrad_bn/' + cfg.name):
-                        call('cy_conv3x3_winograd_wgrad_bn', _ptr(_f32(x, 'conv input')), _ptr(z), _ptr(da), _ptr(dz), _ptr(scale),
-                             _ptr(shift), _ptr(mean), _ptr(invstd), slope, 1 if premasked else 0, _ptr(red), P, _ptr(dW), _ptr(ws),
-                             B_, Hi, Wi, Cin, N, st)
-            else:
-                call('cy_bn_bwd_apply', _ptr(z), _ptr(da), _ptr(dz), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd),
-                     _ptr(gamma), slope, _ptr(red), _ptr(dgamma), _ptr(dbeta), P, N, st)
-        if dW is None:
+                ws = _empty((query('cy_wino_wgrad_ws_floats', B_, Cin, N),), z)
+                with timer.range('conv_wino_wgrad_bn/' + cfg.name):
+                    call('cy_conv3x3_winograd_wgrad_bn', _ptr(x), _ptr(z), _ptr(da), _ptr(dz), _ptr(scale),
+                         _ptr(shift), _ptr(mean), _ptr(invstd), slope, 1 if premasked else 0, _ptr(red), P, _ptr(dW), _ptr(ws),
+                         B_, Hi, Wi, Cin, N, st)
+        else:
+            call('cy_bn_bwd_apply', _ptr(z), _ptr(da), _ptr(dz), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd),
+                 _ptr(gamma), slope, _ptr(red), _ptr(dgamma), _ptr(dbeta), P, N, st)
             dW = conv_wgrad(x, dz, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, cfg.name, ctx.in_affine, plan)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if plan.dgrad is None:
-                raise _lib.HipExtensionError('input gradient of an NCHW-input convolution is not implemented')
-            fuse, h = None, cfg.in_holder
-            if plan.dgrad_bn_fuse and ctx.in_affine is not None and h is not None:
-                bred = zero_pool.take((STATS_COPIES, x.shape[3], 2), torch.float64, x.device)
-                fuse = (x, ctx.in_affine[0], ctx.in_affine[1], h['mean'], h['invstd'], ctx.in_affine[2], bred)
-            dx = conv_dgrad(dz, weight, tuple(x.shape), cfg.k, cfg.stride, cfg.pad, cfg.name, fuse, plan)
-            if fuse is not None:
-                h['premasked'] = plan.dgrad_premasks
-                h['red'] = _empty((x.shape[3], 2), x, torch.float64)
-                call('cy_bn_red_fold', _ptr(bred), STATS_COPIES, 1.0, _ptr(h['red']), None, None, x.shape[3], st)
-        return dx, dW, dbias, dgamma, dbeta, None, None, None
+        return _input_grad(ctx, dz, x, weight, plan, st), dW, dbias, dgamma, dbeta, None, None, None
 
 
 # ------------------------------------------------------------------------------------------------ bf16 convolution path
@@ -894,10 +955,11 @@ class _ConvBlockBF16(torch.autograd.Function):
     """conv -> BatchNorm (batch statistics from the conv epilogue) -> LeakyReLU on the bf16 kernels: x, the raw conv output
     z and the activation are bf16 NHWC; statistics, scale / shift and all parameter gradients are fp32 / double.
     cfg.out_f32: the activation leaves in fp32 (its consumer is an fp32 kernel: the routing head); cfg.in_f32: x was
-    cast from an fp32 producer, whose backward wants its gradient in fp32."""
+    cast from an fp32 producer, whose backward wants its gradient in fp32.  hin: the BnHandover of the bf16 block in front, or
+    None.  Returns (activation, this block's BnHandover for its consumer -- None where the consumer cannot sum for it)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, cfg):
+    def forward(ctx, x, weight, bias, gamma, beta, cfg, hin):
         st = _stream()
         if cfg.in_f32:
             # the producer is an fp32 kernel (the first block): round its activation to bf16 HERE, so that autograd sees an
@@ -911,7 +973,7 @@ class _ConvBlockBF16(torch.autograd.Function):
         bn = cfg.bn
         if bn is None or cfg.slope is None:
             raise _lib.HipExtensionError('the bf16 path is built for conv -> BatchNorm -> LeakyReLU blocks')
-        ctx.cfg, ctx.has_bias = cfg, bias is not None
+        ctx.cfg, ctx.has_bias, ctx.bn_train, ctx.hin, ctx.hout = cfg, bias is not None, bool(bn.training), hin, None
         scale, shift, mean, invstd = (_empty((N,), weight) for _ in range(4))
         if bn.training:
             stats = zero_pool.take((STATS_COPIES, N, 2), torch.float64, x.device)
@@ -921,50 +983,41 @@ class _ConvBlockBF16(torch.autograd.Function):
         else:
             if FOLD_EVAL_BN and 0.0 <= float(cfg.slope) <= 1.0:     # eval mode: ONE launch, BatchNorm folded into weights / bias
                 Wf, bf = fold_eval_bn(weight, bias, gamma, beta, bn)
-                ctx.bn_train = False
                 ctx.save_for_backward()
-                return conv_forward_bf16(x, Wf, bf, cfg.k, cfg.stride, cfg.pad, None, cfg.name, lrelu=float(cfg.slope), out_f32=cfg.out_f32)
+                return conv_forward_bf16(x, Wf, bf, cfg.k, cfg.stride, cfg.pad, None, cfg.name, lrelu=float(cfg.slope), out_f32=cfg.out_f32), None
             z = conv_forward_bf16(x, weight, bias, cfg.k, cfg.stride, cfg.pad, None, cfg.name)
             P = z.numel() // N
             call('cy_bn_eval_scale_shift', _ptr(gamma), _ptr(beta), _ptr(bn.running_mean), _ptr(bn.running_var), float(bn.eps),
                  _ptr(scale), _ptr(shift), N, st)
-        ctx.bn_train, ctx.P = bool(bn.training), P
         out_f32 = cfg.out_f32
         out = torch.empty(z.shape, dtype=torch.float32 if out_f32 else torch.bfloat16, device=z.device)
         call('cy_affine_act_bf16', _ptr(z), _ptr(out), _ptr(scale), _ptr(shift), float(cfg.slope), P, N, 1 if out_f32 else 0, st)
         ctx.save_for_backward(x, weight, z, scale, shift, mean, invstd)
-        h = cfg.out_holder
-        if h is not None:
+        if bn.training and not out_f32:
             # what the CONSUMER block's input-gradient epilogue needs for this block's BatchNorm-backward sums (bf16 output only)
-            h.clear()
-            if bn.training and not out_f32:
-                h.update(z=z, scale=scale, shift=shift, mean=mean, invstd=invstd, slope=float(cfg.slope), red=None)
-        return out
+            ctx.hout = BnHandover(scale, shift, mean, invstd, cfg.slope, z)
+        return out, ctx.hout
 
     @staticmethod
-    def backward(ctx, da):
+    def backward(ctx, da, _hout=None):
         cfg = ctx.cfg
         if not ctx.bn_train:
             raise _lib.HipExtensionError('backward through an eval-mode BatchNorm block is not implemented')
         x, weight, z, scale, shift, mean, invstd = ctx.saved_tensors
         st = _stream()
-        N, P = weight.shape[0], ctx.P
+        N = weight.shape[0]
+        P = z.numel() // N
         da_f32 = da.dtype == torch.float32
         da = _f32(da, 'grad') if da_f32 else _bf(da, 'grad')
         slope = float(cfg.slope)
-        ho = cfg.out_holder
-        if ho is not None and ho.get('red') is not None and not da_f32:
-            red = ho['red']                    # summed by the consumer block's input-gradient epilogues, which also stored da premasked
-            ho['red'] = None
-            slope = 1.0
+        given = ctx.hout.take_red() if ctx.hout is not None and not da_f32 else None
+        if given is not None:
+            red, slope = given[0], 1.0         # summed by the consumer block's input-gradient epilogues, which also stored da premasked
         else:
             red = _empty((N, 2), weight, torch.float64)
             call('cy_bn_bwd_reduce_bf16', _ptr(z), _ptr(da), 1 if da_f32 else 0, _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd),
                  slope, _ptr(red), P, N, st)
-        dist, world = _sync_world()
-        if dist is not None:
-            call('cy_bn_red_fold', _ptr(red), 1, 1.0 / world, _ptr(red), None, None, N, st)
-            dist.all_reduce(red)
+        red = _sync_red(red, N, st)
         dz = torch.empty_like(z)
         dgamma, dbeta = _empty((N,), weight), _empty((N,), weight)
         Bx, Hx, Wx, Cx = x.shape
@@ -984,30 +1037,40 @@ class _ConvBlockBF16(torch.autograd.Function):
             dW = conv_wgrad_bf16(x, dz, cfg.k, cfg.stride, cfg.pad, cfg.name)
         dx = None
         if ctx.needs_input_grad[0]:
-            in_f32, hi = cfg.in_f32, cfg.in_holder
+            in_f32, hi = cfg.in_f32, ctx.hin
             fuse = None
-            if (FUSE_BN_BWD_REDUCE_BF16 and hi is not None and hi.get('z') is not None and not in_f32
-                    and tuple(hi['z'].shape) == tuple(x.shape)):
+            if FUSE_BN_BWD_REDUCE_BF16 and hi is not None and not in_f32 and tuple(hi.z.shape) == tuple(x.shape):
                 Cin = x.shape[3]
                 bred = zero_pool.take((STATS_COPIES, Cin, 2), torch.float64, x.device)
-                fuse = (hi['z'], hi['scale'], hi['shift'], hi['mean'], hi['invstd'], hi['slope'], bred)
+                fuse = (hi.z, hi.scale, hi.shift, hi.mean, hi.invstd, hi.slope, bred)
             dx = conv_dgrad_bf16(dz, weight, tuple(x.shape), cfg.k, cfg.stride, cfg.pad, in_f32, cfg.name, fuse)
             if fuse is not None:
-                hi['red'] = _empty((x.shape[3], 2), weight, torch.float64)
-                call('cy_bn_red_fold', _ptr(fuse[6]), STATS_COPIES, 1.0, _ptr(hi['red']), None, None, x.shape[3], st)
+                red_in = _empty((x.shape[3], 2), weight, torch.float64)
+                call('cy_bn_red_fold', _ptr(bred), STATS_COPIES, 1.0, _ptr(red_in), None, None, x.shape[3], st)
+                hi.give_red(red_in, True)
         dbias = _const_zeros(N, weight) if ctx.has_bias else None       # in front of BatchNorm: analytically zero
-        return dx, dW, dbias, dgamma, dbeta, None
+        return dx, dW, dbias, dgamma, dbeta, None, None
 
 
-def conv_block_bf16(x, weight, bias, gamma, beta, cfg):
-    return _ConvBlockBF16.apply(x, weight, bias, gamma, beta, cfg)
+def conv_block_bf16(x, weight, bias, gamma, beta, cfg, handover=None):
+    """One bf16 conv -> BatchNorm -> LeakyReLU block: (activation, BnHandover or None).  handover: what the bf16 block in
+    front returned, whose BatchNorm-backward sums this block's input-gradient kernel then leaves in it."""
+    return _ConvBlockBF16.apply(x, weight, bias, gamma, beta, cfg, handover)
 
 
-def conv_block(x, weight, bias, gamma, beta, cfg, in_scale=None, in_shift=None):
-    """One conv (+BN) (+activation) block.  cfg.defer_act: returns (z, scale, shift) instead of the activation; the next
-    block then runs with cfg.in_slope set and these tensors as in_scale / in_shift (its input gradient is the gradient
-    with respect to the ACTIVATED value, which is what this block's backward expects)."""
-    return _ConvBlock.apply(x, weight, bias, gamma, beta, cfg, in_scale, in_shift)
+def conv_block(x, weight, bias, gamma, beta, cfg, handover=None):
+    """One conv (+BN) (+activation) block on the fp32 kernels, as one of three Functions: without BatchNorm, the first layer's
+    training block, every other BatchNorm block.  cfg.defer_act: returns (z, BnHandover) instead of the activation; the next
+    block (or ops.affine_act_maxpool) then takes that object as `handover`, with z as its x, and applies the producer's
+    BatchNorm + LeakyReLU on its loads (its input gradient is the gradient with respect to the ACTIVATED value, which is
+    what the producer's backward expects)."""
+    if cfg.bn is None:
+        return _ConvBlockNoBn.apply(x, weight, bias, cfg, handover)
+    plan = conv_plan(x.shape, weight.shape[0], cfg.k, cfg.stride, cfg.pad, cfg.nchw_in)
+    if (plan.conv1_bwd and cfg.bn.training and not cfg.defer_act and not x.requires_grad
+            and (cfg.slope is None or 0.0 <= float(cfg.slope) <= 1.0)):
+        return _Conv1TrainBlock.apply(x, weight, bias, gamma, beta, cfg, plan)
+    return _ConvBnBlock.apply(x, weight, bias, gamma, beta, cfg, plan, handover)
 
 
 # ------------------------------------------------------------------------------------------------ routing
@@ -1201,38 +1264,38 @@ def pool_fusable(C, H, W, slope):
 
 class _AffineActMaxPool(torch.autograd.Function):
     """y = maxpool2(lrelu(z * scale + shift)) of a block that deferred its activation (ConvBlockCfg.defer_act); plays the CONSUMER of the
-    producer's hand-over dict: its backward returns the premasked gradient d = [pos == argmax] dy lrelu'(.) as the gradient of z and leaves
-    the producer's BatchNorm-backward sums in holder['red'] (models.py:135 ... 195: nn.LeakyReLU + nn.MaxPool2d of the DarkNet blocks)."""
+    producer's BnHandover h: its backward returns the premasked gradient d = [pos == argmax] dy lrelu'(.) as the gradient of z and gives
+    the producer's BatchNorm-backward sums to h (models.py:135 ... 195: nn.LeakyReLU + nn.MaxPool2d of the DarkNet blocks)."""
 
     @staticmethod
-    def forward(ctx, z, scale, shift, slope, holder):
+    def forward(ctx, z, h):
         z = _f32(z, 'conv output')
         B, H, W, Cc = z.shape
         y = _empty((B, H // 2, W // 2, Cc), z)
         idx = torch.empty((B, H // 2, W // 2, Cc), dtype=torch.uint8, device=z.device)
         with timer.range('affine_act_maxpool'):
-            call('cy_affine_act_maxpool2', _ptr(z), _ptr(scale), _ptr(shift), float(slope), _ptr(y), _ptr(idx), B, H // 2, W // 2, Cc, _stream())
-        ctx.save_for_backward(z, scale, shift, idx)
-        ctx.slope, ctx.holder = float(slope), holder
+            call('cy_affine_act_maxpool2', _ptr(z), _ptr(h.scale), _ptr(h.shift), h.slope, _ptr(y), _ptr(idx), B, H // 2, W // 2, Cc, _stream())
+        ctx.save_for_backward(z, idx)
+        ctx.h = h
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        z, scale, shift, idx = ctx.saved_tensors
+        z, idx = ctx.saved_tensors
         B, H, W, Cc = z.shape
         dy = _f32(dy, 'pooled gradient')
-        h = ctx.holder
+        h = ctx.h
         d = torch.empty_like(z)
         red = zero_pool.take((Cc, 2), torch.float64, z.device)
         with timer.range('maxpool_bwd_bn'):
-            call('cy_maxpool2_bwd_bn', _ptr(dy), _ptr(idx), _ptr(z), _ptr(scale), _ptr(shift), _ptr(h['mean']), _ptr(h['invstd']), ctx.slope,
+            call('cy_maxpool2_bwd_bn', _ptr(dy), _ptr(idx), _ptr(z), _ptr(h.scale), _ptr(h.shift), _ptr(h.mean), _ptr(h.invstd), h.slope,
                  _ptr(d), _ptr(red), B, H // 2, W // 2, Cc, _stream())
-        h['red'], h['premasked'] = red, True
-        return d, None, None, None, None
+        h.give_red(red, True)
+        return d, None
 
 
-def affine_act_maxpool(z, scale, shift, slope, holder):
-    return _AffineActMaxPool.apply(z, scale, shift, slope, holder)
+def affine_act_maxpool(z, handover):
+    return _AffineActMaxPool.apply(z, handover)
 
 
 class _Upsample(torch.autograd.Function):

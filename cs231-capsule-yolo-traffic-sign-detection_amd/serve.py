@@ -16,6 +16,8 @@ serving loop must not die on one degenerate box.  They come back with class -1 a
 launch behind `cy_pack_detections` (`cy_track_update`, the rule is in include/capsyolo_hip.h), whose state stays in device memory and
 whose record travels beside the detections' record under the same event wait.  `Detections.tracks` is then a `Tracks`.
 """
+import gc
+
 import numpy as np
 import torch
 
@@ -365,6 +367,10 @@ class SignDetector(object):
         torch.cuda.current_stream(self.dev).wait_stream(side)
         torch.cuda.synchronize(self.dev)
         graph = torch.cuda.CUDAGraph()
+        # torch.cuda.graph no longer collects on entry, and a dead cycle that holds a pinned buffer or an event (a detector that
+        # raised: exception -> traceback -> frame -> state) must not be finalised while the stream captures: the frees record and
+        # query events, which a capture refuses, and the error is thrown inside a destructor
+        gc.collect()
         with torch.cuda.graph(graph):
             st.keep = self._device_steps(st)
         st.graph, st.graph_key = graph, self._weights_key()

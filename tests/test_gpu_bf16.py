@@ -240,7 +240,7 @@ def test_conv_bn_lrelu_block_bf16(case):
     cfg = ops.ConvBlockCfg(k, s, 1, False, hb, 0.1, 'blk')
     cfg.out_f32, cfg.in_f32 = out_f32, False
     xg = x.permute(0, 2, 3, 1).contiguous().cuda().to(BF).requires_grad_(True)
-    out = ops.conv_block_bf16(xg, hc.weight, hc.bias, hb.weight, hb.bias, cfg)
+    out, _ = ops.conv_block_bf16(xg, hc.weight, hc.bias, hb.weight, hb.bias, cfg)
     assert out.dtype == (torch.float32 if out_f32 else BF)
     gag = ga.permute(0, 2, 3, 1).contiguous().cuda()
     out.backward(gag if out_f32 else gag.to(BF))

@@ -1301,9 +1301,9 @@ def test_fused_batchnorm_activation_maxpool_and_its_backward(case):
     act = F.leaky_relu(zd * scale.double() + shift.double(), slope)
     pooled, ind = F.max_pool2d(act.permute(0, 3, 1, 2), 2, return_indices=True)
     pooled.backward(dy.permute(0, 3, 1, 2).double())
-    holder = {'mean': mean.to(dev()), 'invstd': invstd.to(dev()), 'red': None}
+    holder = ops.BnHandover(scale.to(dev()), shift.to(dev()), mean.to(dev()), invstd.to(dev()), slope)
     zg = z.to(dev()).requires_grad_(True)
-    y = ops.affine_act_maxpool(zg, scale.to(dev()), shift.to(dev()), slope, holder)
+    y = ops.affine_act_maxpool(zg, holder)
     close(y.permute(0, 3, 1, 2), pooled, 1e-6, 1e-6)
     assert int(torch.count_nonzero(y[0, 0, 0] - float(F.leaky_relu(torch.tensor(0.25) * scale + shift, slope)[0]))) <= C   # (shape check only)
     ops.zero_pool.reset(torch.device('cuda', 0))
@@ -1311,10 +1311,11 @@ def test_fused_batchnorm_activation_maxpool_and_its_backward(case):
     d = zg.grad
     # autograd's dz = d * scale (chain through z * scale + shift); the kernel hands over d itself (the producer applies the BatchNorm)
     close(d * scale.to(dev()), zd.grad.float(), 1e-5, 1e-6)
-    assert holder['premasked'] is True
+    red, premasked = holder.take_red()
+    assert premasked is True
     dref = (zd.grad / scale.double()).detach()
     xhat = (z.double() - mean.double()) * invstd.double()
-    red = holder['red'].cpu()
+    red = red.cpu()
     close(red[:, 0], dref.sum(dim=(0, 1, 2)), 1e-5, 1e-6)          # (fp32 terms d, d * xhat summed in double: the terms' own rounding)
     close(red[:, 1], (dref * xhat).sum(dim=(0, 1, 2)), 1e-4, 1e-5)
     # ties: position 0 of the constant window got the gradient
