@@ -157,6 +157,10 @@ _SIGS = {
     'cy_multi_copy': [_P, _P, _I, _I, _P, _I, _F, _P],
     'cy_adam_multi': [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _P],
     'cy_adam_multi_dev': [_P, _P, _I, _I, _P, _P],
+    'cy_linear_fwd': [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    'cy_linear_dgrad': [_P, _P, _P, _P, _I, _I, _I, _P],
+    'cy_linear_wgrad': [_P, _P, _P, _P, _I, _I, _I, _P],
+    'cy_softmax_xent': [_P, _P, _P, _P, _I, _I, _P],
 }
 _RET = {
     'capsyolo_last_error': (C.c_char_p, []),
@@ -197,6 +201,9 @@ _RET = {
     'cy_track_state_bytes': (_L, [_I, _I]),
     'cy_conv_gemm_bf16_plan': (_I, [C.POINTER(ConvGemm), _I, _I, C.POINTER(C.c_int)]),
     'cy_routing_plan': (_I, [C.POINTER(RoutingFwd), _I, _I, C.POINTER(_L), _I]),
+    'cy_linear_fwd_shares': (_I, [_I, _I, _I]),
+    'cy_linear_fwd_slice': (_I, [_I, _I, _I]),
+    'cy_linear_fwd_ws_floats': (_L, [_I, _I, _I]),
 }
 EXPORTS = sorted(list(_SIGS) + list(_RET))
 ABI_VERSION = 5     # what the signatures above were written against (include/capsyolo_hip.h, csrc/error.cpp)

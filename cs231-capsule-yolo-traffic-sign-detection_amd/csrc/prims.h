@@ -30,6 +30,9 @@ __device__ __forceinline__ void mfma32_v(f32x16& c, float a, float b) {
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
+__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
 // an accumulator tile zeroed by the matrix pipe (C = the inline constant 0), born in AGPRs: no 16 v_accvgpr_write
 __device__ __forceinline__ f32x16 mfma32_zero() {
   f32x16 c;

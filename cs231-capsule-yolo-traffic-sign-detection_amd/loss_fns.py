@@ -7,7 +7,10 @@ from . import ops
 
 
 def cnn_loss(scores, y, params):
-    """loss_fns.py:6-8 (plain-torch baseline model, not a kernel target)."""
+    """loss_fns.py:6-8.  params.cnn_kernels == 'hip': value and gradient in one launch (csrc/linear.hip); otherwise the torch
+    expression of the plain-torch ConvNet."""
+    if getattr(params, 'cnn_kernels', 'torch') == 'hip':
+        return ops.softmax_xent_fn(scores, y)
     return (-F.log_softmax(scores, dim=1).gather(1, y.unsqueeze(1))).sum() / y.size(0)
 
 

@@ -4,7 +4,8 @@ contract and ``state_dict`` keys as the reference's models.py, so reference chec
 libcapsyolo_hip.so (see ops.py); inputs arrive NCHW fp32 as in main.py:57.
 
 New optional ``params`` keys: ``n_iter`` (routing iterations, default 3); ``precision`` ('fp32' default |
-'bf16': the DarkCapsuleNet / DarkCapsuleNet3 backbone on bf16 MFMA kernels, BASELINE configs[4]).
+'bf16': the DarkCapsuleNet / DarkCapsuleNet3 backbone on bf16 MFMA kernels, BASELINE configs[4]); ``cnn_kernels`` ('torch' default |
+'hip': ConvNet on the conv blocks and the linear kernels of csrc/linear.hip).
 """
 from collections import OrderedDict
 
@@ -397,11 +398,50 @@ class DarkCapsuleNet2(nn.Module):
         return self.traffic_sign_capsules(u).view(B, g, g, -1)         # [B,g*g,5+C] -> [B,g,g,5+C]
 
 
+def _cnn_kernels(params):
+    """Optional params.json key ``cnn_kernels``: 'torch' (default: ConvNet on nn.Conv2d / nn.Linear) or 'hip'."""
+    ck = getattr(params, 'cnn_kernels', 'torch')
+    if ck not in ('torch', 'hip'):
+        raise ValueError("params.cnn_kernels must be 'torch' or 'hip', got %r" % (ck,))
+    return ck
+
+
+class HipLinear(nn.Module):
+    """Parameter holder with nn.Linear's names/shapes/init; forward on csrc/linear.hip, the ReLU behind it fused with ``relu``."""
+
+    def __init__(self, cin, cout, relu=False):
+        super().__init__()
+        ref = nn.Linear(cin, cout)                                           # torch's default init
+        self.weight = nn.Parameter(ref.weight.detach().clone())
+        self.bias = nn.Parameter(ref.bias.detach().clone())
+        self.relu = relu
+
+    def forward(self, x):
+        return ops.linear(x, self.weight, self.bias, relu=self.relu)
+
+
+class HipFlattenNCHW(nn.Module):
+    """NHWC activation -> [B, C*H*W] in the reference's flatten order (an NCHW view): one transpose pass."""
+
+    def forward(self, x):
+        return ops.nhwc_to_nchw(x).view(x.shape[0], -1)
+
+
 class ConvNet(nn.Module):
-    """models.py:22-43: the plain-torch CNN baseline (not a kernel target)."""
+    """models.py:22-43.  params.cnn_kernels 'torch' (default): the plain-torch CNN baseline, module for module the reference's.
+    'hip': the same children at the same indices with the same parameter / buffer names and shapes (checkpoints load either way) on
+    the project's kernels -- cnn.0 .. cnn.8 walked by FusedBackbone (the conv1 and Winograd blocks, LeakyReLU 0.01, dropout on
+    torch's RNG, max-pool), cnn.9 the flatten transpose, cnn.10 / cnn.12 on csrc/linear.hip with cnn.11's ReLU fused into cnn.10."""
 
     def __init__(self, params):
         super().__init__()
+        if _cnn_kernels(params) == 'hip':
+            self.cnn = FusedBackbone(
+                HipConv2d(3, 64, 3, padding=1), HipBatchNorm2d(64), HipLeakyReLU(0.01), nn.Dropout(params.dropout),
+                HipConv2d(64, 128, 3, padding=1), HipBatchNorm2d(128), HipLeakyReLU(0.01), nn.Dropout(params.dropout),
+                HipMaxPool2(), HipFlattenNCHW(), HipLinear(128 * 16 * 16, 128, relu=True), nn.Identity(),
+                HipLinear(128, params.n_classes))
+            return
 
         class Flatten(nn.Module):
             def forward(self, x):

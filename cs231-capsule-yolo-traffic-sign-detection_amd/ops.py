@@ -1516,3 +1516,113 @@ def capsule_loss_fn(scores, y, x=None, recon=None, coef=0.0):
 
 def dark_loss_fn(y_pred, y_true, nb, n_classes, l_coord, l_noobj, img):
     return _DarkLoss.apply(y_pred, y_true, nb, n_classes, l_coord, l_noobj, img)
+
+
+# ------------------------------------------------------------------------------------------------ linear layers, cross-entropy
+LINEAR_MAX_M, LINEAR_MAX_N, LINEAR_MAX_K, XENT_MAX_C = 4096, 1024, 1 << 20, 1024     # the range of csrc/linear.hip
+
+
+def _linear_shape_ok(who, M, N, K):
+    if not (1 <= M <= LINEAR_MAX_M and 1 <= N <= LINEAR_MAX_N and 4 <= K <= LINEAR_MAX_K and K % 4 == 0):
+        raise _lib.HipExtensionError('%s: M=%d N=%d K=%d is outside the linear kernels\' range (M 1..%d, N 1..%d, K a multiple of 4 up '
+                                     'to %d); there is no other path' % (who, M, N, K, LINEAR_MAX_M, LINEAR_MAX_N, LINEAR_MAX_K))
+
+
+def _f32_16(t, name):
+    """_f32 and 16-byte aligned (the kernels load and store rows of K floats 16 bytes at a time)."""
+    t = _f32(t, name)
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def linear_shares(M, N, K):
+    """(shares, slice, workspace floats) of cy_linear_fwd for the shape: host arithmetic, answered without a device."""
+    return query('cy_linear_fwd_shares', M, N, K), query('cy_linear_fwd_slice', M, N, K), query('cy_linear_fwd_ws_floats', M, N, K)
+
+
+class _Linear(torch.autograd.Function):
+    """y = act(x W^T + b) on csrc/linear.hip.  x_relu: x is the output of a ReLU; dx is then zeroed where x <= 0 in the store of the
+    input-gradient kernel, which is that ReLU's backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu, x_relu):
+        M, K = x.shape
+        N = weight.shape[0]
+        st = _stream()
+        y = _empty((M, N), x)
+        nws = query('cy_linear_fwd_ws_floats', M, N, K)
+        ws = _empty((nws,), x) if nws else None               # torch's allocator: nothing is allocated by the kernels (graph capture)
+        with timer.range('linear_fwd'):
+            call('cy_linear_fwd', _ptr(x), _ptr(weight), _ptr(bias), _ptr(y), M, N, K, 1 if relu else 0, _ptr(ws), st)
+        ctx.save_for_backward(x, weight, y if relu else None)
+        ctx.relu, ctx.x_relu, ctx.has_bias = relu, x_relu, bias is not None
+        ctx.masked_by_consumer = False                        # set by linear(): the next layer's dgrad applies this layer's ReLU backward
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, y = ctx.saved_tensors
+        M, K = x.shape
+        N = weight.shape[0]
+        st = _stream()
+        dy = _f32(dy, 'dy')
+        if ctx.relu and not ctx.masked_by_consumer:
+            dz = torch.empty_like(dy)
+            call('cy_act_bwd', _ptr(y), _ptr(dy), _ptr(dz), 0.0, dy.numel(), st)
+            dy = dz
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            with timer.range('linear_dgrad'):
+                call('cy_linear_dgrad', _ptr(dy), _ptr(weight), _ptr(dx), _ptr(x) if ctx.x_relu else None, M, N, K, st)
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            dw = torch.empty_like(weight)
+            db = _empty((N,), x) if ctx.has_bias else None
+            with timer.range('linear_wgrad'):
+                call('cy_linear_wgrad', _ptr(dy), _ptr(x), _ptr(dw), _ptr(db), M, N, K, st)
+        return dx, dw, db, None, None
+
+
+def linear(x, weight, bias, relu=False):
+    """F.linear(x, weight, bias), followed by ReLU with ``relu``, as ONE autograd.Function on the kernels of csrc/linear.hip
+    (x [M,K], weight [N,K], bias [N] or None; fp32 on the GPU).  A layer with ``relu`` saves its output.  When that output is the
+    ``x`` of the next ``linear`` call, the ReLU's backward is the mask in the store of the next layer's input-gradient kernel
+    (``dx = 0 where x <= 0``), and this layer takes the gradient as it arrives; for any other consumer this layer masks the gradient
+    itself (cy_act_bwd) -- so a ``relu`` output must not feed a ``linear`` call AND another consumer at once."""
+    if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1] or (bias is not None and tuple(bias.shape) != (weight.shape[0],)):
+        raise _lib.HipExtensionError('linear: x [M,K], weight [N,K], bias [N] expected; got %s, %s, %s'
+                                     % (tuple(x.shape), tuple(weight.shape), None if bias is None else tuple(bias.shape)))
+    _linear_shape_ok('linear', x.shape[0], weight.shape[0], x.shape[1])
+    producer = x.grad_fn if isinstance(x.grad_fn, _Linear._backward_cls) and x.grad_fn.relu else None
+    xa = _f32_16(x, 'x')
+    x_relu = producer is not None and xa is x and torch.is_grad_enabled()
+    y = _Linear.apply(xa, _f32_16(weight, 'weight'), None if bias is None else _f32(bias, 'bias'), bool(relu), x_relu)
+    if x_relu and y.requires_grad:
+        producer.masked_by_consumer = True
+    return y
+
+
+class _SoftmaxXent(torch.autograd.Function):
+    """loss_fns.py:6-8: mean over the batch of -log softmax(scores)[y]; value and gradient in one launch."""
+
+    @staticmethod
+    def forward(ctx, scores, y):
+        M, Cc = scores.shape
+        loss, dscores = _empty((), scores), torch.empty_like(scores)
+        call('cy_softmax_xent', _ptr(scores), _ptr(y), _ptr(loss), _ptr(dscores), M, Cc, _stream())
+        ctx.save_for_backward(dscores)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        return _scaled(ctx.saved_tensors[0], gout), None
+
+
+def softmax_xent_fn(scores, y):
+    if scores.dim() != 2 or y.dim() != 1 or y.shape[0] != scores.shape[0]:
+        raise _lib.HipExtensionError('softmax_xent: scores [M,C] and y [M] expected; got %s, %s' % (tuple(scores.shape), tuple(y.shape)))
+    M, Cc = scores.shape
+    if not (1 <= M <= LINEAR_MAX_M and 1 <= Cc <= XENT_MAX_C):
+        raise _lib.HipExtensionError('softmax_xent: M=%d C=%d is outside the kernel\'s range (M 1..%d, C 1..%d)'
+                                     % (M, Cc, LINEAR_MAX_M, XENT_MAX_C))
+    scores = _f32(scores, 'scores')
+    return _SoftmaxXent.apply(scores, y.to(device=scores.device, dtype=torch.int64).contiguous())

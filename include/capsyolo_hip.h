@@ -442,6 +442,35 @@ int cy_dark_loss(const float* y_pred, const double* y_true, float* loss_out, flo
 /* out = in * (*scalar)  (backward of a scalar loss with upstream gradient on the device) */
 int cy_scale_by_device_scalar(const float* in, const float* scalar, float* out, long long n, void* stream);
 
+/* ------------------------------------------------------------------ linear layers and softmax cross-entropy (csrc/linear.hip)
+ * The nn.Linear pair of ConvNet (models.py:22-43) and cnn_loss (loss_fns.py:6-8).  fp32, row-major, W[N][K] as nn.Linear stores it.
+ * Supported: M 1..4096 rows, N 1..1024 outputs, K a multiple of 4 up to 2^20, C 1..1024 classes; anything else is CY_EINVAL (the
+ * queries return -1).  Tensors read or written 16 bytes at a time (X, W, dX, dW) must be 16-byte aligned.  No atomics: every
+ * entry point repeats bit for bit.
+ *
+ * cy_linear_fwd: Y[M][N] = act(X[M][K] W[N][K]^T + bias), act 0 none / 1 ReLU, bias may be NULL.  The reduction over K runs in
+ * `shares` slices of `slice` elements on separate blocks; with more than one share the partial sums go to ws[shares][M][N] and are
+ * added in a fixed order (16 interleaved runs of ascending shares, then the 16 sums in ascending order).  The rule (host arithmetic; 256 CUs are assumed when no device answers):
+ *   blocks  = ceil(N / 64) * ceil(M / rows),  rows = 16 (M <= 16), 32 (M <= 32), else 64
+ *   shares  = min(ceil(2 CUs / blocks), K / (4 M), ceil(K / 128), 256), at least 1
+ *             -- two blocks per CU; the partial sums at most a quarter of W's bytes; one share while K fits one slice of 128
+ *   slice   = ceil(K / shares) rounded up to a multiple of 64;  shares = ceil(K / slice)
+ * ws: cy_linear_fwd_ws_floats() = shares * M * N floats when shares > 1, else 0 (ws may then be NULL). */
+int cy_linear_fwd_shares(int M, int N, int K);
+int cy_linear_fwd_slice(int M, int N, int K);
+long long cy_linear_fwd_ws_floats(int M, int N, int K);
+int cy_linear_fwd(const float* X, const float* W, const float* bias, float* Y, int M, int N, int K, int act, float* ws,
+                  void* stream);
+/* dX[M][K] = dY[M][N] W[N][K].  X (optional): the layer's own input, the output of a ReLU; then dX[m][k] = 0 where X[m][k] <= 0 --
+ * the backward of the ReLU in front of the layer, applied in the store. */
+int cy_linear_dgrad(const float* dY, const float* W, float* dX, const float* X, int M, int N, int K, void* stream);
+/* dW[N][K] = dY[M][N]^T X[M][K] and (db not NULL) db[N] = the column sums of dY, rows added in ascending order.  The reduction over
+ * M is short: the blocks are slices of K, X and dW are streamed once (N <= 128, M <= 64; otherwise X once per 64 rows of dW). */
+int cy_linear_wgrad(const float* dY, const float* X, float* dW, float* db, int M, int N, int K, void* stream);
+/* loss[0] = mean over the rows of -log softmax(scores[M][C])[y], dscores = its gradient; the row maximum is subtracted before exp.
+ * y int64; a label outside 0 .. C-1 reads nothing and contributes no target term. */
+int cy_softmax_xent(const float* scores, const long long* y, float* loss, float* dscores, int M, int C, void* stream);
+
 /* ------------------------------------------------------------------ data movement / elementwise around the path
  * Layout permutes standing in for the reference's view/permute/cat glue (models.py:8-19, 80-82):
  * out[b][i1][i2][i3] (contiguous, dims nb x d1 x d2 x d3) = in[b*sb + i1*s1 + i2*s2 + i3*s3];

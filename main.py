@@ -46,6 +46,8 @@ shift-and-lightness augmentation (utils.py:126-143, `utils.augmentation`, dead c
 training set stays on the device as bytes and every batch is one gather kernel (capsyolo_amd.class_augment).  Optional params.json
 keys ``aug_max_shift`` (pixels, default 4) and ``aug_max_light`` (on the 0..1 V scale, default 0.05); both 0 give the resident feed
 without jitter.  The eval set is not augmented (see class_augmented_data()).  ``--augment`` stays the detectors' flag.
+``--model cnn --cnn_kernels hip`` (new; also for the ``--combine cnn`` classifier; params.json key ``cnn_kernels``, default ``torch``) runs
+ConvNet on the project's kernels with its Adam and ``--graph`` instead of nn.Conv2d / nn.Linear / torch.optim.Adam; it needs a GPU.
 Data-parallel: launch with ``python -m torch.distributed.run --nproc-per-node N main.py ...``; every rank takes
 its equal shard of each global batch, gradients are averaged with one RCCL all-reduce per step, epoch losses are
 averaged over the ranks before the LR scheduler sees them, metrics run on the gathered predictions, rank 0 writes.
@@ -105,6 +107,9 @@ parser.add_argument('--augment', action='store_true',
 parser.add_argument('--class_augment', action='store_true',
                     help='--mode train|overfit of a classifier (cnn | capsule): shift and lightness jitter per sample and epoch, '
                          'made on the device from the resident training set')
+parser.add_argument('--cnn_kernels', default=None, choices=('torch', 'hip'),
+                    help='--model cnn and the --combine cnn classifier: override params.json cnn_kernels (torch: nn.Conv2d / nn.Linear; '
+                         'hip: the conv blocks and the linear kernels of this project, with its Adam; needs a GPU)')
 parser.add_argument('--gtsrb', default=config.GTSRB, help='--augment: the GTSRB root whose Images/ are the signs to paste')
 parser.add_argument('--max_boxes', type=int, default=16,
                     help='--mode serve: box slots per call (the classifier always runs on this many crops; further boxes are dropped)')
@@ -366,7 +371,13 @@ def load_params(model_dir, args):
         params.batch_size = args.batch_size
     params.fix_ckpt_dir = args.fix_ckpt_dir
     params.graph = args.graph
+    if args.model == 'cnn' and getattr(args, 'cnn_kernels', None) is not None:
+        params.cnn_kernels = args.cnn_kernels
     return params
+
+
+def _cnn_on_hip(params):
+    return params.model == 'cnn' and getattr(params, 'cnn_kernels', 'torch') == 'hip'
 
 
 def synthetic_data(args, params):
@@ -767,7 +778,7 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     if params.device == 'cuda':
         torch.cuda.manual_seed(args.seed)
-    elif args.model != 'cnn':
+    elif args.model != 'cnn' or _cnn_on_hip(params):
         raise SystemExit('model %s runs on hand-written gfx950 kernels only; no GPU is visible' % args.model)
 
     model_cls, loss_fn, predict_fn, metric = model_loss_predict[args.model]
@@ -781,7 +792,8 @@ def main(argv=None):
             if int(name.split('.')[1].split('_')[1]) <= params.fine_tune:
                 param.requires_grad = False
     trainable = [p for p in model.parameters() if p.requires_grad]
-    optimizer = torch.optim.Adam(trainable, lr=args.lr) if args.model == 'cnn' else Adam(trainable, lr=args.lr)
+    torch_cnn = args.model == 'cnn' and not _cnn_on_hip(params)
+    optimizer = torch.optim.Adam(trainable, lr=args.lr) if torch_cnn else Adam(trainable, lr=args.lr)
 
     if args.mode in ('train', 'overfit'):
         if args.augment:

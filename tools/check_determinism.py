@@ -81,5 +81,30 @@ for (Cin, H, Cout, k, s) in ((128, 208, 256, 3, 1), (256, 208, 64, 4, 2), (64, 1
         # (the sums themselves are double atomics: the stored premasked gradient is what must repeat)
         rep(tag + 'fp32 F(4x4,2x2) dgrad + BatchNorm sums (dx)', lambda: ops.conv_dgrad(dz, w, (B, H, H, Cin), k, s, 1, 'c', (zz, sc, sh, mu, isd, 0.1, red)))
         ops.WINOGRAD4_S2_MIN_PIXELS = old
+# the linear kernels of ConvNet (csrc/linear.hip): the forward adds the shares of its split reduction in a fixed order
+for M in (16, 64, 1024):
+    N, K = 128, 32768
+    x, w, bias, dy = torch.randn(M, K, device=dev), torch.randn(N, K, device=dev) * 0.01, torch.randn(N, device=dev), torch.randn(M, N, device=dev)
+    st = torch.cuda.current_stream().cuda_stream
+    ws = torch.empty(max(1, query('cy_linear_fwd_ws_floats', M, N, K)), device=dev)
+    tag = 'linear %d x %d x %d ' % (M, N, K)
+
+    def lin_fwd():
+        y = torch.empty(M, N, device=dev)
+        call('cy_linear_fwd', x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), M, N, K, 1, ws.data_ptr(), st)
+        return y
+
+    def lin_dgrad():
+        dx = torch.empty(M, K, device=dev)
+        call('cy_linear_dgrad', dy.data_ptr(), w.data_ptr(), dx.data_ptr(), x.data_ptr(), M, N, K, st)
+        return dx
+
+    def lin_wgrad():
+        dw, db = torch.empty(N, K, device=dev), torch.empty(N, device=dev)
+        call('cy_linear_wgrad', dy.data_ptr(), x.data_ptr(), dw.data_ptr(), db.data_ptr(), M, N, K, st)
+        return torch.cat([dw.flatten(), db])
+    rep(tag + 'fwd (%d shares)' % query('cy_linear_fwd_shares', M, N, K), lin_fwd)
+    rep(tag + 'dgrad', lin_dgrad)
+    rep(tag + 'wgrad', lin_wgrad)
 print('check_determinism:', 'ok' if bad == 0 else 'FAILED')
 sys.exit(0 if bad == 0 else 1)
