@@ -1406,6 +1406,9 @@ class _DarkCapsuleLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, caps, y):
         caps = _f32(caps, 'caps')
+        if caps.shape[-1] != 5 or y.shape[-1] < 5 or tuple(y.shape[:-1]) != tuple(caps.shape[:-1]):
+            raise _lib.HipExtensionError('darkcapsule_loss: caps must be [B,g,g,5] and the labels [B,g,g,>=5] on the same grid; got %s and %s'
+                                         % (tuple(caps.shape), tuple(y.shape)))
         if not (y.is_cuda and y.dtype == torch.float64):
             y = y.to(device=caps.device, dtype=torch.float64)
         y = y.contiguous()
@@ -1427,6 +1430,9 @@ class _DarkCapsule23Loss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, caps, y, variant):
         caps = _f32(caps, 'caps')
+        if y.dim() != 4 or y.shape[-1] < 5 or tuple(caps.shape[:3]) != tuple(y.shape[:3]):
+            raise _lib.HipExtensionError('darkcapsule%d_loss: the labels must be [B,g,g,5+n_classes] on the grid of the capsules; got %s '
+                                         'and capsules %s' % (variant, tuple(y.shape), tuple(caps.shape)))
         if not (y.is_cuda and y.dtype == torch.float64):
             y = y.to(device=caps.device, dtype=torch.float64)
         y = y.contiguous()
@@ -1435,7 +1441,7 @@ class _DarkCapsule23Loss(torch.autograd.Function):
         cells = y.numel() // (y.shape[-1] * B)
         loss, dcaps = _empty((), caps), torch.empty_like(caps)
         if variant == 2:
-            if caps.shape[-1] != 5 + Cc:
+            if caps.dim() != 4 or caps.shape[-1] != 5 + Cc:
                 raise _lib.HipExtensionError('darkcapsule2_loss: caps last dim %d != 5 + n_classes %d' % (caps.shape[-1], Cc))
             call('cy_darkcapsule2_loss', _ptr(caps), _ptr(y), _ptr(loss), _ptr(dcaps), B, cells, Cc, _stream())
         else:
@@ -1489,10 +1495,19 @@ class _DarkLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y_pred, y_true, nb, n_classes, l_coord, l_noobj, img):
         y_pred = _f32(y_pred, 'y_pred')
+        nb, n_classes = int(nb), int(n_classes)
+        B, g = y_pred.shape[0], (y_pred.shape[1] if y_pred.dim() > 1 else 0)
+        # the kernel strides y_pred by 5 n_boxes + n_classes and y_true by 5 + n_classes over B g g cells
+        if tuple(y_pred.shape) != (B, g, g, 5 * nb + n_classes) or y_true.dim() != 4 or tuple(y_true.shape[:3]) != (B, g, g):
+            raise _lib.HipExtensionError('dark_loss: y_pred must be [B,g,g,5*%d+%d] and y_true [B,g,g,5+%d] on the same grid; got %s and %s'
+                                         % (nb, n_classes, n_classes, tuple(y_pred.shape), tuple(y_true.shape)))
+        if y_true.shape[-1] != 5 + n_classes:
+            if n_classes != 0 or y_true.shape[-1] < 5:
+                raise _lib.HipExtensionError('dark_loss: labels of %d columns with n_classes = %d' % (y_true.shape[-1], n_classes))
+            y_true = y_true[..., :5]                             # recognition-model labels: without classes only these columns are read
         if not (y_true.is_cuda and y_true.dtype == torch.float64):
             y_true = y_true.to(device=y_pred.device, dtype=torch.float64)
         y_true = y_true.contiguous()
-        B, g = y_pred.shape[0], y_pred.shape[1]
         loss, avg_iou = _empty((), y_pred), _empty((), y_pred)
         dpred = torch.empty_like(y_pred)
         call('cy_dark_loss', _ptr(y_pred), _ptr(y_true), _ptr(loss), _ptr(avg_iou), _ptr(dpred), B, g, nb, n_classes,
