@@ -1231,20 +1231,32 @@ class _MaxPool2(torch.autograd.Function):
     def forward(ctx, x):
         x = _f32(x)
         B, H, W, Cc = x.shape
-        y = _empty((B, H // 2, W // 2, Cc), x)
-        idx = _empty((B, H // 2, W // 2, Cc), x, torch.uint8)
-        call('cy_maxpool2_fwd', _ptr(x), _ptr(y), _ptr(idx), B, H // 2, W // 2, Cc, _stream())
-        ctx.save_for_backward(idx)
+        Ho, Wo = H // 2, W // 2                  # nn.MaxPool2d(2) floors: the last row / column of an odd map is ignored
+        y = _empty((B, Ho, Wo, Cc), x)
+        idx = _empty((B, Ho, Wo, Cc), x, torch.uint8)
         ctx.shape = (B, H, W, Cc)
+        ctx.save_for_backward(idx)
+        if y.numel() == 0:                       # a map of one row or column: nothing to launch
+            return y
+        if H != 2 * Ho or W != 2 * Wo:           # the kernels address [B][2 Ho][2 Wo][C]: hand them exactly that
+            x = x[:, :2 * Ho, :2 * Wo].contiguous()
+        call('cy_maxpool2_fwd', _ptr(x), _ptr(y), _ptr(idx), B, Ho, Wo, Cc, _stream())
         return y
 
     @staticmethod
     def backward(ctx, dy):
         (idx,) = ctx.saved_tensors
         B, H, W, Cc = ctx.shape
+        Ho, Wo = H // 2, W // 2
         dy = _f32(dy)
-        dx = _empty((B, H, W, Cc), dy) if (H % 2 == 0 and W % 2 == 0) else torch.zeros((B, H, W, Cc), device=dy.device)
-        call('cy_maxpool2_bwd', _ptr(dy), _ptr(idx), _ptr(dx), B, H // 2, W // 2, Cc, _stream())
+        if idx.numel() == 0:
+            return torch.zeros((B, H, W, Cc), device=dy.device)
+        dx = _empty((B, 2 * Ho, 2 * Wo, Cc), dy)
+        call('cy_maxpool2_bwd', _ptr(dy), _ptr(idx), _ptr(dx), B, Ho, Wo, Cc, _stream())
+        if H != 2 * Ho or W != 2 * Wo:           # the ignored row / column gets a gradient of zero
+            full = torch.zeros((B, H, W, Cc), device=dy.device)
+            full[:, :2 * Ho, :2 * Wo] = dx
+            dx = full
         return dx
 
 
