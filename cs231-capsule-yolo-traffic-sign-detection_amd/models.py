@@ -108,7 +108,7 @@ class FusedBackbone(nn.Sequential):
                 first = False
                 continue
             cin, cout = m.weight.shape[1], m.weight.shape[0]
-            if bn is None or slope is None or not ops.bf16_layer_ok(m.k, m.stride, m.padding, cin, cout):
+            if bn is None or slope is None or not ops.conv_plan_bf16(x.shape, cout, m.k, m.stride, m.padding).ok:
                 raise ops._lib.HipExtensionError('precision bf16: no bf16 kernel for block %s (k=%d s=%d p=%d %d -> %d channels); '
                                                  'built: 3x3/s1/p1 and 4x4/s2/p1 with channels in multiples of 64'
                                                  % (names[i], m.k, m.stride, m.padding, cin, cout))

@@ -119,17 +119,16 @@ def _const_zeros(n, like):
 
 
 # ------------------------------------------------------------------------------------------------ convolution
-def _x_geometry(x, nchw):
+def _x_geometry(shape, nchw):
     if nchw:
-        B, Cin, Hi, Wi = x.shape
+        B, Cin, Hi, Wi = shape
         return B, Hi, Wi, Cin, (Cin * Hi * Wi, Wi, 1, Hi * Wi)
-    B, Hi, Wi, Cin = x.shape
+    B, Hi, Wi, Cin = shape
     return B, Hi, Wi, Cin, (Hi * Wi * Cin, Wi * Cin, Cin, 1)
 
 
 STATS_COPIES = 16       # CY_STATS_COPIES of include/capsyolo_hip.h: BatchNorm statistics are accumulated in 16 striped copies
 USE_CONV1_MOMENTS = True  # ... whose BatchNorm statistics come from the 28 x 28 moment matrix of the input patches (csrc/conv1_moments.hip)
-FUSE_BN_BWD_APPLY_BF16 = True   # bf16 path: BatchNorm-backward pass 2 inside the weight gradient (cy_conv_wgrad_bf16_bn) where the gradient arrives premasked
 USE_CONV1_ONEPASS = True  # ... and whose backward then needs ONE pass over the gradient (cy_conv1_bn_bwd_onepass)
 CONV1_SIGNMASK = True     # ... which takes lrelu'(y) from one bit per element that the activation pass stored (cy_conv1_bn_bwd_onepass_mask: no z recomputed)
 CONV1_MOMENTS_MIN_PIXELS = 1 << 18   # ... from this many pixels on: below, its three launches cost more than the one recompute pass saves
@@ -224,6 +223,61 @@ def conv_plan(in_shape, cout, k, stride, pad, nchw=False, relu=False, lrelu=Fals
                     bool(CONV1_SIGNMASK and conv1_moments and conv1_onepass))
 
 
+BF16_DGRAD_ONE_LAUNCH = True       # bf16 path: the output-parity classes of a strided input gradient in one launch (cy_conv_gemm_bf16_classes)
+FUSE_BN_BWD_REDUCE_BF16 = True     # bf16 path: the producer block's BatchNorm-backward sums out of the consumer's input-gradient epilogue
+FUSE_BN_BWD_APPLY_BF16 = True      # bf16 path: BatchNorm-backward pass 2 inside the weight gradient (cy_conv_wgrad_bf16_bn) where the gradient arrives premasked
+
+ConvPlanBF16 = collections.namedtuple('ConvPlanBF16', [
+    'ok',                      # the bf16 kernels are built for this layer (FusedBackbone._forward_bf16 refuses every other)
+    'fwd', 'dgrad', 'wgrad',   # the kernel family of each pass, named by its timer.range prefix (None where not ok)
+    'dgrad_one_launch',        # the input gradient's output-parity classes go out together (cy_conv_gemm_bf16_classes)
+    'dgrad_bn_fuse',           # the input gradient's epilogue can sum the producer's BatchNorm backward (conv_dgrad_bf16's bn_fuse) ...
+    'dgrad_premasks',          # ... and then stores dx * lrelu'(y), not dx (the bf16 epilogue always does)
+    'wgrad_bn',                # the weight gradient has the form with BatchNorm-backward pass 2 inside (conv_bf16_wgrad_bn)
+    'launches'])               # {'fwd': [...], 'dgrad': [...]}: {BM, BN, TAPIN, ntiles, blocks} per launch; None where the library refuses the GEMM
+
+
+def conv_plan_bf16(in_shape, cout, k, stride, pad, in_f32=False, out_f32=False):
+    """The bf16 twin of conv_plan (in_shape = x's NHWC shape; in_f32: the input gradient leaves in fp32 for an fp32 producer; out_f32:
+    the forward writes fp32).  Host arithmetic on the shape, the library's own answers for the descriptors the launches will carry,
+    and the three switches above AS THEY STAND NOW: every call asks again.  What depends on the step stays at the use: whether a
+    hand-over is there and fits (_input_grad), whether the gradient arrived premasked and in bf16 (_ConvBlockBF16.backward)."""
+    B, Hi, Wi, Cin, xs = _x_geometry(in_shape, False)
+    Ho, Wo = (Hi + 2 * pad - k) // stride + 1, (Wi + 2 * pad - k) // stride + 1
+    # (k < stride leaves input pixels without taps: dgrad_classes refuses, there is no input gradient and launches['dgrad'] is [])
+    classes, descs = _gemm_dgrad_descs(in_shape, (B, Ho, Wo, cout), k, stride, pad) if k >= stride else ((), ())
+    sizes = set((c['TH'], c['TW'], c['Ho'], c['Wo']) for c in classes)
+    one_launch = bool(BF16_DGRAD_ONE_LAUNCH and 1 < len(classes) <= 4 and len(sizes) == 1)      # (even maps: every class the same grid and taps)
+    launches = {'fwd': _launches_bf16([_gemm_fwd_desc(B, Hi, Wi, Cin, xs, cout, k, stride, pad)], False, out_f32),
+                'dgrad': _launches_bf16(descs, one_launch, in_f32)}
+    ok = bool(pad == 1 and launches['fwd'] and launches['dgrad'] and query('cy_conv_wgrad_bf16_ws_floats', B, Ho, Wo, Cin, cout, k, stride) >= 0)
+    wgrad_bn = bool(ok and FUSE_BN_BWD_APPLY_BF16 and query('cy_conv_wgrad_bf16_bn_ws_floats', B, Ho, Wo, Cin, cout, k, stride) >= 0)
+    bn_fuse = bool(FUSE_BN_BWD_REDUCE_BF16 and not in_f32)      # (the sums select other kernels, never another launch plan)
+    fams = ('conv_bf16_fwd', 'conv_bf16_dgrad', 'conv_bf16_wgrad') if ok else (None, None, None)
+    return ConvPlanBF16(ok, *fams, one_launch, bn_fuse, bn_fuse, wgrad_bn, launches)
+
+
+def _launches_bf16(descs, one_launch, out_f32):
+    """cy_conv_gemm_bf16_plan's {BM, BN, TAPIN, ntiles, blocks} per launch (all descriptors in one, or one each); None if refused."""
+    out = []
+    for group in ([descs] if one_launch else [[d] for d in descs]):
+        p = (C.c_int * 5)()
+        if query('cy_conv_gemm_bf16_plan', (ConvGemm * len(group))(*group), len(group), 1 if out_f32 else 0, p) != 0:
+            return None
+        out.append(dict(BM=p[0], BN=p[1], TAPIN=p[2], ntiles=p[3], blocks=p[4]))
+    return out
+
+
+def conv_bf16_plans(op, in_shape, Cout, k, stride, pad, out_f32=False, bnf=False):
+    """conv_plan_bf16(...).launches[op] by pass: op 'fwd' (in_shape = x's) or 'dgrad' (dx's); out_f32: that pass writes fp32.  bnf (the
+    fused sums: input gradient with bf16 output only) selects other kernels, never another launch plan, so it is only checked."""
+    got = None if bnf and (op == 'fwd' or out_f32) else conv_plan_bf16(in_shape, Cout, k, stride, pad, out_f32 and op == 'dgrad',
+                                                                       out_f32 and op == 'fwd').launches[op]
+    if not got:
+        raise _lib.HipExtensionError('no bf16 %s launch for these shapes (bnf=%r): %s' % (op, bnf, query('capsyolo_last_error').decode()))
+    return got
+
+
 def _winograd(x, weight, bias, stats, transpose, f4, tag, out_slope=1.0):
     """x [B,H,W,Cg] NHWC; weight in PyTorch layout; transpose=True computes the input gradient of the layer; f4: on F(4x4,3x3).
     out_slope != 1: LeakyReLU epilogue (eval forward with the BatchNorm folded into weight / bias)."""
@@ -279,7 +333,7 @@ def conv_forward(x, weight, bias, k, stride, pad, nchw=False, stats=None, relu=F
                                      'fused input affine, slope in [0, 1]' % (lrelu,))
     osl = 1.0 if lrelu is None else float(lrelu)
     x, weight = _f32(x, 'conv input'), _f32(weight, 'conv weight')
-    B, Hi, Wi, Cin, xs = _x_geometry(x, nchw)
+    B, Hi, Wi, Cin, xs = _x_geometry(x.shape, nchw)
     Cout = weight.shape[0]
     Ho, Wo = (Hi + 2 * pad - k) // stride + 1, (Wi + 2 * pad - k) // stride + 1
     plan = conv_plan(x.shape, Cout, k, stride, pad, nchw, relu, lrelu is not None)
@@ -308,12 +362,9 @@ def conv_forward(x, weight, bias, k, stride, pad, nchw=False, stats=None, relu=F
     wp = _empty((query('cy_conv_packed_floats', k * k * Cin, Cout),), x)
     call('cy_conv_pack_weights', _ptr(weight), _ptr(wp), Cout, Cin, k, k, k, k, 0, 0, 1, 0, st)
     z = _empty((B, Ho, Wo, Cout), x)
-    a = ConvGemm(X=x.data_ptr(), Wp=wp.data_ptr(), Y=z.data_ptr(),
-                 bias=bias.data_ptr() if bias is not None else None,
-                 stats=stats.data_ptr() if stats is not None else None,
-                 xs_b=xs[0], xs_y=xs[1], xs_x=xs[2], xs_c=xs[3], B=B, Hi=Hi, Wi=Wi, Cin=Cin, Ho=Ho, Wo=Wo, N=Cout,
-                 TH=k, TW=k, in_stride=stride, dy0=-pad, dx0=-pad, dstep=1,
-                 Hy=Ho, Wy=Wo, out_stride=1, out_oy=0, out_ox=0, act=1 if relu else 2 if lrelu is not None else 0, act_slope=osl)
+    a = _gemm_fwd_desc(B, Hi, Wi, Cin, xs, Cout, k, stride, pad, 1 if relu else 2 if lrelu is not None else 0, osl)
+    a.X, a.Wp, a.Y = x.data_ptr(), wp.data_ptr(), z.data_ptr()
+    a.bias, a.stats = bias.data_ptr() if bias is not None else None, stats.data_ptr() if stats is not None else None
     ws = _gemm_workspace(a, x)
     with timer.range('conv_gemm_fwd/' + tag):
         call('cy_conv_gemm', C.byref(a), st)
@@ -357,6 +408,34 @@ def dgrad_classes(Hi, Wi, k, stride, pad):
     return out
 
 
+def _gemm_fwd_desc(B, Hi, Wi, Cin, xs, Cout, k, stride, pad, act=0, act_slope=1.0):
+    """A forward's cy_conv_gemm_t without its pointers, fp32 or bf16 (xs: _x_geometry's strides; act 1: ReLU, 2: LeakyReLU)."""
+    Ho, Wo = (Hi + 2 * pad - k) // stride + 1, (Wi + 2 * pad - k) // stride + 1
+    return ConvGemm(xs_b=xs[0], xs_y=xs[1], xs_x=xs[2], xs_c=xs[3], B=B, Hi=Hi, Wi=Wi, Cin=Cin, Ho=Ho, Wo=Wo, N=Cout,
+                    TH=k, TW=k, in_stride=stride, dy0=-pad, dx0=-pad, dstep=1, Hy=Ho, Wy=Wo, out_stride=1, out_oy=0, out_ox=0,
+                    act=act, act_slope=act_slope)
+
+
+def _gemm_dgrad_descs(in_shape, dz_shape, k, stride, pad):
+    """An input gradient's parity classes (dgrad_classes) and their cy_conv_gemm_t without pointers, fp32 or bf16."""
+    B, Hi, Wi, Cin = in_shape
+    _, Ho, Wo, Cout = dz_shape
+    classes = dgrad_classes(Hi, Wi, k, stride, pad)
+    descs = (ConvGemm * len(classes))()
+    for i, c in enumerate(classes):
+        descs[i] = ConvGemm(xs_b=Ho * Wo * Cout, xs_y=Wo * Cout, xs_x=Cout, xs_c=1, B=B, Hi=Ho, Wi=Wo, Cin=Cout,
+                            Ho=c['Ho'], Wo=c['Wo'], N=Cin, TH=c['TH'], TW=c['TW'], in_stride=1, dy0=c['dy0'], dx0=c['dx0'],
+                            dstep=c['dstep'], Hy=Hi, Wy=Wi, out_stride=c['out_stride'], out_oy=c['out_oy'], out_ox=c['out_ox'], act=0)
+    return classes, descs
+
+
+def _set_bn_fuse(desc, bn_fuse):
+    """The producer's BatchNorm (bn_fuse of conv_dgrad / conv_dgrad_bf16) into an input gradient's descriptor (cy_conv_gemm_t.bn_*)."""
+    bz, bsc, bsh, bmu, bis, bsl, bred = bn_fuse
+    desc.bn_z, desc.bn_scale, desc.bn_shift = bz.data_ptr(), bsc.data_ptr(), bsh.data_ptr()
+    desc.bn_mean, desc.bn_invstd, desc.bn_red, desc.bn_slope = bmu.data_ptr(), bis.data_ptr(), bred.data_ptr(), float(bsl)
+
+
 def conv_dgrad(dz, weight, in_shape, k, stride, pad, tag='conv', bn_fuse=None, plan=None):
     """dx[B,Hi,Wi,Cin] (NHWC) from dz[B,Ho,Wo,Cout]: one GEMM per output-parity class of the stride.
     bn_fuse = (z, scale, shift, mean, invstd, slope, red): dx is the gradient with respect to lrelu(z*scale+shift) of the
@@ -382,18 +461,12 @@ def conv_dgrad(dz, weight, in_shape, k, stride, pad, tag='conv', bn_fuse=None, p
                  _ptr(bis), float(bsl), _ptr(bred), B, Hi, Wi, Cin, Cout, st)
         return dx
     wp = _empty((query('cy_conv_packed_floats', ((k + stride - 1) // stride) ** 2 * Cout, Cin),), dz)
-    for c in dgrad_classes(Hi, Wi, k, stride, pad):
+    for c, a in zip(*_gemm_dgrad_descs(in_shape, dz.shape, k, stride, pad)):
         call('cy_conv_pack_weights', _ptr(weight), _ptr(wp), Cout, Cin, k, k, c['TH'], c['TW'], c['kh0'], c['kw0'],
              c['kstep'], 1, st)
-        a = ConvGemm(X=dz.data_ptr(), Wp=wp.data_ptr(), Y=dx.data_ptr(), bias=None, stats=None,
-                     xs_b=Ho * Wo * Cout, xs_y=Wo * Cout, xs_x=Cout, xs_c=1, B=B, Hi=Ho, Wi=Wo, Cin=Cout,
-                     Ho=c['Ho'], Wo=c['Wo'], N=Cin, TH=c['TH'], TW=c['TW'], in_stride=1,
-                     dy0=c['dy0'], dx0=c['dx0'], dstep=c['dstep'],
-                     Hy=Hi, Wy=Wi, out_stride=c['out_stride'], out_oy=c['out_oy'], out_ox=c['out_ox'], act=0)
+        a.X, a.Wp, a.Y = dz.data_ptr(), wp.data_ptr(), dx.data_ptr()
         if bn_fuse is not None:
-            bz, bsc, bsh, bmu, bis, bsl, bred = bn_fuse
-            a.bn_z, a.bn_scale, a.bn_shift = bz.data_ptr(), bsc.data_ptr(), bsh.data_ptr()
-            a.bn_mean, a.bn_invstd, a.bn_red, a.bn_slope = bmu.data_ptr(), bis.data_ptr(), bred.data_ptr(), float(bsl)
+            _set_bn_fuse(a, bn_fuse)
         ws = _gemm_workspace(a, dz)
         with timer.range('conv_gemm_dgrad/' + tag):
             call('cy_conv_gemm', C.byref(a), st)
@@ -403,7 +476,7 @@ def conv_dgrad(dz, weight, in_shape, k, stride, pad, tag='conv', bn_fuse=None, p
 
 def conv_wgrad(x, dz, k, stride, pad, nchw=False, tag='conv', in_affine=None, plan=None):
     x, dz = _f32(x, 'conv input'), _f32(dz, 'grad')
-    B, Hi, Wi, Cin, xs = _x_geometry(x, nchw)
+    B, Hi, Wi, Cin, xs = _x_geometry(x.shape, nchw)
     _, Ho, Wo, Cout = dz.shape
     st = _stream()
     dW = _empty((Cout, Cin, k, k), dz)
@@ -556,17 +629,22 @@ def _grad_f32(da, cfg, keep_bf16=False):
 
 
 def _input_grad(ctx, dz, x, weight, plan, st):
-    """dx of a block whose input wants one; as the CONSUMER of ctx.hin, the input-gradient kernel's epilogue also sums the
-    producer's BatchNorm backward where the plan has that form, and the sums are given to the hand-over."""
+    """dx of a block whose input wants one (plan: a ConvPlan or a ConvPlanBF16); as the CONSUMER of ctx.hin, the input-gradient
+    kernel's epilogue also sums the producer's BatchNorm backward where the plan has that form, and the sums are given to the
+    hand-over.  The producer's z is x itself on the fp32 path (mean / invstd only in training mode); a bf16 producer hands its z over."""
     if not ctx.needs_input_grad[0]:
         return None
-    if plan.dgrad is None:
+    bf16 = isinstance(plan, ConvPlanBF16)
+    if plan.dgrad is None and not bf16:
         raise _lib.HipExtensionError('input gradient of an NCHW-input convolution is not implemented')
     cfg, h, fuse = ctx.cfg, ctx.hin, None
-    if plan.dgrad_bn_fuse and h is not None and h.mean is not None:
+    if plan.dgrad_bn_fuse and h is not None and (tuple(h.z.shape) == tuple(x.shape) if bf16 else h.mean is not None):
         bred = zero_pool.take((STATS_COPIES, x.shape[3], 2), torch.float64, x.device)
-        fuse = (x, h.scale, h.shift, h.mean, h.invstd, h.slope, bred)
-    dx = conv_dgrad(dz, weight, tuple(x.shape), cfg.k, cfg.stride, cfg.pad, cfg.name, fuse, plan)
+        fuse = (h.z if bf16 else x, h.scale, h.shift, h.mean, h.invstd, h.slope, bred)
+    if bf16:
+        dx = conv_dgrad_bf16(dz, weight, tuple(x.shape), cfg.k, cfg.stride, cfg.pad, cfg.in_f32, cfg.name, fuse, plan)
+    else:
+        dx = conv_dgrad(dz, weight, tuple(x.shape), cfg.k, cfg.stride, cfg.pad, cfg.name, fuse, plan)
     if fuse is not None:
         red = _empty((x.shape[3], 2), x, torch.float64)
         call('cy_bn_red_fold', _ptr(bred), STATS_COPIES, 1.0, _ptr(red), None, None, x.shape[3], st)
@@ -801,11 +879,6 @@ def _bf(t, name='tensor'):
     return t if t.is_contiguous() else t.contiguous()
 
 
-def bf16_layer_ok(k, stride, pad, cin, cout):
-    """The layers the bf16 kernels are built for: the backbone's 3x3/s1/p1 and 4x4/s2/p1 convs (models.py:350-363)."""
-    return pad == 1 and ((k == 3 and stride == 1 and cout % 128 == 0) or (k == 4 and stride == 2)) and cin % 64 == 0 and cout % 64 == 0
-
-
 def cast_bf16(x):
     """fp32 -> bf16 (round to nearest even); the gradient passes through unchanged (it arrives in fp32)."""
     return _CastBF16.apply(x)
@@ -832,14 +905,13 @@ def conv_forward_bf16(x, weight, bias, k, stride, pad, stats=None, tag='conv', l
     """z (bf16 NHWC) = conv2d(x bf16 NHWC) + bias with fp32 accumulation; optional BatchNorm statistics.
     lrelu = slope in [0, 1]: LeakyReLU epilogue (eval forward, BatchNorm folded into weight / bias); out_f32: fp32 output."""
     x, weight = _bf(x, 'conv input'), _f32(weight, 'conv weight')
-    B, Hi, Wi, Cin = x.shape
+    B, Hi, Wi, Cin, xs = _x_geometry(x.shape, False)
     Cout = weight.shape[0]
-    Ho, Wo = (Hi + 2 * pad - k) // stride + 1, (Wi + 2 * pad - k) // stride + 1
     st = _stream()
     wp = torch.empty((query('cy_conv_bf16_packed_elems', k * k * Cin, Cout),), dtype=torch.bfloat16, device=x.device)
     call('cy_conv_bf16_pack_weights', _ptr(weight), _ptr(wp), Cout, Cin, k, k, k, k, 0, 0, 1, 0, st)
-    z = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
-    a = _fwd_desc_bf16(x.shape, Cout, k, stride, pad, lrelu)
+    a = _gemm_fwd_desc(B, Hi, Wi, Cin, xs, Cout, k, stride, pad, 0 if lrelu is None else 2, 1.0 if lrelu is None else float(lrelu))
+    z = torch.empty((B, a.Ho, a.Wo, Cout), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
     a.X, a.Wp, a.Y = x.data_ptr(), wp.data_ptr(), z.data_ptr()
     a.bias, a.stats = bias.data_ptr() if bias is not None else None, stats.data_ptr() if stats is not None else None
     with timer.range('conv_bf16_fwd/' + tag):
@@ -847,11 +919,7 @@ def conv_forward_bf16(x, weight, bias, k, stride, pad, stats=None, tag='conv', l
     return z
 
 
-BF16_DGRAD_ONE_LAUNCH = True       # bf16 path: the output-parity classes of a strided input gradient in one launch (cy_conv_gemm_bf16_classes)
-FUSE_BN_BWD_REDUCE_BF16 = True     # bf16 path: the producer block's BatchNorm-backward sums out of the consumer's input-gradient epilogue
-
-
-def conv_dgrad_bf16(dz, weight, in_shape, k, stride, pad, out_f32=False, tag='conv', bn_fuse=None):
+def conv_dgrad_bf16(dz, weight, in_shape, k, stride, pad, out_f32=False, tag='conv', bn_fuse=None, plan=None):
     """dx [B,Hi,Wi,Cin] (bf16, or fp32 for an fp32 producer) from dz (bf16): one GEMM per output-parity class.
     bn_fuse = (z bf16, scale, shift, mean, invstd, slope, red[STATS_COPIES][Cin][2]) of the PRODUCER block (bf16 output only): the
     epilogues store d = dx * lrelu'(z * scale + shift) -- the premasked gradient -- and add sum d, sum d * xhat of the stored
@@ -860,10 +928,11 @@ def conv_dgrad_bf16(dz, weight, in_shape, k, stride, pad, out_f32=False, tag='co
     if bn_fuse is not None and out_f32:
         raise _lib.HipExtensionError('conv_dgrad_bf16: the fused BatchNorm-backward sums are built for the bf16 output')
     B, Hi, Wi, Cin = in_shape
-    _, Ho, Wo, Cout = dz.shape
+    Cout = dz.shape[3]
+    plan = plan or conv_plan_bf16(in_shape, Cout, k, stride, pad, in_f32=out_f32)      # (a block's backward passes the one it asked for)
     st = _stream()
     dx = torch.empty((B, Hi, Wi, Cin), dtype=torch.float32 if out_f32 else torch.bfloat16, device=dz.device)
-    classes, descs, one_launch = _dgrad_descs_bf16(in_shape, dz.shape, k, stride, pad)
+    classes, descs = _gemm_dgrad_descs(in_shape, dz.shape, k, stride, pad)
     nel = query('cy_conv_bf16_packed_elems', ((k + stride - 1) // stride) ** 2 * Cout, Cin)
     wp = torch.empty((len(classes), nel), dtype=torch.bfloat16, device=dz.device)
     for i, c in enumerate(classes):
@@ -872,11 +941,8 @@ def conv_dgrad_bf16(dz, weight, in_shape, k, stride, pad, out_f32=False, tag='co
         a = descs[i]
         a.X, a.Wp, a.Y = dz.data_ptr(), wp[i].data_ptr(), dx.data_ptr()
         if bn_fuse is not None:
-            bz, bsc, bsh, bmu, bis, bsl, bred = bn_fuse
-            a.bn_z, a.bn_scale, a.bn_shift = _bf(bz, 'producer z').data_ptr(), bsc.data_ptr(), bsh.data_ptr()
-            a.bn_mean, a.bn_invstd, a.bn_red, a.bn_slope = bmu.data_ptr(), bis.data_ptr(), bred.data_ptr(), float(bsl)
-    if one_launch:
-        # the parity classes of a strided layer in ONE launch (even sizes: all classes have the same grid and taps)
+            _set_bn_fuse(a, (_bf(bn_fuse[0], 'producer z'),) + tuple(bn_fuse[1:]))
+    if plan.dgrad_one_launch:
         with timer.range('conv_bf16_dgrad/' + tag):
             call('cy_conv_gemm_bf16_classes', descs, len(classes), 1 if out_f32 else 0, st)
     else:
@@ -884,57 +950,6 @@ def conv_dgrad_bf16(dz, weight, in_shape, k, stride, pad, out_f32=False, tag='co
             with timer.range('conv_bf16_dgrad/' + tag):
                 call('cy_conv_gemm_bf16', C.byref(descs[i]), 1 if out_f32 else 0, st)
     return dx
-
-
-def _fwd_desc_bf16(x_shape, Cout, k, stride, pad, lrelu=None):
-    """The forward's cy_conv_gemm_t without its pointers."""
-    B, Hi, Wi, Cin = x_shape
-    Ho, Wo = (Hi + 2 * pad - k) // stride + 1, (Wi + 2 * pad - k) // stride + 1
-    return ConvGemm(xs_b=Hi * Wi * Cin, xs_y=Wi * Cin, xs_x=Cin, xs_c=1, B=B, Hi=Hi, Wi=Wi, Cin=Cin, Ho=Ho, Wo=Wo, N=Cout,
-                    TH=k, TW=k, in_stride=stride, dy0=-pad, dx0=-pad, dstep=1, Hy=Ho, Wy=Wo, out_stride=1, out_oy=0, out_ox=0,
-                    act=0 if lrelu is None else 2, act_slope=1.0 if lrelu is None else float(lrelu))
-
-
-def _dgrad_descs_bf16(in_shape, dz_shape, k, stride, pad):
-    """The input gradient's parity classes, their cy_conv_gemm_t without pointers, and whether they go in one launch."""
-    B, Hi, Wi, Cin = in_shape
-    _, Ho, Wo, Cout = dz_shape
-    classes = dgrad_classes(Hi, Wi, k, stride, pad)
-    descs = (ConvGemm * len(classes))()
-    for i, c in enumerate(classes):
-        descs[i] = ConvGemm(xs_b=Ho * Wo * Cout, xs_y=Wo * Cout, xs_x=Cout, xs_c=1, B=B, Hi=Ho, Wi=Wo, Cin=Cout,
-                            Ho=c['Ho'], Wo=c['Wo'], N=Cin, TH=c['TH'], TW=c['TW'], in_stride=1, dy0=c['dy0'], dx0=c['dx0'],
-                            dstep=c['dstep'], Hy=Hi, Wy=Wi, out_stride=c['out_stride'], out_oy=c['out_oy'], out_ox=c['out_ox'], act=0)
-    same = all((c['TH'], c['TW'], c['Ho'], c['Wo'], c['dstep'], c['out_stride']) ==
-               (classes[0]['TH'], classes[0]['TW'], classes[0]['Ho'], classes[0]['Wo'], classes[0]['dstep'], classes[0]['out_stride'])
-               for c in classes)
-    return classes, descs, BF16_DGRAD_ONE_LAUNCH and 1 < len(classes) <= 4 and same
-
-
-def _plan_bf16(descs, ncls, out_f32, bnf):
-    plan = (C.c_int * 5)()
-    if bnf:
-        for i in range(ncls):
-            descs[i].bn_red = 1                          # (the plan reads no pointer: only whether the sums are fused)
-    rc = query('cy_conv_gemm_bf16_plan', descs, ncls, 1 if out_f32 else 0, plan)
-    if rc != 0:
-        raise _lib.HipExtensionError('cy_conv_gemm_bf16_plan failed (code %d): %s' % (rc, query('capsyolo_last_error').decode()))
-    return dict(BM=plan[0], BN=plan[1], TAPIN=plan[2], ntiles=plan[3], blocks=plan[4])
-
-
-def conv_bf16_plans(op, in_shape, Cout, k, stride, pad, out_f32=False, bnf=False):
-    """The launches of conv_forward_bf16 (op 'fwd', in_shape = x's NHWC shape) or conv_dgrad_bf16 (op 'dgrad', in_shape = dx's)
-    for these shapes: one dict {BM, BN, TAPIN, ntiles, blocks} per launch, from cy_conv_gemm_bf16_plan (host arithmetic, no GPU)."""
-    B, Hi, Wi, Cin = in_shape
-    if op == 'fwd':
-        if bnf:
-            raise ValueError('the fused BatchNorm-backward sums belong to the input gradient')
-        return [_plan_bf16((ConvGemm * 1)(_fwd_desc_bf16(in_shape, Cout, k, stride, pad)), 1, out_f32, False)]
-    Ho, Wo = (Hi + 2 * pad - k) // stride + 1, (Wi + 2 * pad - k) // stride + 1
-    classes, descs, one_launch = _dgrad_descs_bf16(in_shape, (B, Ho, Wo, Cout), k, stride, pad)
-    if one_launch:
-        return [_plan_bf16(descs, len(classes), out_f32, bnf)]
-    return [_plan_bf16((ConvGemm * 1)(descs[i]), 1, out_f32, bnf) for i in range(len(classes))]
 
 
 def conv_wgrad_bf16(x, dz, k, stride, pad, tag='conv'):
@@ -1021,12 +1036,10 @@ class _ConvBlockBF16(torch.autograd.Function):
         dz = torch.empty_like(z)
         dgamma, dbeta = _empty((N,), weight), _empty((N,), weight)
         Bx, Hx, Wx, Cx = x.shape
-        nws = -1
-        if FUSE_BN_BWD_APPLY_BF16 and slope == 1.0 and not da_f32 and cfg.pad == 1:
+        plan = conv_plan_bf16(x.shape, N, cfg.k, cfg.stride, cfg.pad, cfg.in_f32, cfg.out_f32)
+        if plan.wgrad_bn and slope == 1.0 and not da_f32:
             # premasked gradient: BatchNorm-backward pass 2 inside the weight gradient's loader, dz written for the input gradient
-            nws = query('cy_conv_wgrad_bf16_bn_ws_floats', Bx, z.shape[1], z.shape[2], Cx, N, cfg.k, cfg.stride)
-        if nws >= 0:
-            ws = _empty((nws,), weight)
+            ws = _empty((query('cy_conv_wgrad_bf16_bn_ws_floats', Bx, z.shape[1], z.shape[2], Cx, N, cfg.k, cfg.stride),), weight)
             dW = _empty((N, Cx, cfg.k, cfg.k), weight)
             with timer.range('conv_bf16_wgrad_bn/' + cfg.name):
                 call('cy_conv_wgrad_bf16_bn', _ptr(x), _ptr(da.contiguous()), _ptr(z), _ptr(dz), _ptr(dW), _ptr(ws), _ptr(scale), _ptr(mean),
@@ -1035,21 +1048,8 @@ class _ConvBlockBF16(torch.autograd.Function):
             call('cy_bn_bwd_apply_bf16', _ptr(z), _ptr(da), 1 if da_f32 else 0, _ptr(dz), _ptr(scale), _ptr(shift), _ptr(mean),
                  _ptr(invstd), slope, _ptr(red), _ptr(dgamma), _ptr(dbeta), P, N, st)
             dW = conv_wgrad_bf16(x, dz, cfg.k, cfg.stride, cfg.pad, cfg.name)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            in_f32, hi = cfg.in_f32, ctx.hin
-            fuse = None
-            if FUSE_BN_BWD_REDUCE_BF16 and hi is not None and not in_f32 and tuple(hi.z.shape) == tuple(x.shape):
-                Cin = x.shape[3]
-                bred = zero_pool.take((STATS_COPIES, Cin, 2), torch.float64, x.device)
-                fuse = (hi.z, hi.scale, hi.shift, hi.mean, hi.invstd, hi.slope, bred)
-            dx = conv_dgrad_bf16(dz, weight, tuple(x.shape), cfg.k, cfg.stride, cfg.pad, in_f32, cfg.name, fuse)
-            if fuse is not None:
-                red_in = _empty((x.shape[3], 2), weight, torch.float64)
-                call('cy_bn_red_fold', _ptr(bred), STATS_COPIES, 1.0, _ptr(red_in), None, None, x.shape[3], st)
-                hi.give_red(red_in, True)
         dbias = _const_zeros(N, weight) if ctx.has_bias else None       # in front of BatchNorm: analytically zero
-        return dx, dW, dbias, dgamma, dbeta, None, None
+        return _input_grad(ctx, dz, x, weight, plan, st), dW, dbias, dgamma, dbeta, None, None
 
 
 def conv_block_bf16(x, weight, bias, gamma, beta, cfg, handover=None):

@@ -6,6 +6,7 @@ and, where `eval` is set, of one eval forward under torch.no_grad()."""
 import torch
 
 C1 = [(3, 32, 3, 1, 1)]
+BF16 = [(3, 64, 3, 1, 1), (64, 128, 3, 1, 1), (128, 128, 4, 2, 1)]     # fp32 first block, then two blocks on the bf16 kernels
 # name -> blocks (cin, cout, k, stride, pad), input shape, layout, and what the case switches
 CASES = {
     'c1_mask': dict(blocks=C1, x=(2, 3, 8, 32), nchw=True, switches={'CONV1_MOMENTS_MIN_PIXELS': 0}),
@@ -15,7 +16,14 @@ CASES = {
     'defer_s2': dict(blocks=[(64, 64, 3, 1, 1), (64, 64, 4, 2, 1)], x=(2, 12, 12, 64), nchw=False, x_grad=True, eval=True),
     'pool': dict(blocks=[(16, 32, 3, 1, 1)], x=(2, 8, 8, 16), nchw=False, pool=True),
     'nobn': dict(conv=(16, 8, 3, 1, 1), slopes=(None, 0.0, 0.1), x=(2, 5, 5, 16), nchw=False),
-    'bf16': dict(blocks=[(3, 64, 3, 1, 1), (64, 128, 3, 1, 1), (128, 128, 4, 2, 1)], x=(2, 3, 8, 32), nchw=True, precision='bf16', eval=True),
+    'bf16': dict(blocks=BF16, x=(2, 3, 8, 32), nchw=True, precision='bf16', eval=True),
+    # every block sums for itself and applies with cy_bn_bwd_apply_bf16; block 3's input gradient is one launch per parity class
+    'bf16_unfused': dict(blocks=BF16, x=(2, 3, 8, 32), nchw=True, precision='bf16',
+                         switches={'FUSE_BN_BWD_APPLY_BF16': False, 'FUSE_BN_BWD_REDUCE_BF16': False, 'BF16_DGRAD_ONE_LAUNCH': False}),
+    # block 3 reads a 9 x 32 map: its parity classes differ in size, so they go out one by one although the switch is on
+    'bf16_odd': dict(blocks=BF16, x=(2, 3, 9, 32), nchw=True, precision='bf16'),
+    # no gradient arrives premasked, so no block takes cy_conv_wgrad_bf16_bn although its switch is on
+    'bf16_apply_only': dict(blocks=BF16, x=(2, 3, 8, 32), nchw=True, precision='bf16', switches={'FUSE_BN_BWD_REDUCE_BF16': False}),
 }
 
 

@@ -48,7 +48,7 @@ def test_headline_layers_keep_their_plan(row):
 def desc(M_rows, Cin, N, taps=9, B=1):
     """A stride-1 forward of M_rows x 1 output pixels per image (the plan reads shapes only)."""
     k = 3 if taps == 9 else 1
-    return ops._fwd_desc_bf16((B, M_rows, 1, Cin), N, k, 1, k // 2)
+    return ops._gemm_fwd_desc(*ops._x_geometry((B, M_rows, 1, Cin), False), N, k, 1, k // 2)
 
 
 def plan_of(a, ncls=1, out_f32=0):

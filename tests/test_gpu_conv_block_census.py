@@ -1,7 +1,8 @@
 """The launch sequence of the conv blocks (ops.conv_block / ops.conv_block_bf16 / ops.affine_act_maxpool under FusedBackbone) is
 locked: tests/golden/conv_block_census.json holds, for every case of tests/conv_block_cases.py, the ordered C-ABI entry points of
 one training forward + backward (and one eval forward).  The file was recorded BEFORE the blocks were split into one Function per
-kind and the hand-over between blocks became ops.BnHandover; it is not regenerated to make this test pass."""
+kind and the hand-over between blocks became ops.BnHandover, its bf16_unfused / bf16_odd / bf16_apply_only cases BEFORE the bf16
+path's decisions moved into ops.conv_plan_bf16; it is not regenerated to make this test pass."""
 import json
 import os
 
@@ -36,6 +37,15 @@ def test_the_table_and_the_recorded_file_cover_the_same_cases():
     assert 'cy_maxpool2_bwd_bn' in flat['pool'] and 'cy_bn_bwd_reduce' not in flat['pool']
     assert 'cy_conv_wgrad_bf16_bn' in flat['bf16'] and 'cy_conv1_bn_bwd_reduce_bf16' in flat['bf16']
     assert 'cy_act_bwd' in golden['nobn']['train_slope_0.1'] and 'cy_act_bwd' not in golden['nobn']['train_slope_None']
+    # bf16_unfused: two forwards, block 3's input gradient class by class (four), block 2's one class -- and every block sums and
+    # applies for itself
+    assert flat['bf16_unfused'].count('cy_conv_gemm_bf16') == 7 and 'cy_conv_gemm_bf16_classes' not in flat['bf16_unfused']
+    assert 'cy_conv_wgrad_bf16_bn' not in flat['bf16_unfused'] and flat['bf16_unfused'].count('cy_bn_bwd_apply_bf16') == 2
+    assert 'cy_conv_wgrad_bf16_bn' not in flat['bf16_apply_only'] and 'cy_conv_gemm_bf16_classes' in flat['bf16_apply_only']
+    # bf16_odd: block 3's input gradient (between its weight gradient and the fold of the sums it took for block 2) is four launches
+    odd = flat['bf16_odd']
+    dgrad3 = odd[odd.index('cy_conv_wgrad_bf16') + 1:odd.index('cy_bn_red_fold')]
+    assert 'cy_conv_gemm_bf16_classes' not in odd and dgrad3.count('cy_conv_gemm_bf16') == 4 and 'cy_conv_wgrad_bf16_bn' in odd
 
 
 @pytest.mark.parametrize('name', sorted(cases.CASES))
