@@ -157,6 +157,10 @@ _SIGS = {
     'cy_multi_copy': [_P, _P, _I, _I, _P, _I, _F, _P],
     'cy_adam_multi': [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _P],
     'cy_adam_multi_dev': [_P, _P, _I, _I, _P, _P],
+    'cy_grad_sumsq_multi': [_P, _P, _I, _I, _P, _P],
+    'cy_grad_clip_finish': [_P, _I, _F, _I, _P, _P, _P],
+    'cy_adam_multi_clip': [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P],
+    'cy_adam_multi_dev_clip': [_P, _P, _I, _I, _P, _P, _P],
     'cy_linear_fwd': [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     'cy_linear_dgrad': [_P, _P, _P, _P, _I, _I, _I, _P],
     'cy_linear_wgrad': [_P, _P, _P, _P, _I, _I, _I, _P],

@@ -10,16 +10,18 @@ struct AdamEntry {
   float* p; const float* g; float* m; float* v; long long n;
 };
 
-__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamEntry* __restrict__ table, const int2* __restrict__ blockmap,
-                                                         int chunk, float step_size, float beta1, float beta2, float eps,
-                                                         float inv_bc2_sqrt) {
+// The update of one block-map entry.  CLIP: the gradient is scaled by the clipping coefficient of csrc/gradnorm.hip on its way in
+// (p.grad itself stays as it is); the instantiation without it is the step as it always was.
+template <bool CLIP>
+__device__ __forceinline__ void adam_chunk(const AdamEntry* __restrict__ table, const int2* __restrict__ blockmap, int chunk,
+                                           float step_size, float beta1, float beta2, float eps, float inv_bc2_sqrt, float coef) {
   const int2 bm = blockmap[blockIdx.x];
   const AdamEntry e = table[bm.x];
   const long long begin = (long long)bm.y * chunk;
   long long end = begin + chunk;
   if (end > e.n) end = e.n;
   for (long long i = begin + threadIdx.x; i < end; i += 256) {
-    const float g = e.g[i];
+    const float g = CLIP ? coef * e.g[i] : e.g[i];
     const float m = beta1 * e.m[i] + (1.f - beta1) * g;
     const float v = beta2 * e.v[i] + (1.f - beta2) * g * g;
     e.m[i] = m;
@@ -29,6 +31,12 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamEntry* __rest
   }
 }
 
+__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamEntry* __restrict__ table, const int2* __restrict__ blockmap,
+                                                         int chunk, float step_size, float beta1, float beta2, float eps,
+                                                         float inv_bc2_sqrt) {
+  adam_chunk<false>(table, blockmap, chunk, step_size, beta1, beta2, eps, inv_bc2_sqrt, 1.f);
+}
+
 // The same step with its scalars read from DEVICE memory: hyper = {lr, beta1, beta2, eps, bias_corr1, bias_corr2}.  A captured HIP
 // graph freezes kernel arguments; the step count (bias corrections) and a scheduler's learning rate change from step to step, so
 // the host refreshes the six floats with one small copy in front of every replay (graph_step.py).
@@ -36,20 +44,26 @@ __global__ __launch_bounds__(256) void adam_multi_dev_kernel(const AdamEntry* __
                                                              int chunk, const float* __restrict__ hyper) {
   const float beta1 = hyper[1], beta2 = hyper[2], eps = hyper[3];
   const float step_size = hyper[0] / hyper[4], inv_bc2_sqrt = 1.f / sqrtf(hyper[5]);
-  const int2 bm = blockmap[blockIdx.x];
-  const AdamEntry e = table[bm.x];
-  const long long begin = (long long)bm.y * chunk;
-  long long end = begin + chunk;
-  if (end > e.n) end = e.n;
-  for (long long i = begin + threadIdx.x; i < end; i += 256) {
-    const float g = e.g[i];
-    const float m = beta1 * e.m[i] + (1.f - beta1) * g;
-    const float v = beta2 * e.v[i] + (1.f - beta2) * g * g;
-    e.m[i] = m;
-    e.v[i] = v;
-    const float denom = sqrtf(v) * inv_bc2_sqrt + eps;
-    e.p[i] -= step_size * (m / denom);
-  }
+  adam_chunk<false>(table, blockmap, chunk, step_size, beta1, beta2, eps, inv_bc2_sqrt, 1.f);
+}
+
+// The two steps behind the verdict of cy_grad_clip_finish: record = {total_norm, coef, go, 0} in device memory.  go == 0 (a
+// non-finite gradient under the guard) returns before anything is read or written: the record is one value for the whole launch,
+// so every workgroup takes the same way.
+__global__ __launch_bounds__(256) void adam_multi_clip_kernel(const AdamEntry* __restrict__ table, const int2* __restrict__ blockmap,
+                                                              int chunk, float step_size, float beta1, float beta2, float eps,
+                                                              float inv_bc2_sqrt, const float* __restrict__ record) {
+  if (record[2] == 0.f) return;
+  adam_chunk<true>(table, blockmap, chunk, step_size, beta1, beta2, eps, inv_bc2_sqrt, record[1]);
+}
+
+__global__ __launch_bounds__(256) void adam_multi_dev_clip_kernel(const AdamEntry* __restrict__ table, const int2* __restrict__ blockmap,
+                                                                  int chunk, const float* __restrict__ hyper,
+                                                                  const float* __restrict__ record) {
+  if (record[2] == 0.f) return;
+  const float beta1 = hyper[1], beta2 = hyper[2], eps = hyper[3];
+  const float step_size = hyper[0] / hyper[4], inv_bc2_sqrt = 1.f / sqrtf(hyper[5]);
+  adam_chunk<true>(table, blockmap, chunk, step_size, beta1, beta2, eps, inv_bc2_sqrt, record[1]);
 }
 
 // flat[offset_k + i] = scale * tensor_k[i] (pack) or tensor_k[i] = scale * flat[offset_k + i] (unpack) for a whole list
@@ -94,5 +108,25 @@ extern "C" int cy_adam_multi_dev(const void* table, const void* blockmap, int n_
   CY_REQUIRE(table && blockmap && hyper && n_blocks > 0 && chunk > 0, "cy_adam_multi_dev: bad arguments");
   adam_multi_dev_kernel<<<n_blocks, 256, 0, (hipStream_t)stream>>>((const AdamEntry*)table, (const int2*)blockmap, chunk, hyper);
   CY_LAUNCH_CHECK("cy_adam_multi_dev");
+  return 0;
+}
+
+extern "C" int cy_adam_multi_clip(const void* table, const void* blockmap, int n_blocks, int chunk, float lr, float beta1,
+                                  float beta2, float eps, float bias_corr1, float bias_corr2, const float* record, void* stream) {
+  CY_REQUIRE(table && blockmap && record && n_blocks > 0 && chunk > 0, "cy_adam_multi_clip: bad arguments");
+  CY_REQUIRE(bias_corr1 > 0.f && bias_corr2 > 0.f, "cy_adam_multi_clip: bias corrections must be positive");
+  adam_multi_clip_kernel<<<n_blocks, 256, 0, (hipStream_t)stream>>>((const AdamEntry*)table, (const int2*)blockmap, chunk,
+                                                                    lr / bias_corr1, beta1, beta2, eps,
+                                                                    1.f / sqrtf(bias_corr2), record);
+  CY_LAUNCH_CHECK("cy_adam_multi_clip");
+  return 0;
+}
+
+extern "C" int cy_adam_multi_dev_clip(const void* table, const void* blockmap, int n_blocks, int chunk, const float* hyper,
+                                      const float* record, void* stream) {
+  CY_REQUIRE(table && blockmap && hyper && record && n_blocks > 0 && chunk > 0, "cy_adam_multi_dev_clip: bad arguments");
+  adam_multi_dev_clip_kernel<<<n_blocks, 256, 0, (hipStream_t)stream>>>((const AdamEntry*)table, (const int2*)blockmap, chunk, hyper,
+                                                                        record);
+  CY_LAUNCH_CHECK("cy_adam_multi_dev_clip");
   return 0;
 }

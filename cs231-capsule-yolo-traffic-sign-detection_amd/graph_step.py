@@ -9,6 +9,8 @@ and no kernel allocates, so `torch.cuda.graph` captures the step as it is: hipSt
 tensors the step creates come from the graph's private pool and keep their addresses across replays.  What changes from step to
 step lives in device memory: the batch (static input buffers, filled by `copy_` before the replay) and the optimizer's scalars
 (step count -> bias corrections, a scheduler's learning rate: `optim.Adam.graph_hyper`, six floats refreshed before the replay).
+With `optim.Adam(max_grad_norm=..., skip_nonfinite=...)` the captured step also holds the gradient-norm reduction and its verdict
+(csrc/gradnorm.hip): a replay clips, or skips a non-finite step, with nothing crossing to the host.
 Single process only: the data-parallel gradient all-reduce stays on the eager path.
 """
 import gc
@@ -42,6 +44,8 @@ class GraphedStep(object):
         snap_model = dict((k, v.detach().clone()) for k, v in model.state_dict().items())
         snap_opt = dict((p, dict((k, (v.detach().clone() if torch.is_tensor(v) else v)) for k, v in optimizer.state[p].items()))
                         for g in optimizer.param_groups for p in g['params'] if p in optimizer.state and len(optimizer.state[p]))
+        # optim.Adam's clipping verdict and its count of skipped steps (max_grad_norm / skip_nonfinite) are optimizer state too
+        snap_clip = optimizer._clip_buf.clone() if getattr(optimizer, '_clip_buf', None) is not None else None
         s = torch.cuda.Stream(device=dev)
         s.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(s):
@@ -63,7 +67,11 @@ class GraphedStep(object):
                             v.copy_(old[k]) if old is not None else v.zero_()
                         else:
                             st[k] = old[k] if old is not None else 0
+            if getattr(optimizer, '_clip_buf', None) is not None:
+                optimizer._clip_buf.copy_(snap_clip) if snap_clip is not None else optimizer._clip_reset()
         ops._bump_param_epoch()
+        # frozen kernel arguments of the captured cy_grad_clip_finish, and which Adam kernel the capture holds
+        self._clip_cfg = (getattr(optimizer, 'max_grad_norm', None), getattr(optimizer, 'skip_nonfinite', False))
         self.graph = torch.cuda.CUDAGraph()
         self._refresh_scalars(advance=False)          # valid numbers during the capture (they are not read until a replay)
         optimizer.graph_hyper = self._hyper_dev
@@ -92,8 +100,8 @@ class GraphedStep(object):
         return y_hat, loss
 
     def _captured_step(self):
-        # optim.Adam.step with graph_hyper set launches cy_adam_multi_dev; its per-parameter step counters must not move during the
-        # capture (the replay's counters are advanced by _refresh_scalars)
+        # optim.Adam.step with graph_hyper set launches cy_adam_multi_dev (or its _clip variant); its per-parameter step counters must
+        # not move during the capture (the replay's counters are advanced by _refresh_scalars)
         saved = dict((p, int(self.opt.state[p]['step'])) for g in self.opt.param_groups for p in g['params'] if p in self.opt.state and len(self.opt.state[p]))
         self.opt.step()
         for p, t in saved.items():
@@ -123,6 +131,9 @@ class GraphedStep(object):
         """One training step on `batch`; returns (y_hat, loss) -- the graph's static output tensors (overwritten by the next call)."""
         if any(b.shape != s.shape or b.dtype != s.dtype for b, s in zip(batch, self.static)):
             return self._eager(*batch)                # a ragged last batch: the eager step (same kernels)
+        if (getattr(self.opt, 'max_grad_norm', None), getattr(self.opt, 'skip_nonfinite', False)) != self._clip_cfg:
+            raise RuntimeError('GraphedStep: the optimizer\'s max_grad_norm / skip_nonfinite were %r / %r when the step was captured and '
+                               'are frozen in it; capture a new step to change them' % self._clip_cfg)
         for s, b in zip(self.static, batch):
             if s.data_ptr() != b.data_ptr():
                 s.copy_(b, non_blocking=True)

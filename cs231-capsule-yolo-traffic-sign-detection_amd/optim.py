@@ -1,7 +1,18 @@
 """torch.optim.Adam replacement: every parameter updated by ONE multi-tensor HIP launch per step
 (csrc/adam.hip).  Same hyper-parameters, state layout ('step', 'exp_avg', 'exp_avg_sq') and update
-formula as torch.optim.Adam (main.py:280), so optimizer checkpoints interchange."""
+formula as torch.optim.Adam (main.py:280), so optimizer checkpoints interchange.
+
+Optional, both decided on the device without a host synchronisation (csrc/gradnorm.hip):
+  max_grad_norm=X      global-norm clipping: the update uses coef * g with coef = min(1, X / (total_norm + 1e-6)), total_norm over
+                       every gradient this step() applies.  Unlike torch.nn.utils.clip_grad_norm_, p.grad itself is NOT rewritten.
+  skip_nonfinite=True  a step whose total_norm is not finite (an inf or NaN anywhere in the gradients) changes no bit of any
+                       parameter, exp_avg or exp_avg_sq, and a device counter goes up by one.  The host does not learn of the skip
+                       (that would be a synchronisation): state['step'], hence the bias corrections of later steps, advance as in
+                       any other step.
+With both off, step() issues exactly the launches it issues without them and none of their device state exists."""
 import ctypes as C
+import math
+import numbers
 
 import numpy as np
 import torch
@@ -13,13 +24,48 @@ _CHUNK = 16384
 
 
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False):
+        if max_grad_norm is not None:
+            if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, numbers.Real) or \
+                    not math.isfinite(max_grad_norm) or not max_grad_norm > 0:
+                raise ValueError('capsyolo_amd.optim.Adam: max_grad_norm must be a positive finite number or None, got %r' % (max_grad_norm,))
         # weight_decay and amsgrad are in the group only so that a checkpoint of this optimizer loads into torch.optim.Adam, which
         # reads them from the loaded group; step() refuses any value but torch's default (a checkpoint of torch's may carry one)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False))
         self._plan_key, self._plan = None, None
         self.graph_tables = None     # ... and per group (pinned host, device) pointer tables [n parameters with a gradient][5]
         self.graph_hyper = None      # graph_step.GraphedStep: per group a device tensor of the six step scalars (cy_adam_multi_dev)
+        # attributes, not param_groups entries: state_dict() is that of torch.optim.Adam with or without them
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._clip_buf = None        # device int64[3], made by the first step that needs it: {record as 4 floats, skipped}
+        self._partial = None         # device float64[chunks of all parameters]: the sums of squares of cy_grad_sumsq_multi
+
+    @property
+    def clip_record(self):
+        """Device float32[4] = {total_norm, coef, go (1 | 0), 0} of the last step; None before the first step with an option on."""
+        return None if self._clip_buf is None else self._clip_buf[:2].view(torch.float32)
+
+    @property
+    def skipped_dev(self):
+        """Device int64[1]: steps skipped by skip_nonfinite so far; None before the first step with an option on."""
+        return None if self._clip_buf is None else self._clip_buf[2:3]
+
+    def _clip_reset(self):
+        """record = {0, 1, 1, 0}, skipped = 0: the state before any step (graph_step.GraphedStep after its warm-up steps)."""
+        self.clip_record.copy_(torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float32))
+        self.skipped_dev.zero_()
+
+    def grad_stats(self):
+        """{'norm': total gradient norm of the last step, 'coef': its clipping coefficient, 'skipped': steps skipped so far}.
+        ONE device-to-host copy and ONE synchronisation: call it once per epoch (main.py does), not per step."""
+        if self.max_grad_norm is None and not self.skip_nonfinite:
+            raise RuntimeError('capsyolo_amd.optim.Adam.grad_stats: neither max_grad_norm nor skip_nonfinite is on')
+        if self._clip_buf is None:
+            return {'norm': 0.0, 'coef': 1.0, 'skipped': 0}
+        host = self._clip_buf.cpu()
+        rec = host[:2].view(torch.float32)
+        return {'norm': float(rec[0]), 'coef': float(rec[1]), 'skipped': int(host[2])}
 
     def step_scalars(self, group, t):
         """{lr, beta1, beta2, eps, 1 - beta1^t, 1 - beta2^t}: the scalars of step t of a group."""
@@ -54,9 +100,60 @@ class Adam(torch.optim.Optimizer):
         self._ring_events[k] = ev
         return (self._table_dev, self._bm, len(blocks))
 
+    def _tables(self, group, entries):
+        """(pointer table, block map, number of blocks) of one launch, uploaded on the step's stream."""
+        if self.graph_hyper is not None:
+            # inside a captured step (graph_step.GraphedStep): the pointer table is a tensor of the graph's own (uploaded by a
+            # captured copy from a pinned buffer that nothing else writes), the block map is the eager plan's (same sizes:
+            # the warm-up steps built it), the scalars come from device memory
+            sizes = tuple(e[0].numel() for e in entries)
+            if getattr(self, '_bm_key', None) != (sizes, entries[0][0].device):
+                raise RuntimeError('capsyolo_amd.optim.Adam: capture a step only after an eager step with the same parameters')
+            # (pinned and device buffers made by GraphedStep BEFORE the capture: pinning memory is not a capturable operation)
+            host, table = self.graph_tables[id(group)]
+            if tuple(host.shape) != (len(entries), 5):
+                raise RuntimeError('capsyolo_amd.optim.Adam: the captured step updates %d parameters, its table was made for %d'
+                                   % (len(entries), host.shape[0]))
+            host.numpy()[...] = np.asarray([(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
+                                            for p, g, m, v in entries], dtype=np.int64)
+            table.copy_(host, non_blocking=True)
+            nblocks = sum((p.numel() + _CHUNK - 1) // _CHUNK for p, _, _, _ in entries)
+            return (table, self._bm, nblocks)
+        key = tuple(x.data_ptr() for e in entries for x in e)
+        if key != self._plan_key:
+            self._plan, self._plan_key = self._build_plan(entries, entries[0][0].device), key
+        return self._plan
+
+    def _grad_verdict(self, launches, stream):
+        """The sums of squares of every launch's gradients into consecutive slices of one partial buffer, then ONE
+        cy_grad_clip_finish: the record that every Adam launch of this step reads.  Returns the launches' tables where they are
+        still valid for the Adam launches (one launch, or the captured step's per-group tables), else None."""
+        dev = launches[0][2][0][0].device
+        need = sum((p.numel() + _CHUNK - 1) // _CHUNK for _, _, entries in launches for p, _, _, _ in entries)
+        if self._clip_buf is None:
+            self._clip_buf = torch.zeros(3, dtype=torch.int64, device=dev)
+            self._clip_reset()
+        if self._partial is None or self._partial.numel() < need:
+            # once: room for every parameter of every group (each is in at most one launch of a step)
+            every = sum((p.numel() + _CHUNK - 1) // _CHUNK for g in self.param_groups for p in g['params'])
+            self._partial = torch.empty(max(need, every), dtype=torch.float64, device=dev)
+        tables, off = [], 0
+        for group, _, entries in launches:
+            table, bm, nblocks = self._tables(group, entries)
+            call('cy_grad_sumsq_multi', C.c_void_p(table.data_ptr()), C.c_void_p(bm.data_ptr()), nblocks, _CHUNK,
+                 C.c_void_p(self._partial.data_ptr() + 8 * off), stream)
+            tables.append((table, bm, nblocks))
+            off += nblocks
+        call('cy_grad_clip_finish', C.c_void_p(self._partial.data_ptr()), off,
+             0.0 if self.max_grad_norm is None else self.max_grad_norm, int(self.skip_nonfinite),
+             C.c_void_p(self.clip_record.data_ptr()), C.c_void_p(self.skipped_dev.data_ptr()), stream)
+        # the eager plan is ONE device table that the next launch's upload overwrites
+        return tables if self.graph_hyper is not None or len(launches) == 1 else None
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        launches = []
         for group in self.param_groups:
             if group.get('weight_decay', 0) != 0 or group.get('amsgrad', False) or group.get('maximize', False):
                 raise RuntimeError('capsyolo_amd.optim.Adam implements plain Adam only: weight_decay, amsgrad and maximize must be off')
@@ -78,34 +175,29 @@ class Adam(torch.optim.Optimizer):
                 raise RuntimeError('capsyolo_amd.optim.Adam: the parameters of a captured step must share their step count')
             # one launch per step count: a parameter that had no gradient in some step lags behind the others of its group, and
             # the bias corrections are those of its own count (as in torch.optim.Adam)
-            for t, entries in by_step.items():
-                if self.graph_hyper is not None:
-                    # inside a captured step (graph_step.GraphedStep): the pointer table is a tensor of the graph's own (uploaded by a
-                    # captured copy from a pinned buffer that nothing else writes), the block map is the eager plan's (same sizes:
-                    # the warm-up steps built it), the scalars come from device memory
-                    sizes = tuple(e[0].numel() for e in entries)
-                    if getattr(self, '_bm_key', None) != (sizes, entries[0][0].device):
-                        raise RuntimeError('capsyolo_amd.optim.Adam: capture a step only after an eager step with the same parameters')
-                    # (pinned and device buffers made by GraphedStep BEFORE the capture: pinning memory is not a capturable operation)
-                    host, table = self.graph_tables[id(group)]
-                    if tuple(host.shape) != (len(entries), 5):
-                        raise RuntimeError('capsyolo_amd.optim.Adam: the captured step updates %d parameters, its table was made for %d'
-                                           % (len(entries), host.shape[0]))
-                    host.numpy()[...] = np.asarray([(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
-                                                    for p, g, m, v in entries], dtype=np.int64)
-                    table.copy_(host, non_blocking=True)
-                    nblocks = sum((p.numel() + _CHUNK - 1) // _CHUNK for p, _, _, _ in entries)
-                    call('cy_adam_multi_dev', C.c_void_p(table.data_ptr()), C.c_void_p(self._bm.data_ptr()), nblocks, _CHUNK,
-                         C.c_void_p(self.graph_hyper[id(group)].data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-                    _ops._bump_param_epoch()
-                    continue
-                key = tuple(x.data_ptr() for e in entries for x in e)
-                if key != self._plan_key:
-                    self._plan, self._plan_key = self._build_plan(entries, entries[0][0].device), key
-                table, bm, nblocks = self._plan
+            launches.extend((group, t, entries) for t, entries in by_step.items())
+        if not launches:
+            return loss
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        clip = self.max_grad_norm is not None or self.skip_nonfinite
+        tables = self._grad_verdict(launches, stream) if clip else None
+        record = C.c_void_p(self.clip_record.data_ptr()) if clip else None
+        for k, (group, t, entries) in enumerate(launches):
+            table, bm, nblocks = tables[k] if tables is not None else self._tables(group, entries)
+            if self.graph_hyper is not None:
+                hyper = C.c_void_p(self.graph_hyper[id(group)].data_ptr())
+                if clip:
+                    call('cy_adam_multi_dev_clip', C.c_void_p(table.data_ptr()), C.c_void_p(bm.data_ptr()), nblocks, _CHUNK, hyper,
+                         record, stream)
+                else:
+                    call('cy_adam_multi_dev', C.c_void_p(table.data_ptr()), C.c_void_p(bm.data_ptr()), nblocks, _CHUNK, hyper, stream)
+            else:
                 b1, b2 = group['betas']
-                call('cy_adam_multi', C.c_void_p(table.data_ptr()), C.c_void_p(bm.data_ptr()), nblocks, _CHUNK,
-                     float(group['lr']), float(b1), float(b2), float(group['eps']), float(1.0 - b1 ** t),
-                     float(1.0 - b2 ** t), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-                _ops._bump_param_epoch()          # parameters changed through raw pointers: eval-mode fold caches are stale
+                scalars = (float(group['lr']), float(b1), float(b2), float(group['eps']), float(1.0 - b1 ** t), float(1.0 - b2 ** t))
+                if clip:
+                    call('cy_adam_multi_clip', C.c_void_p(table.data_ptr()), C.c_void_p(bm.data_ptr()), nblocks, _CHUNK, *scalars,
+                         record, stream)
+                else:
+                    call('cy_adam_multi', C.c_void_p(table.data_ptr()), C.c_void_p(bm.data_ptr()), nblocks, _CHUNK, *scalars, stream)
+            _ops._bump_param_epoch()          # parameters changed through raw pointers: eval-mode fold caches are stale
         return loss

@@ -791,6 +791,27 @@ int cy_adam_multi(const void* table, const void* blockmap, int n_blocks, int chu
  * training step captured in a HIP graph, whose kernel arguments are frozen (the host refreshes hyper before every replay). */
 int cy_adam_multi_dev(const void* table, const void* blockmap, int n_blocks, int chunk, const float* hyper, void* stream);
 
+/* Gradient-norm clipping and the non-finite-step guard of optim.Adam, decided on the device (csrc/gradnorm.hip).  The rule, over
+ * every gradient G that one optimizer step applies:
+ *   total_norm = sqrt(sum over G of g^2), squares formed and summed in double from the fp32 values, in a fixed order (no atomics:
+ *                the same gradients give the same bits);
+ *   coef       = min(1, max_norm / (total_norm + 1e-6)) in double, rounded once to fp32; 1 when max_norm <= 0 (no clipping);
+ *   go         = 0 when guard != 0 and total_norm is not finite (some gradient element is inf or NaN), else 1.
+ * cy_grad_sumsq_multi takes Adam's table and block map (above) and writes partial[b], b < n_blocks, one workgroup per entry; the
+ * launches of one step fill consecutive slices of one partial buffer.  Gradients may start at any 4-byte offset.
+ * cy_grad_clip_finish adds the n_partial partials in one workgroup and writes record[4] = {total_norm, coef, go, 0}; with go == 0 it
+ * also adds 1 to *skipped.
+ * The two _clip steps are cy_adam_multi / cy_adam_multi_dev with coef * g in the place of g (the gradient tensors are not
+ * rewritten); with record[2] == 0 they return without touching any parameter, exp_avg or exp_avg_sq.  coef == 1 gives the bits of
+ * the plain step. */
+int cy_grad_sumsq_multi(const void* table, const void* blockmap, int n_blocks, int chunk, double* partial, void* stream);
+int cy_grad_clip_finish(const double* partial, int n_partial, float max_norm /* <= 0: no clipping */, int guard,
+                        float* record /* [4] = {total_norm, coef, go (1 | 0), 0} */, long long* skipped, void* stream);
+int cy_adam_multi_clip(const void* table, const void* blockmap, int n_blocks, int chunk, float lr, float beta1, float beta2,
+                       float eps, float bias_corr1, float bias_corr2, const float* record, void* stream);
+int cy_adam_multi_dev_clip(const void* table, const void* blockmap, int n_blocks, int chunk, const float* hyper,
+                           const float* record, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,8 @@ keys, same registry shape ``name -> (ModelCls, loss_fn, predict_fn, metric)`` (m
   --synthetic N     train on N synthetic GTSRB/GTSDB-shaped samples (the reference ships no data)
   --n_epochs E, --batch_size B   override params.json
   --fix_ckpt_dir    save checkpoints into model_dir, where --restore looks for them
+  --clip_norm X, --skip_nonfinite   global gradient-norm clipping and a guard against non-finite steps, both decided on the device
+                    inside capsyolo_amd.optim.Adam (params.json keys clip_norm, skip_nonfinite)
   params.json keys ``n_iter`` (routing iterations, default 3), ``sync_bn`` (data parallel only)
   --model darkcapsule2 | darkcapsule3   the reference's unwired variants with their losses (models.py:271-337, 403-463)
 ``--mode predict --model darknet_d|darknet_r --combine cnn|capsule --restore last|best`` runs the two-stage chain
@@ -132,6 +134,12 @@ parser.add_argument('--min_hits', type=int, default=None, metavar='H', help='--t
 parser.add_argument('--track_decay', type=float, default=None, metavar='D',
                     help='--track: weight in [0, 1] of the older class scores in a track\'s class vote (default 0.9)')
 parser.add_argument('--no_motion', action='store_true', help='--track: match against a track\'s last box, not against the box moved on by its last step')
+parser.add_argument('--clip_norm', type=float, default=None, metavar='X',
+                    help='clip the global gradient norm of every step to X (params.json key clip_norm): inside the project\'s Adam on the '
+                         'device, without rewriting the gradients; torch.nn.utils.clip_grad_norm_ for the plain-torch cnn baseline')
+parser.add_argument('--skip_nonfinite', action='store_true',
+                    help='a step with an inf or NaN gradient leaves parameters and optimizer state as they are, decided on the device '
+                         '(params.json key skip_nonfinite); needs the project\'s Adam')
 parser.add_argument('--fix_ckpt_dir', action='store_true',
                     help='save checkpoints into model_dir (where --restore reads) instead of model_dir + str(train_frac)')
 
@@ -251,6 +259,10 @@ def train(x, y, model, optimizer, loss_fn, metric, params, bucket, if_eval=True)
     x, y = utils.shuffle(x, y)
     n_batch, it = _batches(x, y, params.batch_size)
     avg_loss, avg_iou, y_hat, y_true = 0.0, 0.0, [], []
+    # --skip_nonfinite: the epoch loss is the mean over the steps with a finite loss value (a skipped batch would hand NaN to
+    # ReduceLROnPlateau); the value is read every step anyway
+    guard, finite_sum, finite_n = getattr(params, 'skip_nonfinite', False), 0.0, 0
+    clip_torch = getattr(params, 'clip_norm', None) if not isinstance(optimizer, Adam) else None
     want_metric = if_eval and metric is not None
     graphed = getattr(params, 'graph', False) and params.world == 1 and params.device != 'cpu'
     for x_bch, y_bch in _feed(it, params, getattr(params, 'augment_source', None)):
@@ -265,7 +277,11 @@ def train(x, y, model, optimizer, loss_fn, metric, params, bucket, if_eval=True)
             if want_metric:
                 y_hat.append(y_hat_bch.detach().clone())  # the graph's output tensor is overwritten by the next replay
                 y_true.append(y_bch.detach().clone())
-            avg_loss += loss.item() / n_batch
+            value = loss.item()
+            if not guard:
+                avg_loss += value / n_batch
+            elif np.isfinite(value):
+                finite_sum, finite_n = finite_sum + value, finite_n + 1
             if params.model == 'darknet_d':
                 avg_iou += params.avg_iou.item() / n_batch
             continue
@@ -276,10 +292,18 @@ def train(x, y, model, optimizer, loss_fn, metric, params, bucket, if_eval=True)
         optimizer.zero_grad()
         loss.backward()
         bucket.allreduce_mean()
+        if clip_torch is not None:                       # the plain-torch cnn baseline; optim.Adam clips inside its step
+            torch.nn.utils.clip_grad_norm_([p for g in optimizer.param_groups for p in g['params']], clip_torch)
         optimizer.step()
-        avg_loss += loss.item() / n_batch
+        value = loss.item()
+        if not guard:
+            avg_loss += value / n_batch
+        elif np.isfinite(value):
+            finite_sum, finite_n = finite_sum + value, finite_n + 1
         if params.model == 'darknet_d':
             avg_iou += params.avg_iou.item() / n_batch
+    if guard:
+        avg_loss = finite_sum / finite_n if finite_n else float('nan')
     score = _metric(metric, y_true, y_hat, params) if want_metric else -1
     if params.model == 'darknet_d' and params.rank == 0:
         print('train avg iou: {:05.3f}'.format(avg_iou), flush=True)
@@ -336,9 +360,13 @@ def train_and_evaluate(model, optimizer, loss_fn, metric, params, data, model_di
                                    'optim_dict': optimizer.state_dict()}, is_best=is_best,
                                   checkpoint=checkpoint_dir(model_dir, params))
             if if_eval:
+                tail = ''
+                if isinstance(optimizer, Adam) and (optimizer.max_grad_norm is not None or optimizer.skip_nonfinite):
+                    stats = optimizer.grad_stats()       # one copy and one synchronisation per epoch
+                    tail = ' | grad norm: {:.4g} | skipped {:d}'.format(stats['norm'], stats['skipped'])
                 print('epoch {} | train loss: {:05.3f} | eval loss: {:05.3f} | best eval loss: {:05.3f} | '
                       'train metric: {:05.3f} | eval metric: {:05.3f} | best eval metric {:05.3f}'.format(
-                          epoch + 1, loss_tr, loss_ev, best_loss_ev, metric_tr, metric_ev, best_metric_ev), flush=True)
+                          epoch + 1, loss_tr, loss_ev, best_loss_ev, metric_tr, metric_ev, best_metric_ev) + tail, flush=True)
                 metrics_tr.append(metric_tr)
                 metrics_ev.append(metric_ev)
                 np.save(os.path.join(model_dir, 'metrics_tr'), metrics_tr)
@@ -371,6 +399,11 @@ def load_params(model_dir, args):
         params.batch_size = args.batch_size
     params.fix_ckpt_dir = args.fix_ckpt_dir
     params.graph = args.graph
+    if getattr(args, 'clip_norm', None) is not None:                                     # the command line wins
+        params.clip_norm = args.clip_norm
+    elif not hasattr(params, 'clip_norm'):
+        params.clip_norm = None
+    params.skip_nonfinite = bool(getattr(args, 'skip_nonfinite', False) or getattr(params, 'skip_nonfinite', False))
     if args.model == 'cnn' and getattr(args, 'cnn_kernels', None) is not None:
         params.cnn_kernels = args.cnn_kernels
     return params
@@ -763,6 +796,11 @@ def main(argv=None):
     if args.model_dir is not None:
         model_dir = args.model_dir
     params = load_params(model_dir, args)
+    if args.model == 'cnn' and not _cnn_on_hip(params) and params.skip_nonfinite:
+        raise SystemExit('--skip_nonfinite needs the project\'s Adam (capsyolo_amd.optim.Adam): the plain-torch cnn baseline trains with '
+                         'torch.optim.Adam; use --cnn_kernels hip or another model')
+    if params.clip_norm is not None and not (np.isfinite(params.clip_norm) and params.clip_norm > 0):
+        raise SystemExit('--clip_norm must be a positive finite number, got %r' % (params.clip_norm,))
     if args.nms_class_aware and int(getattr(params, 'n_classes', 0)) == 0:
         raise SystemExit('--nms_class_aware needs a detector with class scores (n_classes > 0 in %s/params.json)' % model_dir)
     params.rank, params.world, local_rank = dp.init_from_env()
@@ -793,7 +831,8 @@ def main(argv=None):
                 param.requires_grad = False
     trainable = [p for p in model.parameters() if p.requires_grad]
     torch_cnn = args.model == 'cnn' and not _cnn_on_hip(params)
-    optimizer = torch.optim.Adam(trainable, lr=args.lr) if torch_cnn else Adam(trainable, lr=args.lr)
+    optimizer = torch.optim.Adam(trainable, lr=args.lr) if torch_cnn else \
+        Adam(trainable, lr=args.lr, max_grad_norm=params.clip_norm, skip_nonfinite=params.skip_nonfinite)
 
     if args.mode in ('train', 'overfit'):
         if args.augment:
