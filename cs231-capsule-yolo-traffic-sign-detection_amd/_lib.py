@@ -61,6 +61,7 @@ _SIGS = {
     'cy_conv_gemm': [C.POINTER(ConvGemm), _P],
     'cy_conv_wgrad': [C.POINTER(ConvWgrad), _P],
     'cy_channel_sum': [_P, _P, _L, _I, _P],
+    'cy_channel_sum_ws': [_P, _P, _P, _L, _L, _I, _P],
     'cy_wino_pack_weights': [_P, _P, _I, _I, _I, _P],
     'cy_conv1_3x3_fwd': [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P],
     'cy_conv1_3x3_stats': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
@@ -161,6 +162,10 @@ _SIGS = {
     'cy_grad_clip_finish': [_P, _I, _F, _I, _P, _P, _P],
     'cy_adam_multi_clip': [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P],
     'cy_adam_multi_dev_clip': [_P, _P, _I, _I, _P, _P, _P],
+    'cy_adam_multi_ema': [_P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P],
+    'cy_adam_multi_dev_ema': [_P, _P, _P, _I, _I, _P, _P],
+    'cy_adam_multi_clip_ema': [_P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P, _P],
+    'cy_adam_multi_dev_clip_ema': [_P, _P, _P, _I, _I, _P, _P, _P],
     'cy_linear_fwd': [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     'cy_linear_dgrad': [_P, _P, _P, _P, _I, _I, _I, _P],
     'cy_linear_wgrad': [_P, _P, _P, _P, _I, _I, _I, _P],
@@ -170,6 +175,7 @@ _RET = {
     'capsyolo_last_error': (C.c_char_p, []),
     'capsyolo_abi_version': (C.c_int, []),
     'cy_conv_packed_floats': (_L, [_I, _I]),
+    'cy_channel_sum_ws_floats': (_L, [_L, _I]),
     'cy_conv_bf16_packed_elems': (_L, [_I, _I]),
     'cy_conv_wgrad_bf16_ws_floats': (_L, [_I, _I, _I, _I, _I, _I, _I]),
     'cy_conv_wgrad_bf16_bn_ws_floats': (_L, [_I, _I, _I, _I, _I, _I, _I]),

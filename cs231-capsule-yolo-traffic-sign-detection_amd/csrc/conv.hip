@@ -699,9 +699,10 @@ __global__ __launch_bounds__(256) void wgrad_reduce_wide_kernel(const float* __r
   }
 }
 
-// out[n] = sum_p dZ[p][n]; grid (ceil(N/64), splits); one atomic per (block, n)
+// out[n] = sum_p dZ[p][n]; grid (ceil(N/64), splits); one atomic per (block, n).  With `partial` the block's sum goes to
+// partial[split][n] instead (no atomics): channel_sum_finish_kernel adds the splits in a fixed order.
 __global__ void channel_sum_kernel(const float* __restrict__ dZ, float* __restrict__ out, long long P, int N,
-                                   long long rows_per_block) {
+                                   long long rows_per_block, float* __restrict__ partial) {
   __shared__ float red[4][64];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int n = blockIdx.x * 64 + lane;
@@ -713,7 +714,30 @@ __global__ void channel_sum_kernel(const float* __restrict__ dZ, float* __restri
     for (long long r = r0 + wave; r < r1; r += 4) s += dZ[r * N + n];
   red[wave][lane] = s;
   __syncthreads();
-  if (wave == 0 && n < N) atomicAdd(out + n, red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]);
+  if (wave == 0 && n < N) {
+    const float v = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
+    if (partial) partial[(long long)blockIdx.y * N + n] = v;
+    else atomicAdd(out + n, v);
+  }
+}
+
+// out[n] = partial[0][n] + ... + partial[splits - 1][n] in a fixed order: wave w of 16 adds splits w, w + 16, ..., then a fixed tree
+// through LDS.  The same partials give the same bits in every run.
+__global__ __launch_bounds__(1024) void channel_sum_finish_kernel(const float* __restrict__ partial, float* __restrict__ out, int splits,
+                                                                  int N) {
+  __shared__ float red[16][64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int n = blockIdx.x * 64 + lane;
+  float s = 0.f;
+  if (n < N)
+    for (int k = wave; k < splits; k += 16) s += partial[(long long)k * N + n];
+  red[wave][lane] = s;
+  __syncthreads();
+  for (int h = 8; h > 0; h >>= 1) {
+    if (wave < h) red[wave][lane] += red[wave + h][lane];
+    __syncthreads();
+  }
+  if (wave == 0 && n < N) out[n] = red[0][lane];
 }
 
 // Pixel splits of the weight-gradient reduction.  Blocks are long-running (thousands of MFMA stages) and only
@@ -928,17 +952,45 @@ extern "C" int cy_conv_wgrad(const cy_conv_wgrad_t* a, void* stream) {
   return 0;
 }
 
+// the row splits of the channel sum: (number of splits, rows per split)
+static void channel_sum_splits(long long P, int N, long long* splits, long long* rpb) {
+  const int nb = (N + 63) / 64;
+  long long sp = cy_ceil_div(2048, nb);
+  if (sp > cy_ceil_div(P, 64)) sp = cy_ceil_div(P, 64);
+  *rpb = cy_ceil_div(P, sp);
+  *splits = cy_ceil_div(P, *rpb);
+}
+
 extern "C" int cy_channel_sum(const float* dZ, float* out, long long P, int N, void* stream) {
   CY_REQUIRE(dZ && out && P > 0 && N > 0, "cy_channel_sum: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(out, 0, (size_t)N * 4, s);
   if (e != hipSuccess) return cy_set_error((int)e, "cy_channel_sum: memset: %s", hipGetErrorString(e));
-  const int nb = (N + 63) / 64;
-  long long splits = cy_ceil_div(2048, nb);
-  if (splits > cy_ceil_div(P, 64)) splits = cy_ceil_div(P, 64);
-  const long long rpb = cy_ceil_div(P, splits);
-  splits = cy_ceil_div(P, rpb);
-  channel_sum_kernel<<<dim3(nb, (unsigned)splits), 256, 0, s>>>(dZ, out, P, N, rpb);
+  long long splits, rpb;
+  channel_sum_splits(P, N, &splits, &rpb);
+  channel_sum_kernel<<<dim3((N + 63) / 64, (unsigned)splits), 256, 0, s>>>(dZ, out, P, N, rpb, nullptr);
   CY_LAUNCH_CHECK("cy_channel_sum");
+  return 0;
+}
+
+extern "C" long long cy_channel_sum_ws_floats(long long P, int N) {
+  if (P <= 0 || N <= 0) return 0;
+  long long splits, rpb;
+  channel_sum_splits(P, N, &splits, &rpb);
+  return splits > 1 ? splits * N : 0;          // one split: cy_channel_sum adds once per channel onto zero, a fixed order already
+}
+
+extern "C" int cy_channel_sum_ws(const float* dZ, float* out, float* ws, long long ws_floats, long long P, int N, void* stream) {
+  CY_REQUIRE(dZ && out && P > 0 && N > 0, "cy_channel_sum_ws: bad arguments");
+  long long splits, rpb;
+  channel_sum_splits(P, N, &splits, &rpb);
+  CY_REQUIRE(ws && ws_floats >= splits * N, "cy_channel_sum_ws: the workspace holds %lld floats, %lld are needed", ws_floats,
+             splits * N);
+  hipStream_t s = (hipStream_t)stream;
+  const int nb = (N + 63) / 64;
+  channel_sum_kernel<<<dim3(nb, (unsigned)splits), 256, 0, s>>>(dZ, out, P, N, rpb, ws);
+  CY_LAUNCH_CHECK("cy_channel_sum_ws");
+  channel_sum_finish_kernel<<<nb, 1024, 0, s>>>(ws, out, (int)splits, N);
+  CY_LAUNCH_CHECK("cy_channel_sum_ws(finish)");
   return 0;
 }

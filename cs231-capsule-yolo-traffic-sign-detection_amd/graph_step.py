@@ -11,6 +11,8 @@ step lives in device memory: the batch (static input buffers, filled by `copy_` 
 (step count -> bias corrections, a scheduler's learning rate: `optim.Adam.graph_hyper`, six floats refreshed before the replay).
 With `optim.Adam(max_grad_norm=..., skip_nonfinite=...)` the captured step also holds the gradient-norm reduction and its verdict
 (csrc/gradnorm.hip): a replay clips, or skips a non-finite step, with nothing crossing to the host.
+With `optim.Adam(ema_decay=...)` the captured Adam launch also moves the parameters' averages; 1 - d_t is one of the refreshed scalars
+(eight then), so ema_warmup's schedule reaches every replay.
 Single process only: the data-parallel gradient all-reduce stays on the eager path.
 """
 import gc
@@ -35,9 +37,10 @@ class GraphedStep(object):
         dev = self.static[0].device
         # the scalars travel through a ring of pinned buffers (a buffer is rewritten only after the copy that read it has run: the
         # host may be several replays ahead of the device)
-        self._ring = [dict((id(g), torch.empty(6, dtype=torch.float32).pin_memory()) for g in optimizer.param_groups) for _ in range(8)]
+        n_hyper = dict((id(g), len(optimizer.step_scalars(g, 1))) for g in optimizer.param_groups)       # 6, or 8 with an EMA
+        self._ring = [dict((id(g), torch.empty(n_hyper[id(g)], dtype=torch.float32).pin_memory()) for g in optimizer.param_groups) for _ in range(8)]
         self._ring_events, self._ring_pos = [None] * 8, 0
-        self._hyper_dev = dict((id(g), torch.zeros(6, dtype=torch.float32, device=dev)) for g in optimizer.param_groups)
+        self._hyper_dev = dict((id(g), torch.zeros(n_hyper[id(g)], dtype=torch.float32, device=dev)) for g in optimizer.param_groups)
         # eager warm-up steps on a side stream (torch's capture recipe): optimizer state, the zero pool and the kernels' one-time
         # attribute calls (cy_allow_lds) exist before the capture begins.  They must not train: parameters, buffers (BatchNorm running
         # statistics) and optimizer state are put back IN PLACE afterwards (the capture holds their addresses).
@@ -46,6 +49,8 @@ class GraphedStep(object):
                         for g in optimizer.param_groups for p in g['params'] if p in optimizer.state and len(optimizer.state[p]))
         # optim.Adam's clipping verdict and its count of skipped steps (max_grad_norm / skip_nonfinite) are optimizer state too
         snap_clip = optimizer._clip_buf.clone() if getattr(optimizer, '_clip_buf', None) is not None else None
+        # ... and so are the parameters' moving averages (ema_decay)
+        snap_ema = dict((p, v.detach().clone()) for p, v in getattr(optimizer, 'ema', {}).items())
         s = torch.cuda.Stream(device=dev)
         s.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(s):
@@ -69,9 +74,13 @@ class GraphedStep(object):
                             st[k] = old[k] if old is not None else 0
             if getattr(optimizer, '_clip_buf', None) is not None:
                 optimizer._clip_buf.copy_(snap_clip) if snap_clip is not None else optimizer._clip_reset()
+            # an average that a warm-up step made is what the first real step would have made: a copy of the (restored) parameter
+            for p, v in getattr(optimizer, 'ema', {}).items():
+                v.copy_(snap_ema[p] if p in snap_ema else p)
         ops._bump_param_epoch()
         # frozen kernel arguments of the captured cy_grad_clip_finish, and which Adam kernel the capture holds
         self._clip_cfg = (getattr(optimizer, 'max_grad_norm', None), getattr(optimizer, 'skip_nonfinite', False))
+        self._ema_on = getattr(optimizer, 'ema_decay', None) is not None     # (the decay itself is read from device memory)
         self.graph = torch.cuda.CUDAGraph()
         self._refresh_scalars(advance=False)          # valid numbers during the capture (they are not read until a replay)
         optimizer.graph_hyper = self._hyper_dev
@@ -81,6 +90,10 @@ class GraphedStep(object):
             n = sum(1 for q in g['params'] if q.grad is not None)
             self._tables[id(g)] = (torch.empty((n, 5), dtype=torch.int64).pin_memory(), torch.empty((n, 5), dtype=torch.int64, device=dev))
         optimizer.graph_tables = self._tables
+        if self._ema_on:
+            self._ema_tables = dict((k, (torch.empty(h.shape[0], dtype=torch.int64).pin_memory(),
+                                         torch.empty(h.shape[0], dtype=torch.int64, device=dev))) for k, (h, _) in self._tables.items())
+            optimizer.graph_ema_tables = self._ema_tables
         try:
             optimizer.zero_grad(set_to_none=True)
             gc.collect()      # no dead cycle with pinned buffers or events is finalised inside the capture (serve.SignDetector._capture)
@@ -91,6 +104,8 @@ class GraphedStep(object):
         finally:
             optimizer.graph_hyper = None
             optimizer.graph_tables = None
+            if self._ema_on:
+                optimizer.graph_ema_tables = None
 
     def _eager(self, *batch):
         y_hat, loss = self.forward_loss(self.model, *batch)
@@ -134,6 +149,11 @@ class GraphedStep(object):
         if (getattr(self.opt, 'max_grad_norm', None), getattr(self.opt, 'skip_nonfinite', False)) != self._clip_cfg:
             raise RuntimeError('GraphedStep: the optimizer\'s max_grad_norm / skip_nonfinite were %r / %r when the step was captured and '
                                'are frozen in it; capture a new step to change them' % self._clip_cfg)
+        if (getattr(self.opt, 'ema_decay', None) is not None) != self._ema_on:
+            raise RuntimeError('GraphedStep: the optimizer\'s ema_decay was %s when the step was captured and that is frozen in it; '
+                               'capture a new step to change it' % ('on' if self._ema_on else 'off'))
+        if getattr(self.opt, '_ema_swapped', False):
+            raise RuntimeError('GraphedStep: inside ema_weights() the parameters hold their averages; leave it first')
         for s, b in zip(self.static, batch):
             if s.data_ptr() != b.data_ptr():
                 s.copy_(b, non_blocking=True)

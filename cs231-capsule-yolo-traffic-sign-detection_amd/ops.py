@@ -686,10 +686,25 @@ class _ConvBlockNoBn(torch.autograd.Function):
             call('cy_act_bwd', _ptr(z), _ptr(da), _ptr(dz), float(cfg.slope), z.numel(), st)
         dbias = None
         if ctx.has_bias:
-            dbias = _empty((N,), z)
-            call('cy_channel_sum', _ptr(dz), _ptr(dbias), z.numel() // N, N, st)
+            dbias = channel_sum(dz, N, st)
         dW = conv_wgrad(x, dz, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, cfg.name, ctx.in_affine, plan)
         return _input_grad(ctx, dz, x, weight, plan, st), dW, dbias, None, None
+
+
+def channel_sum(dz, N, st=None):
+    """out[n] = sum over the rows of dz [P, N] (the bias gradient of a convolution without BatchNorm) in a fixed order: with more than one
+    row split through cy_channel_sum_ws and its partials, so that the same dz gives the same bits in every run (cy_channel_sum adds its
+    splits with float atomics); with one split cy_channel_sum is a fixed order already."""
+    st = _stream() if st is None else st
+    P = dz.numel() // N
+    out = _empty((N,), dz)
+    need = query('cy_channel_sum_ws_floats', P, N)
+    if need:
+        ws = _empty((need,), dz)
+        call('cy_channel_sum_ws', _ptr(dz), _ptr(out), _ptr(ws), need, P, N, st)
+    else:
+        call('cy_channel_sum', _ptr(dz), _ptr(out), P, N, st)
+    return out
 
 
 class _Conv1TrainBlock(torch.autograd.Function):

@@ -9,7 +9,20 @@ Optional, both decided on the device without a host synchronisation (csrc/gradno
                        parameter, exp_avg or exp_avg_sq, and a device counter goes up by one.  The host does not learn of the skip
                        (that would be a synchronisation): state['step'], hence the bias corrections of later steps, advance as in
                        any other step.
-With both off, step() issues exactly the launches it issues without them and none of their device state exists."""
+With both off, step() issues exactly the launches it issues without them and none of their device state exists.
+
+Optional, kept inside the same Adam launch (the _ema kernels of csrc/adam.hip):
+  ema_decay=D          an exponential moving average of every parameter the optimizer updates: ema = d_t * ema + (1 - d_t) * p after
+                       each update of p, d_t = D, or with ema_warmup=True d_t = min(D, (1 + t) / (10 + t)) with t the parameter's own
+                       step count.  opt.ema[p] starts as a copy of p before p's first step and moves exactly in the steps that update
+                       p: not in a step in which p has no gradient, not in a step skip_nonfinite skips.  `with opt.ema_weights():`
+                       exchanges every parameter with its average (pointers, no copy) for an evaluation; opt.ema_state_dict(model) /
+                       opt.load_ema_state_dict(model, sd) are keyed by the model's parameter names.  opt.ema is an attribute:
+                       state_dict() stays torch.optim.Adam's.  Deliberately left out: buffers (BatchNorm running statistics are
+                       running averages already: both sets of weights use the live ones) and parameters the optimizer never updates
+                       (frozen ones contribute their own values wherever the averaged weights are used).
+With ema_decay=None step() issues exactly the launches it issues today and no EMA tensor or table exists."""
+import contextlib
 import ctypes as C
 import math
 import numbers
@@ -24,22 +37,34 @@ _CHUNK = 16384
 
 
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False, ema_decay=None,
+                 ema_warmup=False):
         if max_grad_norm is not None:
             if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, numbers.Real) or \
                     not math.isfinite(max_grad_norm) or not max_grad_norm > 0:
                 raise ValueError('capsyolo_amd.optim.Adam: max_grad_norm must be a positive finite number or None, got %r' % (max_grad_norm,))
+        if ema_decay is not None:
+            if isinstance(ema_decay, bool) or not isinstance(ema_decay, numbers.Real) or not math.isfinite(ema_decay) or \
+                    not 0 < ema_decay < 1:
+                raise ValueError('capsyolo_amd.optim.Adam: ema_decay must be a number in (0, 1) or None, got %r' % (ema_decay,))
+        elif ema_warmup:
+            raise ValueError('capsyolo_amd.optim.Adam: ema_warmup shapes the schedule of ema_decay: give ema_decay')
         # weight_decay and amsgrad are in the group only so that a checkpoint of this optimizer loads into torch.optim.Adam, which
         # reads them from the loaded group; step() refuses any value but torch's default (a checkpoint of torch's may carry one)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False))
         self._plan_key, self._plan = None, None
         self.graph_tables = None     # ... and per group (pinned host, device) pointer tables [n parameters with a gradient][5]
-        self.graph_hyper = None      # graph_step.GraphedStep: per group a device tensor of the six step scalars (cy_adam_multi_dev)
+        self.graph_hyper = None      # graph_step.GraphedStep: per group a device tensor of step_scalars()'s six floats, eight with an EMA (cy_adam_multi_dev*)
         # attributes, not param_groups entries: state_dict() is that of torch.optim.Adam with or without them
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
         self._clip_buf = None        # device int64[3], made by the first step that needs it: {record as 4 floats, skipped}
         self._partial = None         # device float64[chunks of all parameters]: the sums of squares of cy_grad_sumsq_multi
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema = {}                # parameter -> its moving average (made by the parameter's first step; empty without ema_decay)
+        self.graph_ema_tables = None  # graph_step.GraphedStep: per group (pinned host, device) int64[n]: the EMA pointers of graph_tables' rows
+        self._ema_swapped = False    # inside ema_weights(): p.data and ema[p] have changed places
 
     @property
     def clip_record(self):
@@ -68,9 +93,81 @@ class Adam(torch.optim.Optimizer):
         return {'norm': float(rec[0]), 'coef': float(rec[1]), 'skipped': int(host[2])}
 
     def step_scalars(self, group, t):
-        """{lr, beta1, beta2, eps, 1 - beta1^t, 1 - beta2^t}: the scalars of step t of a group."""
+        """{lr, beta1, beta2, eps, 1 - beta1^t, 1 - beta2^t}: the scalars of step t of a group; with ema_decay two more,
+        {1 - d_t, 0}: the difference is formed here in double and rounded to fp32 once, on its way to the kernel."""
         b1, b2 = group['betas']
-        return [float(group['lr']), float(b1), float(b2), float(group['eps']), float(1.0 - b1 ** t), float(1.0 - b2 ** t)]
+        out = [float(group['lr']), float(b1), float(b2), float(group['eps']), float(1.0 - b1 ** t), float(1.0 - b2 ** t)]
+        if self.ema_decay is not None:
+            out += [1.0 - self.ema_decay_at(t), 0.0]
+        return out
+
+    def ema_decay_at(self, t):
+        """d_t of a parameter's step t (1-based): ema_decay, or with ema_warmup min(ema_decay, (1 + t) / (10 + t))."""
+        if self.ema_decay is None:
+            raise RuntimeError('capsyolo_amd.optim.Adam.ema_decay_at: ema_decay is off')
+        return min(self.ema_decay, (1.0 + t) / (10.0 + t)) if self.ema_warmup else self.ema_decay
+
+    def _model_params(self, model):
+        mine = set(p for g in self.param_groups for p in g['params'])
+        return [(name, p, p in mine) for name, p in model.named_parameters()]
+
+    def ema_state_dict(self, model):
+        """{parameter name of `model`: averaged values}: the average of every parameter that has one, the parameter's own values for the
+        others (frozen ones, ones that have not had a step).  Copies; no buffers (they are not averaged)."""
+        if self.ema_decay is None:
+            raise RuntimeError('capsyolo_amd.optim.Adam.ema_state_dict: ema_decay is off')
+        out = {}
+        for name, p, _ in self._model_params(model):
+            # (inside ema_weights() the two have changed places)
+            avg = p if (p not in self.ema or self._ema_swapped) else self.ema[p]
+            out[name] = avg.detach().clone()
+        return out
+
+    def load_ema_state_dict(self, model, sd):
+        """The inverse: the entries of the parameters this optimizer updates become their averages (copied into the tensor an average
+        already has: a captured step holds its address); entries of other parameters are ignored."""
+        if self.ema_decay is None:
+            raise RuntimeError('capsyolo_amd.optim.Adam.load_ema_state_dict: ema_decay is off')
+        if self._ema_swapped:
+            raise RuntimeError('capsyolo_amd.optim.Adam.load_ema_state_dict: not inside ema_weights()')
+        todo = [(name, p) for name, p, mine in self._model_params(model) if mine and p.requires_grad]
+        for name, p in todo:
+            if name not in sd or tuple(sd[name].shape) != tuple(p.shape):
+                raise KeyError('capsyolo_amd.optim.Adam.load_ema_state_dict: no entry %r of shape %s' % (name, tuple(p.shape)))
+        with torch.no_grad():
+            for name, p in todo:
+                if p in self.ema:
+                    self.ema[p].copy_(sd[name])
+                else:
+                    self.ema[p] = sd[name].detach().to(device=p.device, dtype=p.dtype, copy=True).contiguous()
+        self._plan_key = None
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with opt.ema_weights():` every parameter that has an average holds it (p.data and opt.ema[p] change places: two pointers,
+        no copy); on exit the parameters are the tensors, with the bits, they were.  For an evaluation or a state_dict() of the averaged
+        model; step() is refused inside.  The eval-mode fold caches (ops.fold_eval_bn) are keyed on ops' parameter epoch, which is moved
+        on entry and on exit."""
+        if self.ema_decay is None:
+            raise RuntimeError('capsyolo_amd.optim.Adam.ema_weights: ema_decay is off')
+        if self._ema_swapped:
+            raise RuntimeError('capsyolo_amd.optim.Adam.ema_weights: already inside')
+        if self.graph_hyper is not None or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
+            raise RuntimeError('capsyolo_amd.optim.Adam.ema_weights: a captured step is being recorded (it holds the parameters\' addresses)')
+        self._swap_ema()
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+
+    def _swap_ema(self):
+        for p, avg in list(self.ema.items()):
+            live = p.data
+            p.data = avg
+            self.ema[p] = live
+        self._ema_swapped = not self._ema_swapped
+        self._plan_key = None
+        _ops._bump_param_epoch()
 
     def _build_plan(self, entries, device):
         """Pointer table + block map on the device.  The block map depends on the sizes only and is uploaded once; the
@@ -87,6 +184,11 @@ class Adam(torch.optim.Optimizer):
             self._ring = [torch.empty((len(entries), 5), dtype=torch.int64).pin_memory() for _ in range(4)]
             self._ring_events = [None] * 4
             self._ring_pos = 0
+            self._ema_table_dev, self._ema_ring = None, None
+        if self.ema_decay is not None and self._ema_table_dev is None:
+            # the averages' pointers: a second table (the layout of the first is cy_adam_multi's and stays) with a ring of its own
+            self._ema_table_dev = torch.empty(len(entries), dtype=torch.int64, device=device)
+            self._ema_ring = [torch.empty(len(entries), dtype=torch.int64).pin_memory() for _ in range(4)]
         k = self._ring_pos
         self._ring_pos = (k + 1) % 4
         if self._ring_events[k] is not None:
@@ -95,6 +197,10 @@ class Adam(torch.optim.Optimizer):
         host.numpy()[...] = np.asarray([(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
                                         for p, g, m, v in entries], dtype=np.int64)
         self._table_dev.copy_(host, non_blocking=True)
+        if self.ema_decay is not None:
+            host = self._ema_ring[k]
+            host.numpy()[...] = np.asarray([self.ema[p].data_ptr() for p, _, _, _ in entries], dtype=np.int64)
+            self._ema_table_dev.copy_(host, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(device))
         self._ring_events[k] = ev
@@ -117,12 +223,24 @@ class Adam(torch.optim.Optimizer):
             host.numpy()[...] = np.asarray([(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
                                             for p, g, m, v in entries], dtype=np.int64)
             table.copy_(host, non_blocking=True)
+            if self.ema_decay is not None:
+                if self.graph_ema_tables is None or tuple(self.graph_ema_tables[id(group)][0].shape) != (len(entries),):
+                    raise RuntimeError('capsyolo_amd.optim.Adam: the captured step has no table for the %d EMA pointers' % len(entries))
+                host, table_ema = self.graph_ema_tables[id(group)]
+                host.numpy()[...] = np.asarray([self.ema[p].data_ptr() for p, _, _, _ in entries], dtype=np.int64)
+                table_ema.copy_(host, non_blocking=True)
             nblocks = sum((p.numel() + _CHUNK - 1) // _CHUNK for p, _, _, _ in entries)
             return (table, self._bm, nblocks)
         key = tuple(x.data_ptr() for e in entries for x in e)
+        if self.ema_decay is not None:
+            key += tuple(self.ema[e[0]].data_ptr() for e in entries)
         if key != self._plan_key:
             self._plan, self._plan_key = self._build_plan(entries, entries[0][0].device), key
         return self._plan
+
+    def _ema_table(self, group):
+        """The device table of EMA pointers that belongs to the table _tables(group, ...) has just uploaded."""
+        return self.graph_ema_tables[id(group)][1] if self.graph_hyper is not None else self._ema_table_dev
 
     def _grad_verdict(self, launches, stream):
         """The sums of squares of every launch's gradients into consecutive slices of one partial buffer, then ONE
@@ -153,6 +271,9 @@ class Adam(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        if self._ema_swapped:
+            raise RuntimeError('capsyolo_amd.optim.Adam.step: inside ema_weights() the parameters hold their averages; leave it first')
+        ema = self.ema_decay is not None
         launches = []
         for group in self.param_groups:
             if group.get('weight_decay', 0) != 0 or group.get('amsgrad', False) or group.get('maximize', False):
@@ -169,6 +290,8 @@ class Adam(torch.optim.Optimizer):
                     st['exp_avg'] = torch.zeros_like(p)
                     st['exp_avg_sq'] = torch.zeros_like(p)
                 st['step'] = int(st['step']) + 1
+                if ema and p not in self.ema:
+                    self.ema[p] = p.detach().clone()      # the parameter before its first step
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 by_step.setdefault(st['step'], []).append((p, g, st['exp_avg'], st['exp_avg_sq']))
             if self.graph_hyper is not None and len(by_step) > 1:
@@ -184,20 +307,21 @@ class Adam(torch.optim.Optimizer):
         record = C.c_void_p(self.clip_record.data_ptr()) if clip else None
         for k, (group, t, entries) in enumerate(launches):
             table, bm, nblocks = tables[k] if tables is not None else self._tables(group, entries)
+            head = [C.c_void_p(table.data_ptr())]
+            if ema:
+                head.append(C.c_void_p(self._ema_table(group).data_ptr()))
+            head += [C.c_void_p(bm.data_ptr()), nblocks, _CHUNK]
+            name = 'cy_adam_multi' + ('_dev' if self.graph_hyper is not None else '') + ('_clip' if clip else '') + ('_ema' if ema else '')
             if self.graph_hyper is not None:
-                hyper = C.c_void_p(self.graph_hyper[id(group)].data_ptr())
-                if clip:
-                    call('cy_adam_multi_dev_clip', C.c_void_p(table.data_ptr()), C.c_void_p(bm.data_ptr()), nblocks, _CHUNK, hyper,
-                         record, stream)
-                else:
-                    call('cy_adam_multi_dev', C.c_void_p(table.data_ptr()), C.c_void_p(bm.data_ptr()), nblocks, _CHUNK, hyper, stream)
+                hyper = self.graph_hyper[id(group)]
+                if hyper.numel() != (8 if ema else 6):
+                    raise RuntimeError('capsyolo_amd.optim.Adam: the captured step\'s scalars are %d floats, this step reads %d'
+                                       % (hyper.numel(), 8 if ema else 6))
+                tail = [C.c_void_p(hyper.data_ptr())]
             else:
-                b1, b2 = group['betas']
-                scalars = (float(group['lr']), float(b1), float(b2), float(group['eps']), float(1.0 - b1 ** t), float(1.0 - b2 ** t))
-                if clip:
-                    call('cy_adam_multi_clip', C.c_void_p(table.data_ptr()), C.c_void_p(bm.data_ptr()), nblocks, _CHUNK, *scalars,
-                         record, stream)
-                else:
-                    call('cy_adam_multi', C.c_void_p(table.data_ptr()), C.c_void_p(bm.data_ptr()), nblocks, _CHUNK, *scalars, stream)
+                scalars = self.step_scalars(group, t)
+                assert len(scalars) == (8 if ema else 6), scalars       # {six of Adam} + {1 - d_t, 0}: what the entry point's argument list takes
+                tail = scalars[:6] + ([scalars[6]] if ema else [])
+            call(name, *(head + tail + ([record] if clip else []) + [stream]))
             _ops._bump_param_epoch()          # parameters changed through raw pointers: eval-mode fold caches are stale
         return loss

@@ -37,14 +37,41 @@ def save_checkpoint(state, is_best, checkpoint):
         shutil.copyfile(filepath, os.path.join(checkpoint, 'best.pth.tar'))
 
 
+class NoEmaInCheckpoint(ValueError):
+    """--use_ema on a checkpoint that was written without --ema."""
+
+
 def load_checkpoint(checkpoint, model, params=None, optimizer=None):
-    """utils.py:52-60 (the reference raises a str on a missing file; a real exception here)."""
+    """utils.py:52-60 (the reference raises a str on a missing file; a real exception here).
+    An 'ema_state_dict' entry (main.py --ema: the optimizer's moving averages under the model's parameter names) goes back into an
+    optimizer that keeps averages; a checkpoint without the entry loads as it always did.  params.use_ema (main.py --use_ema, the
+    modes that only run the model): the averaged values become the model's parameters; True needs the entry (NoEmaInCheckpoint
+    otherwise), 'if_present' takes it when it is there.  Buffers are the checkpoint's 'state_dict' ones either way."""
     if not os.path.exists(checkpoint):
         raise FileNotFoundError("File doesn't exist {}".format(checkpoint))
     ckpt = torch.load(checkpoint, map_location='cpu', weights_only=False)
     model.load_state_dict(ckpt['state_dict'])
     if optimizer and 'optim_dict' in ckpt:
         optimizer.load_state_dict(ckpt['optim_dict'])
+    if optimizer and getattr(optimizer, 'ema_decay', None) is not None and 'ema_state_dict' in ckpt:
+        optimizer.load_ema_state_dict(model, ckpt['ema_state_dict'])
+    use_ema = getattr(params, 'use_ema', False) if params is not None else False
+    if use_ema:
+        if 'ema_state_dict' in ckpt:
+            from . import ops
+            ema = ckpt['ema_state_dict']
+            bad = [name for name, p in model.named_parameters() if name not in ema or tuple(ema[name].shape) != tuple(p.shape)]
+            if bad:
+                raise ValueError("--use_ema: the 'ema_state_dict' of {} does not fit this model: no entry of the parameter's shape for {}"
+                                 .format(checkpoint, ', '.join(bad[:5]) + (' ...' if len(bad) > 5 else '')))
+            with torch.no_grad():
+                for name, p in model.named_parameters():
+                    p.copy_(ema[name])
+            ops._bump_param_epoch()
+            print("Using the averaged (EMA) parameters of {}".format(checkpoint))
+        elif use_ema != 'if_present':
+            raise NoEmaInCheckpoint("--use_ema: {} has no 'ema_state_dict' entry: it was written by a training run without --ema"
+                                    .format(checkpoint))
     return ckpt
 
 

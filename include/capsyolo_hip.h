@@ -279,8 +279,15 @@ int cy_conv4x4s2_winograd_dgrad(const float* dZ, const float* U, float* dX, cons
                                 const float* bn_shift, const float* bn_mean, const float* bn_invstd, float bn_slope,
                                 double* bn_red, int B, int H, int W, int Cin, int Cout, void* stream);
 
-/* per-channel sum over pixels: out[N] = sum_p dZ[p][n]  (bias gradient of convs without BatchNorm) */
+/* per-channel sum over pixels: out[N] = sum_p dZ[p][n]  (bias gradient of convs without BatchNorm).  The row splits are added with
+ * float atomics: with more than one split two runs may differ in the last bits. */
 int cy_channel_sum(const float* dZ, float* out, long long P, int N, void* stream);
+/* The same sum with the same row splits in a FIXED order: every split writes its sum to ws[split][n] and a second launch adds the
+ * splits (16 interleaved running sums per channel, then a fixed tree).  No memset and no atomics: the same dZ gives the same bits in
+ * every run, which a training step that is to repeat to the bit needs.  ws: cy_channel_sum_ws_floats(P, N)
+ * floats, not initialised; 0 means one split, where cy_channel_sum is a fixed order already. */
+long long cy_channel_sum_ws_floats(long long P, int N);
+int cy_channel_sum_ws(const float* dZ, float* out, float* ws, long long ws_floats, long long P, int N, void* stream);
 
 /* ------------------------------------------------------------------ bf16 convolution path (params.json "precision": "bf16")
  * The backbone's 3x3/s1 and 4x4/s2 layers (models.py:350-363) on v_mfma_f32_32x32x16_bf16 with fp32 accumulation:
@@ -811,6 +818,26 @@ int cy_adam_multi_clip(const void* table, const void* blockmap, int n_blocks, in
                        float eps, float bias_corr1, float bias_corr2, const float* record, void* stream);
 int cy_adam_multi_dev_clip(const void* table, const void* blockmap, int n_blocks, int chunk, const float* hyper,
                            const float* record, void* stream);
+
+/* An exponential moving average (EMA) of the parameters, kept inside the Adam launch (optim.Adam(ema_decay=...)).  The four steps
+ * above, each with one more pass per element after the parameter has its new value p:
+ *   ema += one_minus_decay * (p - ema)            (= decay * ema + (1 - decay) * p)
+ * ema_table: device array of n_tensors float*, ema_table[k] the average of the parameter of table[k] (same numel, fp32, no overlap
+ * with any tensor of table); table and blockmap are those of cy_adam_multi, whose record layout does not change.
+ * one_minus_decay = 1 - decay, formed in double by the caller and rounded ONCE to fp32 (in (0, 1]); the kernels never form
+ * 1.f - decay.  The _dev variants read it from hyper[6]: with an EMA hyper holds 8 floats {lr, beta1, beta2, eps, bias_corr1,
+ * bias_corr2, one_minus_decay, 0}, so a captured step can follow a decay schedule.
+ * Parameters, exp_avg and exp_avg_sq get the bits of the step without the average.  In the _clip variants record[2] == 0 returns
+ * before anything is read or written: a skipped step changes no bit of an average.  36 bytes per element against 28. */
+int cy_adam_multi_ema(const void* table, const void* ema_table, const void* blockmap, int n_blocks, int chunk, float lr, float beta1,
+                      float beta2, float eps, float bias_corr1, float bias_corr2, float one_minus_decay, void* stream);
+int cy_adam_multi_dev_ema(const void* table, const void* ema_table, const void* blockmap, int n_blocks, int chunk,
+                          const float* hyper /* [8] */, void* stream);
+int cy_adam_multi_clip_ema(const void* table, const void* ema_table, const void* blockmap, int n_blocks, int chunk, float lr,
+                           float beta1, float beta2, float eps, float bias_corr1, float bias_corr2, float one_minus_decay,
+                           const float* record, void* stream);
+int cy_adam_multi_dev_clip_ema(const void* table, const void* ema_table, const void* blockmap, int n_blocks, int chunk,
+                               const float* hyper /* [8] */, const float* record, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,15 @@ keys, same registry shape ``name -> (ModelCls, loss_fn, predict_fn, metric)`` (m
   --fix_ckpt_dir    save checkpoints into model_dir, where --restore looks for them
   --clip_norm X, --skip_nonfinite   global gradient-norm clipping and a guard against non-finite steps, both decided on the device
                     inside capsyolo_amd.optim.Adam (params.json keys clip_norm, skip_nonfinite)
+  --ema D [--ema_warmup]   an exponential moving average of the parameters with decay D in (0, 1), kept inside capsyolo_amd.optim.Adam's
+                    launch (params.json keys ema_decay, ema_warmup): every evaluation of the training loop, hence
+                    eval metric, `best` and best.pth.tar, judges the averaged weights, and the checkpoints gain 'ema_state_dict' (the
+                    averages under the model's parameter names) next to 'state_dict' and 'optim_dict', which stay what they were.
+                    --ema_warmup: d_t = min(D, (1 + t) / (10 + t)).  Buffers (BatchNorm running statistics) are not averaged.
+                    best.pth.tar's 'state_dict' holds the LIVE weights of the epoch whose AVERAGED weights scored best: `--restore best`
+                    without --use_ema runs weights that were not the ones judged.
+  --use_ema         --mode predict | detect | serve | interpret: run on the checkpoint's 'ema_state_dict' (detector, and the --combine
+                    classifier when its checkpoint has one); a checkpoint written without --ema is refused
   params.json keys ``n_iter`` (routing iterations, default 3), ``sync_bn`` (data parallel only)
   --model darkcapsule2 | darkcapsule3   the reference's unwired variants with their losses (models.py:271-337, 403-463)
 ``--mode predict --model darknet_d|darknet_r --combine cnn|capsule --restore last|best`` runs the two-stage chain
@@ -140,6 +149,15 @@ parser.add_argument('--clip_norm', type=float, default=None, metavar='X',
 parser.add_argument('--skip_nonfinite', action='store_true',
                     help='a step with an inf or NaN gradient leaves parameters and optimizer state as they are, decided on the device '
                          '(params.json key skip_nonfinite); needs the project\'s Adam')
+parser.add_argument('--ema', type=float, default=None, metavar='D',
+                    help='keep an exponential moving average of the parameters with decay D in (0, 1) inside the project\'s Adam launch '
+                         '(params.json key ema_decay); evaluation, best and the checkpoint\'s ema_state_dict use the averaged weights. '
+                         'best.pth.tar is then chosen by the averaged weights\' metric while its state_dict holds the live ones: restore it '
+                         'with --use_ema to run what was judged')
+parser.add_argument('--ema_warmup', action='store_true',
+                    help='--ema: decay min(D, (1 + t) / (10 + t)) at a parameter\'s step t (params.json key ema_warmup)')
+parser.add_argument('--use_ema', action='store_true',
+                    help='--mode predict | detect | serve | interpret: load the checkpoint\'s ema_state_dict into the model\'s parameters')
 parser.add_argument('--fix_ckpt_dir', action='store_true',
                     help='save checkpoints into model_dir (where --restore reads) instead of model_dir + str(train_frac)')
 
@@ -346,19 +364,27 @@ def train_and_evaluate(model, optimizer, loss_fn, metric, params, data, model_di
     bucket = dp.GradBucket(model)
     losses_tr, losses_ev, metrics_tr, metrics_ev = [], [], [], []
     best_metric_ev, best_loss_ev = float('-inf'), float('inf')
+    ema = isinstance(optimizer, Adam) and optimizer.ema_decay is not None
     for epoch in range(params.n_epochs):
         if_eval = (epoch + 1) % params.eval_every == 0                                   # main.py:168
         loss_tr, metric_tr = train(x_tr, y_tr, model, optimizer, loss_fn, metric, params, bucket, if_eval)
-        loss_ev, metric_ev = evaluate(x_ev, y_ev, model, loss_fn, metric, params, if_eval)
+        if ema:
+            # the averaged weights are what is judged: eval loss and metric, is_best and with it best.pth.tar (the BatchNorm running
+            # statistics are the live ones: buffers are not averaged)
+            with optimizer.ema_weights():
+                loss_ev, metric_ev = evaluate(x_ev, y_ev, model, loss_fn, metric, params, if_eval)
+        else:
+            loss_ev, metric_ev = evaluate(x_ev, y_ev, model, loss_fn, metric, params, if_eval)
         loss_tr, loss_ev = _mean_over_ranks(loss_tr, params), _mean_over_ranks(loss_ev, params)
         scheduler.step(loss_tr)                                                          # plateau on the TRAIN loss (main.py:174)
         is_best = metric_ev > best_metric_ev
         best_metric_ev = max(best_metric_ev, metric_ev)
         best_loss_ev = min(best_loss_ev, loss_ev)
         if params.rank == 0:
-            utils.save_checkpoint({'epoch': epoch + 1, 'state_dict': model.state_dict(),
-                                   'optim_dict': optimizer.state_dict()}, is_best=is_best,
-                                  checkpoint=checkpoint_dir(model_dir, params))
+            state = {'epoch': epoch + 1, 'state_dict': model.state_dict(), 'optim_dict': optimizer.state_dict()}
+            if ema:
+                state['ema_state_dict'] = optimizer.ema_state_dict(model)
+            utils.save_checkpoint(state, is_best=is_best, checkpoint=checkpoint_dir(model_dir, params))
             if if_eval:
                 tail = ''
                 if isinstance(optimizer, Adam) and (optimizer.max_grad_norm is not None or optimizer.skip_nonfinite):
@@ -404,6 +430,12 @@ def load_params(model_dir, args):
     elif not hasattr(params, 'clip_norm'):
         params.clip_norm = None
     params.skip_nonfinite = bool(getattr(args, 'skip_nonfinite', False) or getattr(params, 'skip_nonfinite', False))
+    if getattr(args, 'ema', None) is not None:                                           # the command line wins
+        params.ema_decay = args.ema
+    elif not hasattr(params, 'ema_decay'):
+        params.ema_decay = None
+    params.ema_warmup = bool(getattr(args, 'ema_warmup', False) or getattr(params, 'ema_warmup', False))
+    params.use_ema = bool(getattr(args, 'use_ema', False))
     if args.model == 'cnn' and getattr(args, 'cnn_kernels', None) is not None:
         params.cnn_kernels = args.cnn_kernels
     return params
@@ -530,6 +562,8 @@ def _combined_classifier(args, model_dir):
         os.path.join(os.path.dirname(os.path.abspath(model_dir)), args.combine)
     class_args = argparse.Namespace(**dict(vars(args), model=args.combine))
     class_params = load_params(class_model_dir, class_args)
+    if class_params.use_ema:
+        class_params.use_ema = 'if_present'         # the classifier's averages are used when its checkpoint has them
     class_model = model_loss_predict[args.combine][0](class_params).to(device=class_params.device)
     return class_model, class_model_dir, class_params
 
@@ -801,6 +835,17 @@ def main(argv=None):
                          'torch.optim.Adam; use --cnn_kernels hip or another model')
     if params.clip_norm is not None and not (np.isfinite(params.clip_norm) and params.clip_norm > 0):
         raise SystemExit('--clip_norm must be a positive finite number, got %r' % (params.clip_norm,))
+    if params.ema_decay is not None:
+        if isinstance(params.ema_decay, bool) or not isinstance(params.ema_decay, (int, float)) or \
+                not (np.isfinite(params.ema_decay) and 0 < params.ema_decay < 1):
+            raise SystemExit('--ema must be a decay in (0, 1), got %r' % (params.ema_decay,))
+        if args.model == 'cnn' and not _cnn_on_hip(params):
+            raise SystemExit('--ema needs the project\'s Adam (capsyolo_amd.optim.Adam): the plain-torch cnn baseline trains with '
+                             'torch.optim.Adam; use --cnn_kernels hip or another model')
+    elif params.ema_warmup:
+        raise SystemExit('--ema_warmup shapes the schedule of --ema: give --ema D')
+    if params.use_ema and args.mode not in ('predict', 'detect', 'serve', 'interpret'):
+        raise SystemExit('--use_ema runs a restored model on its averaged weights: --mode predict | detect | serve | interpret')
     if args.nms_class_aware and int(getattr(params, 'n_classes', 0)) == 0:
         raise SystemExit('--nms_class_aware needs a detector with class scores (n_classes > 0 in %s/params.json)' % model_dir)
     params.rank, params.world, local_rank = dp.init_from_env()
@@ -832,7 +877,8 @@ def main(argv=None):
     trainable = [p for p in model.parameters() if p.requires_grad]
     torch_cnn = args.model == 'cnn' and not _cnn_on_hip(params)
     optimizer = torch.optim.Adam(trainable, lr=args.lr) if torch_cnn else \
-        Adam(trainable, lr=args.lr, max_grad_norm=params.clip_norm, skip_nonfinite=params.skip_nonfinite)
+        Adam(trainable, lr=args.lr, max_grad_norm=params.clip_norm, skip_nonfinite=params.skip_nonfinite,
+             ema_decay=params.ema_decay, ema_warmup=params.ema_warmup)
 
     if args.mode in ('train', 'overfit'):
         if args.augment:
@@ -848,14 +894,12 @@ def main(argv=None):
         return train_and_evaluate(model, optimizer, loss_fn, metric, params, data, model_dir, restore_file=args.restore)
     if args.augment:
         raise SystemExit('--augment belongs to --mode train')
-    if args.mode == 'predict':
-        return predict(args, model, model_dir, data_dir, params)
-    if args.mode == 'detect':
-        return detect(args, model, model_dir, data_dir, params)
-    if args.mode == 'serve':
-        return serve(args, model, model_dir, data_dir, params)
-    if args.mode == 'interpret':
-        return interpret(args, model, model_dir, data_dir, params)
+    modes = {'predict': predict, 'detect': detect, 'serve': serve, 'interpret': interpret}
+    if args.mode in modes:
+        try:
+            return modes[args.mode](args, model, model_dir, data_dir, params)
+        except utils.NoEmaInCheckpoint as e:
+            raise SystemExit(str(e))
 
 
 if __name__ == '__main__':
