@@ -7,4 +7,4 @@ through the C-ABI of ``include/capsyolo_hip.h``.  There is no CPU fallback.
 """
 from . import _lib  # noqa: F401
 
-__all__ = ['config', 'models', 'loss_fns', 'predict_fns', 'utils', 'optim', 'dp', 'synth', 'ops']
+__all__ = ['config', 'models', 'loss_fns', 'predict_fns', 'utils', 'optim', 'dp', 'synth', 'ops', 'attack']

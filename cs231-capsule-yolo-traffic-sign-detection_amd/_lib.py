@@ -170,6 +170,9 @@ _SIGS = {
     'cy_linear_dgrad': [_P, _P, _P, _P, _I, _I, _I, _P],
     'cy_linear_wgrad': [_P, _P, _P, _P, _I, _I, _I, _P],
     'cy_softmax_xent': [_P, _P, _P, _P, _I, _I, _P],
+    'cy_conv_image_grad': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P],
+    'cy_attack_step': [_P, _P, _P, _F, _F, _F, _F, _L, _P],
+    'cy_grad_saliency_u8': [_P, _P, _I, _I, _I, _P],
 }
 _RET = {
     'capsyolo_last_error': (C.c_char_p, []),
@@ -214,6 +217,7 @@ _RET = {
     'cy_linear_fwd_shares': (_I, [_I, _I, _I]),
     'cy_linear_fwd_slice': (_I, [_I, _I, _I]),
     'cy_linear_fwd_ws_floats': (_L, [_I, _I, _I]),
+    'cy_conv_image_grad_ok': (_I, [_I, _I, _I, _I, _I, _I]),
 }
 EXPORTS = sorted(list(_SIGS) + list(_RET))
 ABI_VERSION = 5     # what the signatures above were written against (include/capsyolo_hip.h, csrc/error.cpp)

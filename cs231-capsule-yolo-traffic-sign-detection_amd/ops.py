@@ -223,6 +223,56 @@ def conv_plan(in_shape, cout, k, stride, pad, nchw=False, relu=False, lrelu=Fals
                     bool(CONV1_SIGNMASK and conv1_moments and conv1_onepass))
 
 
+ImageGradPlan = collections.namedtuple('ImageGradPlan', [
+    'ok',                      # cy_conv_image_grad takes this first layer (Cin 3, stride 1, k odd up to 9, pad 0..k/2, Cout up to 1024)
+    'family',                  # its timer.range prefix
+    'tile',                    # (rows, columns) of image pixels per block
+    'blocks',                  # blocks of the launch: B * ceil(H / 16) * ceil(W / 32)
+    'chunks'])                 # passes over LDS: ceil(Cout / 8) chunks of dz channels
+IMAGE_GRAD_TILE, IMAGE_GRAD_CK = (16, 32), 8      # IG_TY x IG_TX, IG_CK of csrc/image_grad.hip
+
+
+def image_grad_plan(in_shape_nchw, cout, k, stride, pad):
+    """Whether the gradient with respect to the NCHW image of one first layer is built (csrc/image_grad.hip), and the launch it
+    takes: an ImageGradPlan.  Host arithmetic and the library's own cy_conv_image_grad_ok; conv_plan and ConvPlan know nothing of it
+    (ConvPlan.dgrad stays None for an NCHW input: that field names the NHWC input-gradient kernels)."""
+    B, Cin, Hi, Wi = (int(v) for v in in_shape_nchw)
+    cout, k, stride, pad = int(cout), int(k), int(stride), int(pad)
+    ok = bool(Cin == 3 and stride == 1 and _shape_ok('cy_conv_image_grad_ok', B, Hi, Wi, cout, k, pad))
+    ty, tx = IMAGE_GRAD_TILE
+    return ImageGradPlan(ok, 'conv_image_grad', IMAGE_GRAD_TILE, B * (-(-Hi // ty)) * (-(-Wi // tx)) if ok else 0,
+                         -(-cout // IMAGE_GRAD_CK) if ok else 0)
+
+
+def conv_image_grad(dy, weight, in_shape, k, pad, act=None, slope=1.0, scale=None, tag='conv'):
+    """dx[B,3,H,W] (NCHW) of a stride-1 first layer from dy[B,Ho,Wo,Cout] (NHWC) and weight[Cout,3,k,k].  act: the block's own
+    output, whose sign selects 1 or `slope` (in [0, 1]) as the activation's derivative; scale[Cout]: the eval-mode BatchNorm scale.
+    Both are applied on the kernel's loads of dy (capsyolo_hip.h: cy_conv_image_grad); without them dy is the gradient dz itself."""
+    dy, weight = _f32(dy, 'grad'), _f32(weight, 'conv weight')
+    B, Cin, Hi, Wi = (int(v) for v in in_shape)
+    Cout = weight.shape[0]
+    if tuple(weight.shape) != (Cout, Cin, k, k) or tuple(dy.shape) != (B, Hi + 2 * pad - k + 1, Wi + 2 * pad - k + 1, Cout):
+        raise _lib.HipExtensionError('conv_image_grad: dy %s and weight %s do not belong to a %dx%d / pad %d layer on an image %s'
+                                     % (tuple(dy.shape), tuple(weight.shape), k, k, pad, (B, Cin, Hi, Wi)))
+    if not image_grad_plan((B, Cin, Hi, Wi), Cout, k, 1, pad).ok:
+        raise _lib.HipExtensionError('conv_image_grad: no kernel for image %s, Cout=%d, k=%d, pad=%d (built: 3 input channels, stride 1, '
+                                     'k odd in 1..9, pad 0..k//2, Cout 1..1024)' % ((B, Cin, Hi, Wi), Cout, k, pad))
+    if act is not None:
+        act = _f32(act, 'activation')
+        if tuple(act.shape) != tuple(dy.shape) or not 0.0 <= float(slope) <= 1.0:
+            raise _lib.HipExtensionError('conv_image_grad: act %s must have the shape of dy %s and slope %r must lie in [0, 1]'
+                                         % (tuple(act.shape), tuple(dy.shape), slope))
+    if scale is not None:
+        scale = _f32(scale, 'scale')
+        if tuple(scale.shape) != (Cout,):
+            raise _lib.HipExtensionError('conv_image_grad: scale %s must be [%d]' % (tuple(scale.shape), Cout))
+    dx = _empty((B, Cin, Hi, Wi), dy)
+    with timer.range('conv_image_grad/' + tag):
+        call('cy_conv_image_grad', _ptr(dy), _ptr(act), _ptr(scale), _ptr(weight), _ptr(dx), B, Hi, Wi, Cin, Cout, k, pad, float(slope),
+             _stream())
+    return dx
+
+
 BF16_DGRAD_ONE_LAUNCH = True       # bf16 path: the output-parity classes of a strided input gradient in one launch (cy_conv_gemm_bf16_classes)
 FUSE_BN_BWD_REDUCE_BF16 = True     # bf16 path: the producer block's BatchNorm-backward sums out of the consumer's input-gradient epilogue
 FUSE_BN_BWD_APPLY_BF16 = True      # bf16 path: BatchNorm-backward pass 2 inside the weight gradient (cy_conv_wgrad_bf16_bn) where the gradient arrives premasked
@@ -635,9 +685,11 @@ def _input_grad(ctx, dz, x, weight, plan, st):
     if not ctx.needs_input_grad[0]:
         return None
     bf16 = isinstance(plan, ConvPlanBF16)
-    if plan.dgrad is None and not bf16:
-        raise _lib.HipExtensionError('input gradient of an NCHW-input convolution is not implemented')
     cfg, h, fuse = ctx.cfg, ctx.hin, None
+    if plan.dgrad is None and not bf16:
+        if cfg.nchw_in and image_grad_plan(x.shape, weight.shape[0], cfg.k, cfg.stride, cfg.pad).ok:
+            return conv_image_grad(dz, weight, tuple(x.shape), cfg.k, cfg.pad, tag=cfg.name)     # a first layer: the gradient of the image
+        raise _lib.HipExtensionError('input gradient of an NCHW-input convolution is not implemented')
     if plan.dgrad_bn_fuse and h is not None and (tuple(h.z.shape) == tuple(x.shape) if bf16 else h.mean is not None):
         bred = zero_pool.take((STATS_COPIES, x.shape[3], 2), torch.float64, x.device)
         fuse = (h.z if bf16 else x, h.scale, h.shift, h.mean, h.invstd, h.slope, bred)
@@ -681,13 +733,18 @@ class _ConvBlockNoBn(torch.autograd.Function):
         x, weight, z = ctx.saved_tensors
         N = weight.shape[0]
         plan = conv_plan(x.shape, N, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in)
-        if cfg.slope is not None:
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        # a first layer with an activation: the image-gradient kernel takes the activation's derivative from the sign of z on its
+        # loads of da (z and the block's output have one sign for a slope in [0, 1]), so dx needs no dz in memory
+        image = bool(need_x and cfg.nchw_in and cfg.slope is not None and 0.0 <= float(cfg.slope) <= 1.0
+                     and image_grad_plan(x.shape, N, cfg.k, cfg.stride, cfg.pad).ok)
+        if cfg.slope is not None and (need_w or need_b or (need_x and not image)):
             dz = torch.empty_like(z)
             call('cy_act_bwd', _ptr(z), _ptr(da), _ptr(dz), float(cfg.slope), z.numel(), st)
-        dbias = None
-        if ctx.has_bias:
-            dbias = channel_sum(dz, N, st)
-        dW = conv_wgrad(x, dz, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, cfg.name, ctx.in_affine, plan)
+        dbias = channel_sum(dz, N, st) if need_b else None
+        dW = conv_wgrad(x, dz, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, cfg.name, ctx.in_affine, plan) if need_w else None
+        if image:
+            return conv_image_grad(da, weight, tuple(x.shape), cfg.k, cfg.pad, z, float(cfg.slope), None, cfg.name), dW, dbias, None, None
         return _input_grad(ctx, dz, x, weight, plan, st), dW, dbias, None, None
 
 
@@ -791,15 +848,16 @@ class _ConvBnBlock(torch.autograd.Function):
     that is not the first layer's training block.  hin: the hand-over of a producer whose raw output x is (the BatchNorm +
     LeakyReLU of that block are applied on this block's loads).  cfg.defer_act: returns (z, BnHandover) and leaves the
     activation to the consumer.  Eval mode runs on the running statistics -- folded into weights / bias where that is one
-    launch -- and has no backward."""
+    launch -- and its backward gives the input gradient alone, on the folded path, when the input asked for one (eval_dx)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, cfg, plan, hin):
+    def forward(ctx, x, weight, bias, gamma, beta, cfg, plan, hin, eval_dx=False):
         x, weight = _f32(x, 'conv input'), _f32(weight, 'conv weight')
         st = _stream()
         N = weight.shape[0]
         bn = cfg.bn
         ctx.cfg, ctx.has_bias, ctx.bn_train, ctx.hin, ctx.hout = cfg, bias is not None, bool(bn.training), hin, None
+        ctx.eval_dx, ctx.x_shape = False, tuple(x.shape)
         ctx.set_materialize_grads(False)      # the hand-over that leaves next to z is no tensor and gets no gradient
         ctx.in_affine = ina = None if hin is None else (hin.scale, hin.shift, hin.slope)
         scale, shift, mean, invstd = (_empty((N,), x) for _ in range(4))
@@ -812,13 +870,19 @@ class _ConvBnBlock(torch.autograd.Function):
             if FOLD_EVAL_BN and not cfg.defer_act and ina is None and 0.0 <= slope <= 1.0:
                 # eval mode (predict_fns.py:38-43, 65-69): ONE launch per block.  The first layer applies scale / shift in its
                 # own epilogue (its kernel takes them); every other layer runs on weights and bias with the BatchNorm folded in
-                ctx.save_for_backward()
+                # eval_dx (conv_block: the input wants a gradient): what the input gradient needs is kept -- the output for the
+                # sign of z, and the weight the forward ran on (a first-layer block: the raw weight and the BatchNorm scale)
+                ctx.eval_dx = bool(eval_dx and not cfg.out_bf16)
                 if plan.conv1:
                     call('cy_bn_eval_scale_shift', _ptr(gamma), _ptr(beta), _ptr(bn.running_mean), _ptr(bn.running_var),
                          float(bn.eps), _ptr(scale), _ptr(shift), N, st)
-                    return conv1_affine_act(x, weight, bias, scale, shift, slope, cfg.name, cfg.out_bf16)
+                    out = conv1_affine_act(x, weight, bias, scale, shift, slope, cfg.name, cfg.out_bf16)
+                    ctx.save_for_backward(*((out, weight, scale) if ctx.eval_dx else ()))
+                    return out
                 Wf, bf = fold_eval_bn(weight, bias, gamma, beta, bn)
-                return _leave(conv_forward(x, Wf, bf, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, None, False, cfg.name, None, lrelu=slope), cfg, st)
+                out = conv_forward(x, Wf, bf, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, None, False, cfg.name, None, lrelu=slope)
+                ctx.save_for_backward(*((out, Wf, None) if ctx.eval_dx else ()))
+                return _leave(out, cfg, st)
             z = conv_forward(x, weight, bias, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, None, False, cfg.name, ina)
             call('cy_bn_eval_scale_shift', _ptr(gamma), _ptr(beta), _ptr(bn.running_mean), _ptr(bn.running_var),
                  float(bn.eps), _ptr(scale), _ptr(shift), N, st)
@@ -839,7 +903,9 @@ class _ConvBnBlock(torch.autograd.Function):
         cfg = ctx.cfg
         da = _grad_f32(da, cfg)
         if not ctx.bn_train:
-            raise _lib.HipExtensionError('backward through an eval-mode BatchNorm block is not implemented')
+            if not ctx.eval_dx:
+                raise _lib.HipExtensionError('backward through an eval-mode BatchNorm block is not implemented')
+            return (_ConvBnBlock._eval_input_grad(ctx, da),) + (None,) * 8
         st = _stream()
         x, weight, z, scale, shift, mean, invstd, gamma = ctx.saved_tensors
         N = weight.shape[0]
@@ -884,7 +950,27 @@ class _ConvBnBlock(torch.autograd.Function):
             call('cy_bn_bwd_apply', _ptr(z), _ptr(da), _ptr(dz), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd),
                  _ptr(gamma), slope, _ptr(red), _ptr(dgamma), _ptr(dbeta), P, N, st)
             dW = conv_wgrad(x, dz, cfg.k, cfg.stride, cfg.pad, cfg.nchw_in, cfg.name, ctx.in_affine, plan)
-        return _input_grad(ctx, dz, x, weight, plan, st), dW, dbias, dgamma, dbeta, None, None, None
+        return _input_grad(ctx, dz, x, weight, plan, st), dW, dbias, dgamma, dbeta, None, None, None, None
+
+    @staticmethod
+    def _eval_input_grad(ctx, da):
+        """dx of a folded eval-mode block, and nothing else: lrelu'(z) from the sign of the saved output, the BatchNorm scale inside
+        the weight the forward ran on (or, for a first-layer block, on the image-gradient kernel's loads)."""
+        cfg = ctx.cfg
+        if any(ctx.needs_input_grad[1:5]):
+            raise _lib.HipExtensionError('conv block %s: an eval-mode BatchNorm block gives the input gradient only; its weight, bias, '
+                                         'gamma and beta get no gradient there (switch their requires_grad off, or train())' % cfg.name)
+        out, weight, scale = ctx.saved_tensors
+        slope = 1.0 if cfg.slope is None else float(cfg.slope)
+        if cfg.nchw_in:
+            if not image_grad_plan(ctx.x_shape, weight.shape[0], cfg.k, cfg.stride, cfg.pad).ok:
+                raise _lib.HipExtensionError('input gradient of an NCHW-input convolution is not implemented')
+            return conv_image_grad(da, weight, ctx.x_shape, cfg.k, cfg.pad, out, slope, scale, cfg.name)
+        dz = da
+        if slope != 1.0:
+            dz = torch.empty_like(out)
+            call('cy_act_bwd', _ptr(out), _ptr(da), _ptr(dz), slope, out.numel(), _stream())
+        return conv_dgrad(dz, weight, ctx.x_shape, cfg.k, cfg.stride, cfg.pad, cfg.name)
 
 
 # ------------------------------------------------------------------------------------------------ bf16 convolution path
@@ -1085,7 +1171,10 @@ def conv_block(x, weight, bias, gamma, beta, cfg, handover=None):
     if (plan.conv1_bwd and cfg.bn.training and not cfg.defer_act and not x.requires_grad
             and (cfg.slope is None or 0.0 <= float(cfg.slope) <= 1.0)):
         return _Conv1TrainBlock.apply(x, weight, bias, gamma, beta, cfg, plan)
-    return _ConvBnBlock.apply(x, weight, bias, gamma, beta, cfg, plan, handover)
+    # an eval-mode block whose input wants a gradient keeps what that gradient needs (decided here: inside a Function's forward the
+    # grad mode is off); under torch.no_grad() and for inputs without requires_grad nothing is kept
+    eval_dx = bool(not cfg.bn.training and torch.is_grad_enabled() and x.requires_grad)
+    return _ConvBnBlock.apply(x, weight, bias, gamma, beta, cfg, plan, handover, eval_dx)
 
 
 # ------------------------------------------------------------------------------------------------ routing

@@ -478,6 +478,34 @@ int cy_linear_wgrad(const float* dY, const float* X, float* dW, float* db, int M
  * y int64; a label outside 0 .. C-1 reads nothing and contributes no target term. */
 int cy_softmax_xent(const float* scores, const long long* y, float* loss, float* dscores, int M, int C, void* stream);
 
+/* ------------------------------------------------------------------ gradient with respect to the image (csrc/image_grad.hip)
+ * The input gradient of a first layer: a stride-1 convolution that reads the NCHW image.  dx[B][3][H][W] (NCHW fp32) from
+ * dy[B][Ho][Wo][Cout] (NHWC fp32, Ho = H + 2 pad - k + 1) and W[Cout][3][k][k]; the activation's derivative and an eval-mode
+ * BatchNorm scale are applied on the loads of dy:
+ *   dz[p][co]       = dy[p][co] * (act == NULL ? 1 : (act[p][co] > 0 ? 1 : slope)) * (scale == NULL ? 1 : scale[co])
+ *   dx[b][c][y][x]  = sum over co, kh, kw of dz[b][y + pad - kh][x + pad - kw][co] * W[co][c][kh][kw]     (terms off the map are absent)
+ * act: the block's own OUTPUT [B][Ho][Wo][Cout] (its sign is the sign of the pre-activation for a slope in [0, 1]; other slopes are
+ * refused when act is given).  Supported: Cin == 3, k odd in 1..9, pad 0..k/2, Cout 1..1024, H and W >= k - 2 pad, any B whose tile
+ * count stays below 2^31; everything else is CY_EINVAL before a launch, and cy_conv_image_grad_ok answers 0 for the shape.  fp32
+ * accumulation, no atomics, no workspace: every element of dx is summed by one thread with co, kh, kw ascending, so a call repeats bit
+ * for bit.  Tiles of 16 x 32 image pixels per block; partial tiles and taps off the map are predicated. */
+int cy_conv_image_grad_ok(int B, int H, int W, int Cout, int k, int pad);
+int cy_conv_image_grad(const float* dy, const float* act, const float* scale, const float* W, float* dx, int B, int H, int Wd,
+                       int Cin, int Cout, int k, int pad, float slope, void* stream);
+
+/* ------------------------------------------------------------------ attack step and saliency map (csrc/attack.hip)
+ * cy_attack_step: one signed-gradient step of FGSM / PGD, in place on x, n elements, every line one fp32 rounding:
+ *   s = (g > 0) - (g < 0)                       (0 for g == 0 and for NaN)
+ *   t = x + alpha * s                           (alpha * s is exact)
+ *   t = min(max(t, x0 - eps), x0 + eps)         (each bound rounded once)
+ *   x = min(max(t, lo), hi)
+ * alpha, eps >= 0 and lo <= hi, else CY_EINVAL. */
+int cy_attack_step(float* x, const float* x0, const float* g, float alpha, float eps, float lo, float hi, long long n, void* stream);
+/* out[b][y][x] (uint8) = floor(m / max_b * 255 + 0.5), m = max over the 3 channels of |g[b][c][y][x]| and max_b the largest m of image
+ * b (the quotient, the product and the sum each rounded once to fp32).  NaN counts as 0, infinity as FLT_MAX; an image whose max_b is
+ * 0 gives zeros.  One workgroup per image: a workgroup reduction for max_b, then one store pass.  No atomics. */
+int cy_grad_saliency_u8(const float* g, unsigned char* out, int B, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------ data movement / elementwise around the path
  * Layout permutes standing in for the reference's view/permute/cat glue (models.py:8-19, 80-82):
  * out[b][i1][i2][i3] (contiguous, dims nb x d1 x d2 x d3) = in[b*sb + i1*s1 + i2*s2 + i3*s3];

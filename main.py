@@ -48,6 +48,12 @@ hit counts; one line per frame goes to <model_dir>/tracks_output.txt, serve_outp
 ``--mode interpret --model capsule --restore last|best [--synthetic N] [--index I]`` is the reference's capsule_interpret.py:
 the 16 x 11 perturbation sweep of sample I's labelled capsule through the fused decoder kernel, written to <model_dir>/img/
 (see interpret()).
+``--mode attack --model capsule|cnn --restore last|best [--use_ema] [--synthetic N] --eps 0,1,2,4,8 [--attack fgsm|pgd --attack_steps K
+--attack_alpha A] [--index I]`` (new) measures the restored classifier's accuracy under a bounded perturbation of every test image
+(capsyolo_amd.attack: the gradient with respect to the image on the project's kernels; ``--eps`` and ``--attack_alpha`` in grey levels) and
+writes one ``eps:accuracy, `` entry per level to <model_dir>/attack_output.txt; with ``--index`` also sample I clean, perturbed at the
+largest level, and its saliency map as attack_<I>_clean.ppm / _adv.ppm / _saliency.ppm (see attack()).  ``--model cnn`` needs
+``--cnn_kernels hip``.
 ``--mode train --model darknet_d|darknet_r|darkcapsule* --augment [--gtsrb DIR] [--synthetic N]`` (new) trains on the reference's
 sign-paste augmentation (build_data.py:171-288) made fresh for every batch on the device instead of frozen as ``--aug N`` copies:
 the raw frames of <data_dir>/train_raw.p (``build_data.py --keep_raw``) stay on the device, ``add_signs`` comes from params.json
@@ -87,7 +93,7 @@ from capsyolo_amd.predict_fns import class_pred, class_scores_device, dark_class
 
 parser = argparse.ArgumentParser()
 parser.add_argument('--model', default='cnn', help=' | '.join(config.model_names))
-parser.add_argument('--mode', default='train', help='train | predict | detect | serve | overfit | interpret')
+parser.add_argument('--mode', default='train', help='train | predict | detect | serve | overfit | interpret | attack')
 parser.add_argument('--summary', default=True, help='if summarize model', action='store_true')
 parser.add_argument('--seed', type=int, default=0, help='random seed')
 parser.add_argument('--lr', type=float, default=1e-3, help='learning rate')
@@ -106,7 +112,24 @@ parser.add_argument('--model_dir', default=None, help='model dir')
 parser.add_argument('--show', default=False, help='save result', action='store_true')
 parser.add_argument('--npy', default=False, help='data is npy file', action='store_true')
 parser.add_argument('--synthetic', type=int, default=0, help='use N synthetic samples instead of data/')
-parser.add_argument('--index', type=int, default=0, help='--mode interpret: which sample of the eval set (or of the --synthetic samples)')
+class _StoreGiven(argparse.Action):
+    """store, and note in <dest>_given that the option was on the command line (a default cannot tell)."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        setattr(namespace, self.dest + '_given', True)
+
+
+parser.add_argument('--index', type=int, default=0, action=_StoreGiven,
+                    help='--mode interpret: which sample of the eval set (or of the --synthetic samples).  --mode attack: when given, '
+                         'also write this test sample clean, perturbed and as a saliency map')
+parser.set_defaults(index_given=False)
+parser.add_argument('--eps', default=None, metavar='E0,E1,...',
+                    help='--mode attack: the perturbation bounds in grey levels (1 = 1/128 of the centred input), e.g. 0,1,2,4,8')
+parser.add_argument('--attack', default='fgsm', choices=('fgsm', 'pgd'), help='--mode attack: one signed-gradient step, or projected steps')
+parser.add_argument('--attack_steps', type=int, default=10, metavar='K', help='--attack pgd: number of steps')
+parser.add_argument('--attack_alpha', type=float, default=None, metavar='A',
+                    help='--attack pgd: step size in grey levels (default: 2.5 * eps / steps)')
 parser.add_argument('--n_epochs', type=int, default=0, help='override params.json n_epochs')
 parser.add_argument('--batch_size', type=int, default=0, help='override params.json batch_size')
 parser.add_argument('--graph', action='store_true',
@@ -815,6 +838,89 @@ def interpret(args, model, model_dir, data_dir, params):
     return res
 
 
+def check_attack(args):
+    """The refusals of --mode attack that need neither the data nor a device; returns the --eps levels (grey levels, as given)."""
+    from capsyolo_amd import attack as image_attack
+    if args.model not in ('cnn', 'capsule'):
+        raise SystemExit('attack mode differentiates the classifiers with respect to the image: %s; got --model %s'
+                         % (image_attack.SUPPORTED, args.model))
+    if args.restore is None:
+        raise SystemExit('Must give restore file last/best')
+    if args.eps is None:
+        raise SystemExit('attack mode needs --eps E0,E1,... (grey levels, e.g. 0,1,2,4,8)')
+    try:
+        levels = image_attack.parse_grey_levels(args.eps)
+        if args.attack_alpha is not None:
+            image_attack.parse_grey_levels(args.attack_alpha, '--attack_alpha')
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if args.attack == 'pgd' and args.attack_steps < 1:
+        raise SystemExit('--attack_steps %d: at least one step' % args.attack_steps)
+    if getattr(args, 'index_given', False) and args.index < 0:
+        raise SystemExit('--index %d: at least 0' % args.index)
+    return levels
+
+
+def attack(args, model, model_dir, data_dir, params):
+    """`--mode attack`: the restored classifier's accuracy on the test set (`--synthetic N`: N synthetic GTSRB-shaped samples,
+    otherwise data_dir/test.p) with every image moved inside an L-infinity ball of --eps grey levels by FGSM, or by --attack pgd with
+    --attack_steps steps of --attack_alpha grey levels (default 2.5 * eps / steps), against the margin loss (capsule, without the
+    reconstruction term) or the cross-entropy (cnn).  Writes `level:accuracy, ` per level, in the format of metric_output.txt, to
+    <model_dir>/attack_output.txt and returns {level: accuracy}.  --index I: sample I as it is, at the largest level, and the
+    saliency map of its gradient (grey, 0..255 of the image's own maximum) go to attack_<I>_clean.ppm / _adv.ppm / _saliency.ppm."""
+    from capsyolo_amd import attack as image_attack
+    levels = check_attack(args)
+    if args.model == 'cnn' and not _cnn_on_hip(params):
+        raise SystemExit('attack mode runs on the project\'s kernels: %s' % image_attack.SUPPORTED)
+    if params.device != 'cuda':
+        raise SystemExit('attack mode runs on hand-written gfx950 kernels only; no GPU is visible')
+    if args.synthetic:
+        x, y = synth.images(args.synthetic, 32), synth.gtsrb_labels(args.synthetic, params.n_classes)
+    else:
+        import pickle
+        with open(data_dir + config.te_d, 'rb') as f:
+            x, y = pickle.load(f)
+    x, y = np.asarray(x), np.asarray(y)
+    if getattr(args, 'index_given', False) and args.index >= len(y):
+        raise SystemExit('--index %d: the set has %d samples' % (args.index, len(y)))
+    path = os.path.join(model_dir, args.restore + '.pth.tar')
+    print("Restoring parameters from {}".format(path))
+    utils.load_checkpoint(path, model, params)
+    params.recon = False                                     # the attacked loss is the classification loss
+    loss_fn = model_loss_predict[args.model][1]
+    g = image_attack.GREY
+
+    def how(level):
+        """(attack, alpha, steps) at one level, in input units; a PGD whose step would be 0 is the single step."""
+        alpha = (args.attack_alpha if args.attack_alpha is not None else 2.5 * level / args.attack_steps) * g
+        return (args.attack, alpha, args.attack_steps) if args.attack == 'pgd' and alpha > 0 else ('fgsm', None, 0)
+    out = {}
+    for level in levels:
+        kind, alpha, steps = how(level)
+        out[level] = image_attack.robust_accuracy(model, x, y, params, loss_fn, [level * g], attack=kind, alpha=alpha, steps=steps,
+                                                  batch_size=params.batch_size)[level * g]
+    with open(os.path.join(model_dir, 'attack_output.txt'), 'w') as text_file:
+        for k, v in out.items():
+            text_file.write("{:g}:{}, ".format(k, v))
+            print("{:g}:{}, ".format(k, v))
+    if getattr(args, 'index_given', False):
+        i, level = args.index, max(levels)
+        xi = torch.from_numpy(np.ascontiguousarray(x[i:i + 1])).to(device=params.device, dtype=torch.float32).permute(0, 3, 1, 2).contiguous()
+        yi = torch.from_numpy(np.ascontiguousarray(y[i:i + 1])).to(device=params.device, dtype=torch.int64)
+        kind, alpha, steps = how(level)
+        model.eval()
+        if kind == 'fgsm':
+            adv = image_attack.fgsm(model, xi, yi, params, loss_fn, level * g)
+        else:
+            adv = image_attack.pgd(model, xi, yi, params, loss_fn, level * g, alpha, steps)
+        sal = image_attack.saliency(model, xi, yi, params, loss_fn)[0].cpu().numpy()
+        stem = os.path.join(model_dir, 'attack_%d_' % i)
+        capsule_interpret.write_ppm(stem + 'clean.ppm', capsule_interpret.to_bytes(x[i]))
+        capsule_interpret.write_ppm(stem + 'adv.ppm', capsule_interpret.to_bytes(adv[0].permute(1, 2, 0).cpu().numpy()))
+        capsule_interpret.write_ppm(stem + 'saliency.ppm', np.ascontiguousarray(np.repeat(sal[:, :, None], 3, axis=2)))
+    return out
+
+
 def main(argv=None):
     args = parser.parse_args(argv)
     if args.model not in config.model_names:
@@ -824,6 +930,8 @@ def main(argv=None):
         check_class_augment(args)
     if args.mode == 'serve':
         check_serve(args)
+    if args.mode == 'attack':
+        check_attack(args)
     check_nms(args)
     check_track(args)
     data_dir, model_dir = config.data_dir[args.model], config.model_dir[args.model]
@@ -844,8 +952,11 @@ def main(argv=None):
                              'torch.optim.Adam; use --cnn_kernels hip or another model')
     elif params.ema_warmup:
         raise SystemExit('--ema_warmup shapes the schedule of --ema: give --ema D')
-    if params.use_ema and args.mode not in ('predict', 'detect', 'serve', 'interpret'):
-        raise SystemExit('--use_ema runs a restored model on its averaged weights: --mode predict | detect | serve | interpret')
+    if params.use_ema and args.mode not in ('predict', 'detect', 'serve', 'interpret', 'attack'):
+        raise SystemExit('--use_ema runs a restored model on its averaged weights: --mode predict | detect | serve | interpret | attack')
+    if args.mode == 'attack' and args.model == 'cnn' and not _cnn_on_hip(params):
+        from capsyolo_amd import attack as image_attack
+        raise SystemExit('attack mode runs on the project\'s kernels: %s' % image_attack.SUPPORTED)
     if args.nms_class_aware and int(getattr(params, 'n_classes', 0)) == 0:
         raise SystemExit('--nms_class_aware needs a detector with class scores (n_classes > 0 in %s/params.json)' % model_dir)
     params.rank, params.world, local_rank = dp.init_from_env()
@@ -894,7 +1005,7 @@ def main(argv=None):
         return train_and_evaluate(model, optimizer, loss_fn, metric, params, data, model_dir, restore_file=args.restore)
     if args.augment:
         raise SystemExit('--augment belongs to --mode train')
-    modes = {'predict': predict, 'detect': detect, 'serve': serve, 'interpret': interpret}
+    modes = {'predict': predict, 'detect': detect, 'serve': serve, 'interpret': interpret, 'attack': attack}
     if args.mode in modes:
         try:
             return modes[args.mode](args, model, model_dir, data_dir, params)

@@ -106,5 +106,14 @@ for M in (16, 64, 1024):
     rep(tag + 'fwd (%d shares)' % query('cy_linear_fwd_shares', M, N, K), lin_fwd)
     rep(tag + 'dgrad', lin_dgrad)
     rep(tag + 'wgrad', lin_wgrad)
+# the gradient with respect to the image (csrc/image_grad.hip): one thread sums each element in one order.  CapsuleNet's conv1 with
+# the ReLU's derivative on the loads, ConvNet's first block with derivative and BatchNorm scale, a backbone's first block plain
+for (Cout, k, pad, H, slope, scaled) in ((256, 9, 0, 32, 0.0, False), (64, 3, 1, 32, 0.01, True), (128, 3, 1, 208, None, False)):
+    Ho = H + 2 * pad - k + 1
+    dy, act = torch.randn(B, Ho, Ho, Cout, device=dev), torch.randn(B, Ho, Ho, Cout, device=dev)
+    w, sc = torch.randn(Cout, 3, k, k, device=dev) * 0.05, torch.rand(Cout, device=dev) + 0.5
+    rep('image grad 3<-%d k%d p%d %dx%d%s%s' % (Cout, k, pad, H, H, '' if slope is None else ' act %g' % slope, ' scale' if scaled else ''),
+        lambda: ops.conv_image_grad(dy, w, (B, 3, H, H), k, pad, None if slope is None else act, 1.0 if slope is None else slope,
+                                    sc if scaled else None))
 print('check_determinism:', 'ok' if bad == 0 else 'FAILED')
 sys.exit(0 if bad == 0 else 1)
