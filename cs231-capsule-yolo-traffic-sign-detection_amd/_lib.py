@@ -53,6 +53,12 @@ class Decoder(C.Structure):
                [(k, C.c_int) for k in ('n', 'C', 'D', 'n_delta')]
 
 
+class AdamStep(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ('table', 'ema_table', 'blockmap', 'hyper', 'record')] + \
+               [(k, C.c_int) for k in ('n_blocks', 'chunk')] + \
+               [(k, C.c_float) for k in ('lr', 'beta1', 'beta2', 'eps', 'bias_corr1', 'bias_corr2', 'one_minus_decay')]
+
+
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_longlong
 
 # name -> argtypes (all return int unless listed in _RET)
@@ -156,16 +162,9 @@ _SIGS = {
     'cy_cast_f32_bf16': [_P, _P, _L, _P],
     'cy_cast_bf16_f32': [_P, _P, _L, _P],
     'cy_multi_copy': [_P, _P, _I, _I, _P, _I, _F, _P],
-    'cy_adam_multi': [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _P],
-    'cy_adam_multi_dev': [_P, _P, _I, _I, _P, _P],
+    'cy_adam_step': [C.POINTER(AdamStep), _P],
     'cy_grad_sumsq_multi': [_P, _P, _I, _I, _P, _P],
     'cy_grad_clip_finish': [_P, _I, _F, _I, _P, _P, _P],
-    'cy_adam_multi_clip': [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P],
-    'cy_adam_multi_dev_clip': [_P, _P, _I, _I, _P, _P, _P],
-    'cy_adam_multi_ema': [_P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P],
-    'cy_adam_multi_dev_ema': [_P, _P, _P, _I, _I, _P, _P],
-    'cy_adam_multi_clip_ema': [_P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P, _P],
-    'cy_adam_multi_dev_clip_ema': [_P, _P, _P, _I, _I, _P, _P, _P],
     'cy_linear_fwd': [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     'cy_linear_dgrad': [_P, _P, _P, _P, _I, _I, _I, _P],
     'cy_linear_wgrad': [_P, _P, _P, _P, _I, _I, _I, _P],
@@ -220,7 +219,7 @@ _RET = {
     'cy_conv_image_grad_ok': (_I, [_I, _I, _I, _I, _I, _I]),
 }
 EXPORTS = sorted(list(_SIGS) + list(_RET))
-ABI_VERSION = 5     # what the signatures above were written against (include/capsyolo_hip.h, csrc/error.cpp)
+ABI_VERSION = 6     # what the signatures above were written against (include/capsyolo_hip.h, csrc/error.cpp)
 
 _lib = None
 
@@ -254,14 +253,14 @@ def load():
     return lib
 
 
-TRACE = None        # a list: every C-ABI call appends its entry-point name (launch census of tests / tools); None = off
+TRACE = None        # a list: every C-ABI call appends its entry-point name, or the caller's label (launch census of tests / tools); None = off
 
 
-def call(name, *args):
+def call(name, *args, trace=None):
     """Call an int-returning entry point; non-zero -> HipExtensionError with the library's message."""
     lib = load()
     if TRACE is not None:
-        TRACE.append(name)
+        TRACE.append(name if trace is None else trace)
     rc = getattr(lib, name)(*args)
     if rc != 0:
         msg = lib.capsyolo_last_error()

@@ -1,17 +1,14 @@
 // Global gradient norm for optim.Adam's clipping and non-finite guard (gfx950): a deterministic two-stage reduction over every
-// gradient of a step that leaves its verdict in device memory, where the Adam launch reads it (csrc/adam.hip, the _clip kernels).
+// gradient of a step that leaves its verdict in device memory, where the Adam launch reads it (csrc/adam.hip, cy_adam_step's record).
 //   stage 1  cy_grad_sumsq_multi: one workgroup per entry of Adam's own block map, partial[b] = sum of g^2 over that chunk
 //   stage 2  cy_grad_clip_finish: one workgroup adds the partials and writes record = {total_norm, coef, go, 0}
 // The squares are formed and summed in double from the fp32 values: no overflow (an fp32 square is below 2^256), so the sum is
 // non-finite exactly when some gradient element is.  Every sum has a fixed order (strided per-thread sums, then a tree through
 // LDS) and there are no atomics: two runs on the same gradients give the same bits.  HBM-bound: one read of 4 B per element.
 #include "common.h"
+#include "multi_tensor.h"
 
 namespace {
-
-struct AdamEntry {                     // a row of Adam's pointer table (csrc/adam.hip)
-  float* p; const float* g; float* m; float* v; long long n;
-};
 
 // sum over the 256 threads of the workgroup in a fixed tree; the result is valid in thread 0
 __device__ __forceinline__ double block_sum_256(double acc, double* red) {
@@ -32,9 +29,8 @@ __global__ __launch_bounds__(256) void grad_sumsq_multi_kernel(const AdamEntry* 
   __shared__ double red[256];
   const int2 bm = blockmap[blockIdx.x];
   const AdamEntry e = table[bm.x];
-  const long long begin = (long long)bm.y * chunk;
-  long long end = begin + chunk;
-  if (end > e.n) end = e.n;
+  long long begin, end;
+  chunk_range(bm, chunk, e.n, begin, end);
   double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
   long long i = begin + threadIdx.x;
   for (; i + 768 < end; i += 1024) {

@@ -115,7 +115,7 @@ class GraphedStep(object):
         return y_hat, loss
 
     def _captured_step(self):
-        # optim.Adam.step with graph_hyper set launches cy_adam_multi_dev (or its _clip variant); its per-parameter step counters must
+        # optim.Adam.step with graph_hyper set launches cy_adam_step with its scalars in device memory (hyper); its per-parameter step counters must
         # not move during the capture (the replay's counters are advanced by _refresh_scalars)
         saved = dict((p, int(self.opt.state[p]['step'])) for g in self.opt.param_groups for p in g['params'] if p in self.opt.state and len(self.opt.state[p]))
         self.opt.step()

@@ -11,7 +11,7 @@ Optional, both decided on the device without a host synchronisation (csrc/gradno
                        any other step.
 With both off, step() issues exactly the launches it issues without them and none of their device state exists.
 
-Optional, kept inside the same Adam launch (the _ema kernels of csrc/adam.hip):
+Optional, kept inside the same Adam launch (cy_adam_step's ema_table):
   ema_decay=D          an exponential moving average of every parameter the optimizer updates: ema = d_t * ema + (1 - d_t) * p after
                        each update of p, d_t = D, or with ema_warmup=True d_t = min(D, (1 + t) / (10 + t)) with t the parameter's own
                        step count.  opt.ema[p] starts as a copy of p before p's first step and moves exactly in the steps that update
@@ -31,9 +31,14 @@ import numpy as np
 import torch
 
 from . import ops as _ops
-from ._lib import call
+from ._lib import AdamStep, call
 
 _CHUNK = 16384
+
+
+def _n_chunks(p):
+    """Block-map entries (workgroups) of one tensor."""
+    return (p.numel() + _CHUNK - 1) // _CHUNK
 
 
 class Adam(torch.optim.Optimizer):
@@ -54,7 +59,7 @@ class Adam(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False))
         self._plan_key, self._plan = None, None
         self.graph_tables = None     # ... and per group (pinned host, device) pointer tables [n parameters with a gradient][5]
-        self.graph_hyper = None      # graph_step.GraphedStep: per group a device tensor of step_scalars()'s six floats, eight with an EMA (cy_adam_multi_dev*)
+        self.graph_hyper = None      # graph_step.GraphedStep: per group a device tensor of step_scalars()'s six floats, eight with an EMA (cy_adam_step's hyper)
         # attributes, not param_groups entries: state_dict() is that of torch.optim.Adam with or without them
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
@@ -169,13 +174,25 @@ class Adam(torch.optim.Optimizer):
         self._plan_key = None
         _ops._bump_param_epoch()
 
+    def _upload(self, entries, table, ema_table):
+        """The rows of `entries` into a (pinned host, device) pair of pointer tables [n][5], and the pointers of their averages into a
+        pair [n] where there is one: filled on the host, copied asynchronously on the step's stream."""
+        host, dev = table
+        host.numpy()[...] = np.asarray([(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
+                                        for p, g, m, v in entries], dtype=np.int64)
+        dev.copy_(host, non_blocking=True)
+        if ema_table is not None:
+            host, dev = ema_table
+            host.numpy()[...] = np.asarray([self.ema[p].data_ptr() for p, _, _, _ in entries], dtype=np.int64)
+            dev.copy_(host, non_blocking=True)
+
     def _build_plan(self, entries, device):
         """Pointer table + block map on the device.  The block map depends on the sizes only and is uploaded once; the
         table (the gradient tensors are new allocations every step) goes through a small ring of pinned staging buffers
         with an asynchronous copy on the step's stream: no host synchronisation in the step."""
         blocks = []
         for k, (p, g, m, v) in enumerate(entries):
-            blocks.extend((k, c) for c in range((p.numel() + _CHUNK - 1) // _CHUNK))
+            blocks.extend((k, c) for c in range(_n_chunks(p)))
         sizes = tuple(e[0].numel() for e in entries)
         if getattr(self, '_bm_key', None) != (sizes, device):
             bm = np.asarray(blocks, dtype=np.int32).reshape(-1, 2)
@@ -186,21 +203,15 @@ class Adam(torch.optim.Optimizer):
             self._ring_pos = 0
             self._ema_table_dev, self._ema_ring = None, None
         if self.ema_decay is not None and self._ema_table_dev is None:
-            # the averages' pointers: a second table (the layout of the first is cy_adam_multi's and stays) with a ring of its own
+            # the averages' pointers: a second table (the layout of the first stays [n][5]) with a ring of its own
             self._ema_table_dev = torch.empty(len(entries), dtype=torch.int64, device=device)
             self._ema_ring = [torch.empty(len(entries), dtype=torch.int64).pin_memory() for _ in range(4)]
         k = self._ring_pos
         self._ring_pos = (k + 1) % 4
         if self._ring_events[k] is not None:
             self._ring_events[k].synchronize()           # four steps old: long done
-        host = self._ring[k]
-        host.numpy()[...] = np.asarray([(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
-                                        for p, g, m, v in entries], dtype=np.int64)
-        self._table_dev.copy_(host, non_blocking=True)
-        if self.ema_decay is not None:
-            host = self._ema_ring[k]
-            host.numpy()[...] = np.asarray([self.ema[p].data_ptr() for p, _, _, _ in entries], dtype=np.int64)
-            self._ema_table_dev.copy_(host, non_blocking=True)
+        self._upload(entries, (self._ring[k], self._table_dev),
+                     (self._ema_ring[k], self._ema_table_dev) if self.ema_decay is not None else None)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(device))
         self._ring_events[k] = ev
@@ -220,16 +231,13 @@ class Adam(torch.optim.Optimizer):
             if tuple(host.shape) != (len(entries), 5):
                 raise RuntimeError('capsyolo_amd.optim.Adam: the captured step updates %d parameters, its table was made for %d'
                                    % (len(entries), host.shape[0]))
-            host.numpy()[...] = np.asarray([(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
-                                            for p, g, m, v in entries], dtype=np.int64)
-            table.copy_(host, non_blocking=True)
+            ema_pair = None
             if self.ema_decay is not None:
                 if self.graph_ema_tables is None or tuple(self.graph_ema_tables[id(group)][0].shape) != (len(entries),):
                     raise RuntimeError('capsyolo_amd.optim.Adam: the captured step has no table for the %d EMA pointers' % len(entries))
-                host, table_ema = self.graph_ema_tables[id(group)]
-                host.numpy()[...] = np.asarray([self.ema[p].data_ptr() for p, _, _, _ in entries], dtype=np.int64)
-                table_ema.copy_(host, non_blocking=True)
-            nblocks = sum((p.numel() + _CHUNK - 1) // _CHUNK for p, _, _, _ in entries)
+                ema_pair = self.graph_ema_tables[id(group)]
+            self._upload(entries, (host, table), ema_pair)
+            nblocks = sum(_n_chunks(p) for p, _, _, _ in entries)
             return (table, self._bm, nblocks)
         key = tuple(x.data_ptr() for e in entries for x in e)
         if self.ema_decay is not None:
@@ -247,13 +255,13 @@ class Adam(torch.optim.Optimizer):
         cy_grad_clip_finish: the record that every Adam launch of this step reads.  Returns the launches' tables where they are
         still valid for the Adam launches (one launch, or the captured step's per-group tables), else None."""
         dev = launches[0][2][0][0].device
-        need = sum((p.numel() + _CHUNK - 1) // _CHUNK for _, _, entries in launches for p, _, _, _ in entries)
+        need = sum(_n_chunks(p) for _, _, entries in launches for p, _, _, _ in entries)
         if self._clip_buf is None:
             self._clip_buf = torch.zeros(3, dtype=torch.int64, device=dev)
             self._clip_reset()
         if self._partial is None or self._partial.numel() < need:
             # once: room for every parameter of every group (each is in at most one launch of a step)
-            every = sum((p.numel() + _CHUNK - 1) // _CHUNK for g in self.param_groups for p in g['params'])
+            every = sum(_n_chunks(p) for g in self.param_groups for p in g['params'])
             self._partial = torch.empty(max(need, every), dtype=torch.float64, device=dev)
         tables, off = [], 0
         for group, _, entries in launches:
@@ -304,24 +312,26 @@ class Adam(torch.optim.Optimizer):
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         clip = self.max_grad_norm is not None or self.skip_nonfinite
         tables = self._grad_verdict(launches, stream) if clip else None
-        record = C.c_void_p(self.clip_record.data_ptr()) if clip else None
         for k, (group, t, entries) in enumerate(launches):
             table, bm, nblocks = tables[k] if tables is not None else self._tables(group, entries)
-            head = [C.c_void_p(table.data_ptr())]
+            a = AdamStep(table=table.data_ptr(), blockmap=bm.data_ptr(), n_blocks=nblocks, chunk=_CHUNK)
             if ema:
-                head.append(C.c_void_p(self._ema_table(group).data_ptr()))
-            head += [C.c_void_p(bm.data_ptr()), nblocks, _CHUNK]
-            name = 'cy_adam_multi' + ('_dev' if self.graph_hyper is not None else '') + ('_clip' if clip else '') + ('_ema' if ema else '')
+                a.ema_table = self._ema_table(group).data_ptr()
+            if clip:
+                a.record = self.clip_record.data_ptr()
             if self.graph_hyper is not None:
                 hyper = self.graph_hyper[id(group)]
                 if hyper.numel() != (8 if ema else 6):
                     raise RuntimeError('capsyolo_amd.optim.Adam: the captured step\'s scalars are %d floats, this step reads %d'
                                        % (hyper.numel(), 8 if ema else 6))
-                tail = [C.c_void_p(hyper.data_ptr())]
+                a.hyper = hyper.data_ptr()
             else:
                 scalars = self.step_scalars(group, t)
-                assert len(scalars) == (8 if ema else 6), scalars       # {six of Adam} + {1 - d_t, 0}: what the entry point's argument list takes
-                tail = scalars[:6] + ([scalars[6]] if ema else [])
-            call(name, *(head + tail + ([record] if clip else []) + [stream]))
+                a.lr, a.beta1, a.beta2, a.eps, a.bias_corr1, a.bias_corr2 = scalars[:6]
+                if ema:
+                    a.one_minus_decay = scalars[6]
+            # the label says what was launched: it is read off the descriptor, not off the options
+            label = 'cy_adam_step' + ('+dev' if a.hyper else '') + ('+clip' if a.record else '') + ('+ema' if a.ema_table else '')
+            call('cy_adam_step', C.byref(a), stream, trace=label)
             _ops._bump_param_epoch()          # parameters changed through raw pointers: eval-mode fold caches are stale
         return loss

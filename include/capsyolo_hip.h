@@ -808,10 +808,7 @@ typedef struct {
 } cy_decoder_t;
 int cy_decoder_fwd(const cy_decoder_t* a, void* stream);
 
-/* ------------------------------------------------------------------ optimizer
- * torch.optim.Adam step (main.py:72,280) for a list of tensors in ONE launch.
- * table: device array of n_tensors records {param, grad, exp_avg, exp_avg_sq, numel} (5 x 8 bytes);
- * blockmap: device array of n_blocks int2 {tensor index, chunk index}. */
+/* ------------------------------------------------------------------ optimizer */
 /* zero-fill (asynchronous on `stream`) of the per-step scratch arena that the statistics kernels accumulate into */
 int cy_zero_bytes(void* p, long long nbytes, void* stream);
 /* Gradient bucket of the data-parallel step (between loss.backward() and optimizer.step(), main.py:71-72): every
@@ -819,12 +816,38 @@ int cy_zero_bytes(void* p, long long nbytes, void* stream);
  * int64 offset into flat, int64 numel}; blockmap[b] = {tensor index, chunk index}. */
 int cy_multi_copy(const void* table, const void* blockmap, int n_blocks, int chunk, float* flat, int unpack, float scale,
                   void* stream);
-int cy_adam_multi(const void* table, const void* blockmap, int n_blocks, int chunk,
-                  float lr, float beta1, float beta2, float eps, float bias_corr1, float bias_corr2,
-                  void* stream);
-/* The same step with its six scalars {lr, beta1, beta2, eps, bias_corr1, bias_corr2} read from device memory (hyper): for a
- * training step captured in a HIP graph, whose kernel arguments are frozen (the host refreshes hyper before every replay). */
-int cy_adam_multi_dev(const void* table, const void* blockmap, int n_blocks, int chunk, const float* hyper, void* stream);
+
+/* torch.optim.Adam step (main.py:72,280) for a list of tensors in ONE launch of n_blocks workgroups, whatever the descriptor selects.
+ * table: device array of n_tensors records {param, grad, exp_avg, exp_avg_sq, numel} (5 x 8 bytes); blockmap: device array of
+ * n_blocks int2 {tensor index, chunk index}.  The rule, per element, in torch's single-tensor order and in fp32:
+ *   g = coef * grad (record != NULL; the gradient tensors are not rewritten) or grad;
+ *   m = beta1 * m + (1 - beta1) * g;  v = beta2 * v + (1 - beta2) * g * g;
+ *   p -= (lr / bias_corr1) * (m / (sqrt(v) / sqrt(bias_corr2) + eps));
+ *   ema += one_minus_decay * (p - ema)  (ema_table != NULL), with the p just stored (= decay * ema + (1 - decay) * p).
+ * The three pointers that may be NULL select the variant; each adds to the plain step and changes nothing else of it:
+ *   hyper      the scalars come from device memory, {lr, beta1, beta2, eps, bias_corr1, bias_corr2}, with an ema_table two more,
+ *              {one_minus_decay, 0}: for a step captured in a HIP graph, whose kernel arguments are frozen (the host refreshes hyper
+ *              before every replay, so a captured step follows the step count and a decay schedule).  lr / bias_corr1 and
+ *              1 / sqrt(bias_corr2) are then formed on the device, else on the host.  Scalars in device memory cannot be checked
+ *              by the entry point: optim.Adam.step_scalars is their only source.
+ *   record     cy_grad_clip_finish's record (below): coef = record[1]; record[2] == 0 returns before anything is read or written,
+ *              so a skipped step changes no bit of a parameter, exp_avg, exp_avg_sq or average.
+ *   ema_table  device array of n_tensors float*, ema_table[k] the moving average of the parameter of table[k] (same numel, fp32, no
+ *              overlap with any tensor of table).  one_minus_decay = 1 - decay is formed in double by the caller and rounded ONCE
+ *              to fp32, in (0, 1]: the kernel never forms 1.f - decay.  Parameters, exp_avg and exp_avg_sq get the bits of the step
+ *              without the average; 36 bytes per element against 28.
+ * Refused with a message that names the field: a NULL table or blockmap, n_blocks or chunk <= 0, and with host scalars a bias
+ * correction that is not positive or, with an ema_table, a one_minus_decay outside (0, 1]. */
+typedef struct {
+  const void* table;       /* [n][5] int64 rows (p, g, exp_avg, exp_avg_sq, numel) */
+  const void* ema_table;   /* [n] float*; NULL = no moving average */
+  const void* blockmap;    /* [n_blocks] (tensor, chunk) */
+  const float* hyper;      /* device scalars, 6 floats or 8 with an ema_table; NULL = the host scalars below */
+  const float* record;     /* cy_grad_clip_finish's record[4]; NULL = no clipping / guard */
+  int n_blocks, chunk;
+  float lr, beta1, beta2, eps, bias_corr1, bias_corr2, one_minus_decay;   /* read only when hyper == NULL */
+} cy_adam_step_t;
+int cy_adam_step(const cy_adam_step_t* a, void* stream);
 
 /* Gradient-norm clipping and the non-finite-step guard of optim.Adam, decided on the device (csrc/gradnorm.hip).  The rule, over
  * every gradient G that one optimizer step applies:
@@ -835,37 +858,10 @@ int cy_adam_multi_dev(const void* table, const void* blockmap, int n_blocks, int
  * cy_grad_sumsq_multi takes Adam's table and block map (above) and writes partial[b], b < n_blocks, one workgroup per entry; the
  * launches of one step fill consecutive slices of one partial buffer.  Gradients may start at any 4-byte offset.
  * cy_grad_clip_finish adds the n_partial partials in one workgroup and writes record[4] = {total_norm, coef, go, 0}; with go == 0 it
- * also adds 1 to *skipped.
- * The two _clip steps are cy_adam_multi / cy_adam_multi_dev with coef * g in the place of g (the gradient tensors are not
- * rewritten); with record[2] == 0 they return without touching any parameter, exp_avg or exp_avg_sq.  coef == 1 gives the bits of
- * the plain step. */
+ * also adds 1 to *skipped.  cy_adam_step reads the record. */
 int cy_grad_sumsq_multi(const void* table, const void* blockmap, int n_blocks, int chunk, double* partial, void* stream);
 int cy_grad_clip_finish(const double* partial, int n_partial, float max_norm /* <= 0: no clipping */, int guard,
                         float* record /* [4] = {total_norm, coef, go (1 | 0), 0} */, long long* skipped, void* stream);
-int cy_adam_multi_clip(const void* table, const void* blockmap, int n_blocks, int chunk, float lr, float beta1, float beta2,
-                       float eps, float bias_corr1, float bias_corr2, const float* record, void* stream);
-int cy_adam_multi_dev_clip(const void* table, const void* blockmap, int n_blocks, int chunk, const float* hyper,
-                           const float* record, void* stream);
-
-/* An exponential moving average (EMA) of the parameters, kept inside the Adam launch (optim.Adam(ema_decay=...)).  The four steps
- * above, each with one more pass per element after the parameter has its new value p:
- *   ema += one_minus_decay * (p - ema)            (= decay * ema + (1 - decay) * p)
- * ema_table: device array of n_tensors float*, ema_table[k] the average of the parameter of table[k] (same numel, fp32, no overlap
- * with any tensor of table); table and blockmap are those of cy_adam_multi, whose record layout does not change.
- * one_minus_decay = 1 - decay, formed in double by the caller and rounded ONCE to fp32 (in (0, 1]); the kernels never form
- * 1.f - decay.  The _dev variants read it from hyper[6]: with an EMA hyper holds 8 floats {lr, beta1, beta2, eps, bias_corr1,
- * bias_corr2, one_minus_decay, 0}, so a captured step can follow a decay schedule.
- * Parameters, exp_avg and exp_avg_sq get the bits of the step without the average.  In the _clip variants record[2] == 0 returns
- * before anything is read or written: a skipped step changes no bit of an average.  36 bytes per element against 28. */
-int cy_adam_multi_ema(const void* table, const void* ema_table, const void* blockmap, int n_blocks, int chunk, float lr, float beta1,
-                      float beta2, float eps, float bias_corr1, float bias_corr2, float one_minus_decay, void* stream);
-int cy_adam_multi_dev_ema(const void* table, const void* ema_table, const void* blockmap, int n_blocks, int chunk,
-                          const float* hyper /* [8] */, void* stream);
-int cy_adam_multi_clip_ema(const void* table, const void* ema_table, const void* blockmap, int n_blocks, int chunk, float lr,
-                           float beta1, float beta2, float eps, float bias_corr1, float bias_corr2, float one_minus_decay,
-                           const float* record, void* stream);
-int cy_adam_multi_dev_clip_ema(const void* table, const void* ema_table, const void* blockmap, int n_blocks, int chunk,
-                               const float* hyper /* [8] */, const float* record, void* stream);
 
 #ifdef __cplusplus
 }

@@ -182,7 +182,7 @@ def test_cabi_declares_and_binds_the_new_entry_points():
     for name in ('cy_conv_image_grad', 'cy_conv_image_grad_ok', 'cy_attack_step', 'cy_grad_saliency_u8'):
         assert re.search(r'\b%s\s*\(' % name, header)
         assert name in _lib.EXPORTS and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 5 and lib.capsyolo_abi_version() == 5      # additions only
+    assert _lib.ABI_VERSION == 6 and lib.capsyolo_abi_version() == 6
     assert _lib.query('cy_conv_image_grad_ok', 1024, 32, 32, 256, 9, 0) == 1
     assert _lib.query('cy_conv_image_grad_ok', 2, 32, 32, 64, 4, 1) == 0
 

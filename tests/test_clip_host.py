@@ -1,4 +1,4 @@
-"""CPU-side tests of optim.Adam's gradient-norm clipping and non-finite guard (csrc/gradnorm.hip, the _clip kernels of csrc/adam.hip):
+"""CPU-side tests of optim.Adam's gradient-norm clipping and non-finite guard (csrc/gradnorm.hip, cy_adam_step's record in csrc/adam.hip):
 the C ABI, the constructor's argument checks, the unchanged state_dict, main.py's options, and the float64 reference of the GPU tests
 (tests/clip_ref.py) against an independent restatement of the rule on the recipe those tests use."""
 import importlib.util
@@ -18,7 +18,7 @@ from capsyolo_amd import _lib, optim
 import clip_ref
 import test_gpu_adam as A
 
-NEW = {'cy_grad_sumsq_multi': 6, 'cy_grad_clip_finish': 7, 'cy_adam_multi_clip': 12, 'cy_adam_multi_dev_clip': 7}
+NEW = {'cy_grad_sumsq_multi': 6, 'cy_grad_clip_finish': 7, 'cy_adam_step': 2}     # (the step that reads the record: tests/test_adam_step_host.py)
 
 
 def test_the_four_exports():
@@ -31,7 +31,7 @@ def test_the_four_exports():
         assert len(args.split(',')) == n_args, name
         assert name in _lib.EXPORTS and hasattr(lib, name)
         assert len(_lib._SIGS[name]) == n_args, name
-    assert lib.capsyolo_abi_version() == _lib.ABI_VERSION == 5            # additions only
+    assert lib.capsyolo_abi_version() == _lib.ABI_VERSION == 6
 
 
 @pytest.mark.parametrize('v', [0, -1, float('inf'), float('nan')])

@@ -1,4 +1,4 @@
-"""CPU-side tests of optim.Adam's moving average of the parameters (the _ema kernels of csrc/adam.hip): the constructor's argument checks,
+"""CPU-side tests of optim.Adam's moving average of the parameters (cy_adam_step's ema_table in csrc/adam.hip): the constructor's argument checks,
 the decay schedule, step_scalars, the unchanged state_dict, the C ABI, main.py's options, and the float64 reference of the GPU tests
 (tests/ema_ref.py) against closed forms and on the recipe those tests use."""
 import importlib.util
@@ -19,23 +19,21 @@ from capsyolo_amd import _lib, optim
 import ema_ref
 import test_gpu_adam as A
 
-NEW = {'cy_adam_multi_ema': 13, 'cy_adam_multi_dev_ema': 7, 'cy_adam_multi_clip_ema': 14, 'cy_adam_multi_dev_clip_ema': 8}
-
-
 def test_the_four_exports():
+    """The four steps with the average are cy_adam_step with an ema_table: one entry point of two arguments, whose descriptor carries
+    ema_table and one_minus_decay (its field order: test_host_logic.test_ctypes_structs_match_header_field_order; that the eight
+    entry points it replaced are gone: tests/test_adam_step_host.py)."""
     header = open(os.path.join(REPO, 'include', 'capsyolo_hip.h')).read()
     lib = _lib.load()
-    for name, n_args in NEW.items():
-        decl = re.search(r'\bint %s\(([^;]*)\);' % name, header, re.S)
-        assert decl, '%s is not declared in capsyolo_hip.h' % name
-        args = re.sub(r'/\*.*?\*/', '', decl.group(1), flags=re.S)
-        assert len(args.split(',')) == n_args, name
-        assert 'ema_table' in args
-        assert name in _lib.EXPORTS and hasattr(lib, name)
-        assert len(_lib._SIGS[name]) == n_args, name
-    # the four steps without the average keep their signatures
-    assert [len(_lib._SIGS[n]) for n in ('cy_adam_multi', 'cy_adam_multi_dev', 'cy_adam_multi_clip', 'cy_adam_multi_dev_clip')] == [11, 6, 12, 7]
-    assert lib.capsyolo_abi_version() == _lib.ABI_VERSION == 5            # additions only
+    decl = re.search(r'\bint cy_adam_step\(([^;]*)\);', header, re.S)
+    assert decl, 'cy_adam_step is not declared in capsyolo_hip.h'
+    args = re.sub(r'/\*.*?\*/', '', decl.group(1), flags=re.S)
+    assert len(args.split(',')) == 2 and 'cy_adam_step_t' in args
+    assert 'cy_adam_step' in _lib.EXPORTS and hasattr(lib, 'cy_adam_step') and len(_lib._SIGS['cy_adam_step']) == 2
+    body = re.search(r'typedef struct \{([^{}]*)\}\s*cy_adam_step_t;', header, re.S).group(1)
+    assert 'ema_table' in body and 'one_minus_decay' in body
+    assert set(['ema_table', 'one_minus_decay']) <= set(f[0] for f in _lib.AdamStep._fields_)
+    assert lib.capsyolo_abi_version() == _lib.ABI_VERSION == 6
 
 
 @pytest.mark.parametrize('v', [True, False, 0, 1, 0.0, 1.0, -0.5, 1.5, float('inf'), float('nan'), '0.9', (0.9,)])

@@ -1,4 +1,4 @@
-"""GPU tests of csrc/adam.hip behind capsyolo_amd.optim.Adam: both kernels (cy_adam_multi, and cy_adam_multi_dev with its scalars
+"""GPU tests of csrc/adam.hip behind capsyolo_amd.optim.Adam: both kernels (cy_adam_step, and cy_adam_step+dev with its scalars
 in device memory, otherwise reached through a captured graph only) against torch.optim.Adam on float64 CPU copies, over tensor
 sizes around the 16384-element chunk, two parameter groups, hyper-parameters other than the defaults, a learning rate that changes,
 gradients with exact zeros and a parameter that has no gradient in some steps; and optimizer checkpoints in both directions.
@@ -105,7 +105,7 @@ def test_two_groups_thirty_steps():
 
 @pytest.mark.parametrize('gi', [0, 1])
 def test_device_scalar_kernel_without_a_capture(gi):
-    """cy_adam_multi_dev with the tables and scalars that graph_step.GraphedStep gives it, launched eagerly.  One group and a gradient
+    """cy_adam_step+dev with the tables and scalars that graph_step.GraphedStep gives it, launched eagerly.  One group and a gradient
     for every parameter in every step: a captured step has one block map and a fixed set of parameters by design (optim.Adam refuses
     anything else on this path).  The device is synchronised after every step because this test rewrites the ONE pinned table per
     step that a capture reads once."""

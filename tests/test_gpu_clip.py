@@ -1,5 +1,5 @@
 """GPU tests of optim.Adam's gradient-norm clipping and non-finite guard: csrc/gradnorm.hip (cy_grad_sumsq_multi, cy_grad_clip_finish) and the
-two _clip kernels of csrc/adam.hip, against tests/clip_ref.py (clip_grad_norm_ + torch.optim.Adam in float64 on the CPU; checked against the
+two Adam steps that read its record (cy_adam_step of csrc/adam.hip, host or device scalars), against tests/clip_ref.py (clip_grad_norm_ + torch.optim.Adam in float64 on the CPU; checked against the
 written-out rule in tests/test_clip_host.py).  The recipe is clip_ref's: the 8 tensors of tests/test_gpu_adam.py, max_norm = 1.0, gradients that
 clip on even steps and do not on odd ones.  Parameters, exp_avg and exp_avg_sq are held to test_gpu_adam.py's rule (rtol 1e-5, atol 1e-6).
 
@@ -111,7 +111,7 @@ def test_norm_against_float64(layout):
 
 
 def test_clipped_steps_two_groups():
-    """10 steps of the recipe through cy_adam_multi_clip: two groups (ONE norm over both, three Adam launches in the steps where parameter
+    """10 steps of the recipe through cy_adam_step+clip: two groups (ONE norm over both, three Adam launches in the steps where parameter
     2 lags), even steps clipped.  p.grad keeps its bits.  Measured on the MI355X: largest error / tolerance 0.56 on the parameters (the fp32
     1 - beta2 of DESIGN.md section 6n, as in test_gpu_adam.py), 8e-4 on exp_avg, 1e-5 on exp_avg_sq."""
     ref, hip, o_ref, o_hip = _two_groups(clip_ref.MAX_NORM, False)
@@ -132,7 +132,7 @@ def test_clipped_steps_two_groups():
 
 @pytest.mark.parametrize('gi', [0, 1])
 def test_clipped_steps_device_scalar_kernel(gi):
-    """The same through cy_adam_multi_dev_clip, launched eagerly with the tables and scalars of graph_step.GraphedStep as
+    """The same through cy_adam_step+dev+clip, launched eagerly with the tables and scalars of graph_step.GraphedStep as
     test_gpu_adam.test_device_scalar_kernel_without_a_capture does (one group, a gradient for every parameter: the captured path
     refuses anything else).  Measured on the MI355X: largest error / tolerance 0.58 / 7e-4 / 6e-6 (parameters / exp_avg /
     exp_avg_sq) with the default betas, 0.04 / 6e-4 / 8e-6 with betas (0.5, 0.9)."""
@@ -160,12 +160,12 @@ def test_clipped_steps_device_scalar_kernel(gi):
     A._compare('clipped, device scalars, group %d' % gi, ref, hip, o_ref, o_hip)
 
 
-@pytest.mark.parametrize('kernel', ['cy_adam_multi_clip', 'cy_adam_multi_dev_clip'])
+@pytest.mark.parametrize('kernel', ['cy_adam_step+clip', 'cy_adam_step+dev+clip'])
 def test_inactive_clipping_is_the_plain_step(kernel):
     """max_grad_norm = 1e30 never clips (coef is exactly 1.0f): parameters, exp_avg and exp_avg_sq of 5 steps have the bits of an Adam without
     the option, for both kernels."""
     from capsyolo_amd import _lib
-    dev = kernel.endswith('dev_clip')
+    dev = kernel.endswith('dev+clip')
     _, plain = A._params(range(8))
     _, clip = A._params(range(8))
     o_plain, o_clip = optim.Adam(plain, **A.GROUPS[1]), optim.Adam(clip, max_grad_norm=1e30, **A.GROUPS[1])

@@ -1,4 +1,4 @@
-"""GPU tests of optim.Adam's moving average of the parameters: the four _ema kernels of csrc/adam.hip (host or device scalars x clip record or
+"""GPU tests of optim.Adam's moving average of the parameters: the four steps of cy_adam_step with an ema_table (csrc/adam.hip; host or device scalars x clip record or
 none) against tests/ema_ref.py (the rule in float64 on the CPU around clip_ref.ClipRef; checked against closed forms in
 tests/test_ema_host.py), the exchange `with opt.ema_weights()`, checkpoints, the captured step and main.py's options.  The recipe is
 ema_ref's: the 8 tensors of tests/test_gpu_adam.py (sizes around the 16384-element chunk), two groups, 30 steps, the learning rate cut
@@ -143,14 +143,14 @@ def test_the_step_is_undisturbed(dev, clip):
     """For each of the four kernel pairs: parameters, exp_avg and exp_avg_sq after 30 steps with ema_decay = 0.999 have the bits of the run
     with ema_decay = None, the run with the average goes through the _ema entry point and the run without it through the entry point
     it always went through; without the option no EMA tensor or table exists."""
-    name = 'cy_adam_multi' + ('_dev' if dev else '') + ('_clip' if clip else '')
+    name = 'cy_adam_step' + ('+dev' if dev else '') + ('+clip' if clip else '')
     p_off, o_off, tr_off = _thirty_steps(dev, clip, None)
     p_on, o_on, tr_on = _thirty_steps(dev, clip, 0.999)
     n_first = 1 if dev else 0                                            # the eager first step of the device-scalar runs
-    launches = sum(1 for n in tr_off if n.startswith('cy_adam_multi'))
+    launches = sum(1 for n in tr_off if n.startswith('cy_adam_step'))
     assert launches == (30 if dev else 2 * 30 + 20)                      # two groups, and a third launch in parameter 2's 20 steps (it lags)
-    assert tr_off.count(name) == launches - n_first and tr_on.count(name + '_ema') == launches - n_first
-    assert not any(n.endswith('_ema') for n in tr_off) and [n.replace('_ema', '') for n in tr_on] == tr_off
+    assert tr_off.count(name) == launches - n_first and tr_on.count(name + '+ema') == launches - n_first
+    assert not any(n.endswith('+ema') for n in tr_off) and [n.replace('+ema', '') for n in tr_on] == tr_off
     assert o_off.ema == {} and getattr(o_off, '_ema_table_dev', None) is None and getattr(o_off, '_ema_ring', None) is None
     # (parameter 0 is one element whose gradient is the recipe's exact zero: it never moves, and neither does its average)
     assert set(o_on.ema) == set(p_on) and all(not torch.equal(o_on.ema[p], p) for p in p_on[1:]) and torch.equal(o_on.ema[p_on[0]], p_on[0])
@@ -161,7 +161,7 @@ def test_the_step_is_undisturbed(dev, clip):
 # ------------------------------------------------------------------------------------------------ 2. the average is right
 @pytest.mark.parametrize('decay,warmup', CONFIGS)
 def test_the_average_against_float64(decay, warmup):
-    """The averages of the 8 tensors against ema_ref at steps 10 and 30 (cy_adam_multi_ema, two groups, parameter 2 lagging).
+    """The averages of the 8 tensors against ema_ref at steps 10 and 30 (cy_adam_step+ema, two groups, parameter 2 lagging).
     Measured on the MI355X (largest error / tolerance over the 8 tensors, step 10 / step 30): 0.25 / 0.55 (0.9), 0.51 / 0.56 (0.9 with the
     warm-up), 0.04 / 0.06 (0.999), 0.51 / 0.56 (0.999 with the warm-up); the parameters themselves 0.56 / 0.56 (the fp32 1 - beta2 of
     DESIGN.md section 6n)."""
@@ -244,7 +244,7 @@ def test_a_parameter_without_a_gradient_keeps_its_average():
 
 # ------------------------------------------------------------------------------------------------ 4. skip
 def test_a_skipped_step_moves_no_average():
-    """skip_nonfinite with one gradient element inf in step 5 and one NaN in step 11 (cy_adam_multi_clip_ema: record[2] == 0 returns before
+    """skip_nonfinite with one gradient element inf in step 5 and one NaN in step 11 (cy_adam_step+clip+ema: record[2] == 0 returns before
     anything is read or written): every average, parameter, exp_avg and exp_avg_sq keeps its bits across the two steps, skipped counts 2,
     and averages and state after 30 steps are the reference's.  Measured on the MI355X: averages 0.47 of the tolerance, parameters /
     exp_avg / exp_avg_sq 0.53 / 0.13 / 0.51."""
@@ -389,7 +389,7 @@ def test_checkpoint_round_trip(tmp_path):
 # ------------------------------------------------------------------------------------------------ 7. captured step
 def test_graphed_step_keeps_the_average():
     """A CapsuleNet step on 8 synthetic samples (32 x 32, reconstruction on) with ema_decay = 0.9 and the warm-up, captured
-    (cy_adam_multi_dev_ema, eight scalars) and replayed 6 times against 6 eager steps from the same start.  The three warm-up steps of the
+    (cy_adam_step+dev+ema, eight scalars) and replayed 6 times against 6 eager steps from the same start.  The three warm-up steps of the
     capture are rolled back: every average equals its parameter afterwards.  The decay of replay t is (1 + t) / (10 + t): it can only
     have come from device memory (the capture froze every kernel argument), and hyper[6] holds 1 - 7/16 after the sixth.
 
@@ -416,9 +416,9 @@ def test_graphed_step_keeps_the_average():
     _lib.TRACE = trace = []
     try:
         step = GraphedStep(net_g, fwd, opt_g, (xs[0], ys[0]), warmup=3)
-        captured = [n for n in trace if n.startswith('cy_adam_multi')]
+        captured = [n for n in trace if n.startswith('cy_adam_step')]
         del trace[:]
-        assert captured == ['cy_adam_multi_ema'] * 3 + ['cy_adam_multi_dev_ema']
+        assert captured == ['cy_adam_step+ema'] * 3 + ['cy_adam_step+dev+ema']
         assert set(opt_g.ema) == set(pg) and all(torch.equal(opt_g.ema[q], q) and opt_g.ema[q].data_ptr() != q.data_ptr() for q in pg)
         for (n, a), (_, b) in zip(net_g.state_dict().items(), net_e.state_dict().items()):
             assert torch.equal(a, b), n
@@ -428,8 +428,8 @@ def test_graphed_step_keeps_the_average():
             l.backward()
             opt_e.step()
             step(x, y)
-        assert not any(n.startswith('cy_adam_multi') and n != 'cy_adam_multi_ema' for n in trace)       # the replays call nothing
-        assert trace.count('cy_adam_multi_ema') == 6
+        assert not any(n.startswith('cy_adam_step') and n != 'cy_adam_step+ema' for n in trace)       # the replays call nothing
+        assert trace.count('cy_adam_step+ema') == 6
     finally:
         _lib.TRACE = None
     torch.cuda.synchronize()

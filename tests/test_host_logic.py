@@ -27,13 +27,14 @@ def test_cabi_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), 'libcapsyolo_hip.so does not export %s' % name
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
-    assert lib.capsyolo_abi_version() == _lib.ABI_VERSION == 5
+    assert lib.capsyolo_abi_version() == _lib.ABI_VERSION == 6
 
 
 def test_ctypes_structs_match_header_field_order():
     header = open(os.path.join(REPO, 'include', 'capsyolo_hip.h')).read()
     for cname, struct in (('cy_conv_gemm_t', _lib.ConvGemm), ('cy_conv_wgrad_t', _lib.ConvWgrad),
-                          ('cy_routing_fwd_t', _lib.RoutingFwd), ('cy_routing_bwd_t', _lib.RoutingBwd)):
+                          ('cy_routing_fwd_t', _lib.RoutingFwd), ('cy_routing_bwd_t', _lib.RoutingBwd),
+                          ('cy_adam_step_t', _lib.AdamStep)):
         body = re.search(r'typedef struct \{([^{}]*)\}\s*%s;' % cname, header, re.S).group(1)
         body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
         fields = []

@@ -131,7 +131,7 @@ def test_cabi_declares_and_binds_the_decoder():
     assert re.search(r'\bcy_decoder_fwd\s*\(', header)
     assert 'cy_decoder_fwd' in _lib.EXPORTS and hasattr(lib, 'cy_decoder_fwd')
     assert len(_lib._SIGS['cy_decoder_fwd']) == 2
-    assert _lib.ABI_VERSION == 5 and lib.capsyolo_abi_version() == 5
+    assert _lib.ABI_VERSION == 6 and lib.capsyolo_abi_version() == 6
 
 
 def test_decoder_struct_matches_header_field_order():

@@ -41,7 +41,7 @@ def test_share_rule_without_a_device():
         assert name in _lib.EXPORTS and hasattr(_lib.load(), name)
     header = open(os.path.join(REPO, 'include', 'capsyolo_hip.h')).read()
     assert 'cy_linear_fwd_ws_floats' in header and 'cy_softmax_xent' in header
-    assert _lib.load().capsyolo_abi_version() == 5                       # additions only
+    assert _lib.load().capsyolo_abi_version() == 6
 
 
 def test_refusals_before_any_launch():

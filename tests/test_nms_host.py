@@ -24,7 +24,7 @@ def test_entry_points_are_declared_and_exported():
         assert re.search(r'\bint %s\(' % name, header)
         assert name in _lib.EXPORTS and hasattr(lib, name)
     assert 'cy_nms_boxes' in _lib._SIGS and len(_lib._SIGS['cy_nms_boxes']) == len(ARGS) + 1
-    assert _lib.ABI_VERSION == 5 and lib.capsyolo_abi_version() == 5
+    assert _lib.ABI_VERSION == 6 and lib.capsyolo_abi_version() == 6
     # 48 bytes of LDS per box: 160 KiB hold 3413 of them, far more than the 722 of a 19 x 19 grid with two boxes per cell
     assert _lib.query('cy_nms_max_per_image') == (160 * 1024) // 48 == 3413
 

@@ -90,4 +90,4 @@ def test_new_entry_points_are_exported():
     lib = _lib.load()
     for name in ('cy_crop_resize_u8', 'cy_combine_scores', 'cy_yolo_decode_boxes_conf', 'cy_confusion_sweep'):
         assert name in _lib.EXPORTS and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 5
+    assert _lib.ABI_VERSION == 6

@@ -80,7 +80,7 @@ def test_cabi_declares_and_binds_the_rank_counts():
         assert re.search(r'\b%s\s*\(' % name, header)
         assert name in _lib.EXPORTS and hasattr(lib, name)
     assert len(_lib._SIGS['cy_rank_counts']) == 10
-    assert _lib.ABI_VERSION == 5 and lib.capsyolo_abi_version() == 5
+    assert _lib.ABI_VERSION == 6 and lib.capsyolo_abi_version() == 6
 
 
 def test_rank_counts_refuses_what_does_not_fit_int32():

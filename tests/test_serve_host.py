@@ -22,7 +22,7 @@ def test_entry_points_are_declared_and_exported():
     for name in NAMES:
         assert re.search(r'\bint %s\(' % name, header)
         assert name in _lib.EXPORTS and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 5 and lib.capsyolo_abi_version() == 5
+    assert _lib.ABI_VERSION == 6 and lib.capsyolo_abi_version() == 6
 
 
 def _crop_args(**kw):

@@ -26,7 +26,7 @@ def test_entry_points_are_declared_and_exported():
     for struct in ('cy_tracks_header_t', 'cy_track_t'):
         assert re.search(r'\}\s*%s;' % struct, header)
     assert 'cy_track_update' in _lib._SIGS and len(_lib._SIGS['cy_track_update']) == len(ARGS) + 1
-    assert _lib.ABI_VERSION == 5 and lib.capsyolo_abi_version() == 5
+    assert _lib.ABI_VERSION == 6 and lib.capsyolo_abi_version() == 6
     # 8 bytes a pair: 4096 pairs are 32 KiB of the 48 KiB a launch gets without opting in
     assert _lib.query('cy_track_max_pairs') == 4096
     q = lambda T, C: _lib.query('cy_track_state_bytes', T, C)            # noqa: E731
