@@ -143,6 +143,7 @@ _SIGS = {
     'cy_boxes_crop_resize_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P],
     'cy_pack_detections': [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     'cy_nms_boxes': [_P, _P, _P, _P, _P, _I, _I, C.c_double, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    'cy_yolo_decode_tiles_conf': [_P, _P, _P, _P, _I, C.c_double, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     'cy_track_update': [_P, _P, _P, _P, _P, _I, _I, _I, C.c_double, _I, _I, _F, _I, _P, _P, _P],
     'cy_draw_boxes_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _I, _P, _P, _P],
     'cy_paste_resize_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _I, _L, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P],

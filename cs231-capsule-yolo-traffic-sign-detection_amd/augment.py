@@ -187,19 +187,48 @@ def paste_resize_device(frames, bank, sample_img, sample_rect, begin, pastes, oh
     return into
 
 
-def plan_batch(frame_idx, hw, boxes, bank, add_signs, seed, iteration, side, n_grid, n_classes):
+def window_labels(boxes_xy, classes, window, side, n_grid, n_classes, min_visible=0.6):
+    """float64 [g, g, 5 + C]: the labels of one window (y0, y1, x0, x1), half-open, of a frame whose boxes are boxes_xy [k, 4] =
+    (x1, y1, x2, y2) in frame pixels -- what a detector trained on the windows of a tiling (tiles.tile_rects) is to answer.  A box is
+    labelled iff at least min_visible of its area lies inside the window; its label is the box clipped to the window, relative to
+    the window's origin, through label_grid with the window's size as the image (skip_conflicts=False, as for every augmented
+    sample).  A box without area is never labelled."""
+    y0, y1, x0, x1 = (float(v) for v in window)
+    kept, kept_classes = [], []
+    for k, (bx1, by1, bx2, by2) in enumerate(np.asarray(boxes_xy, dtype=np.float64).reshape(-1, 4)):
+        cx1, cy1, cx2, cy2 = max(bx1, x0), max(by1, y0), min(bx2, x1), min(by2, y1)
+        area = (bx2 - bx1) * (by2 - by1)
+        if not (area > 0 and cx2 > cx1 and cy2 > cy1):
+            continue
+        if (cx2 - cx1) * (cy2 - cy1) >= float(min_visible) * area:
+            kept.append([cx1 - x0, cy1 - y0, cx2 - x0, cy2 - y0])
+            kept_classes.append(classes[k] if n_classes else 0)
+    return label_grid(np.array(kept, dtype=np.float64).reshape(-1, 4), kept_classes, (y1 - y0, x1 - x0), side, n_grid, n_classes,
+                      skip_conflicts=False)
+
+
+def plan_batch(frame_idx, hw, boxes, bank, add_signs, seed, iteration, side, n_grid, n_classes, tiles=None):
     """The plan of one batch of augmented samples.  frame_idx [n]: the numbers of the frames in the whole set, which seed the samples;
     hw [n, 2] and boxes (n arrays [k, 5]: x1, y1, x2, y2, class) belong to them in the same order.
+    tiles (a tiles.TileSpec): every sample is ONE window of its frame's tile table, drawn after all paste draws of the sample -- so
+    the pastes of a sample are the same with and without tiles -- and labelled by window_labels.  None: the whole frame, no draw.
     Returns (sample_rect [n, 4], begin [n + 1], pastes [k, 9], y float64 [n, g, g, 5 + C])."""
-    begin, rows, ys = [0], [], []
+    begin, rows, ys, rects = [0], [], [], []
     for k, f in enumerate(frame_idx):
         b = np.asarray(boxes[k], dtype=np.float64).reshape(-1, 5)
-        r, bx, cl = plan_pastes(sample_rng(seed, f, iteration), b[:, 0:4], hw[k], bank, add_signs)
+        rng = sample_rng(seed, f, iteration)
+        r, bx, cl = plan_pastes(rng, b[:, 0:4], hw[k], bank, add_signs)
         rows.append(r)
         begin.append(begin[-1] + len(r))
-        ys.append(label_grid(bx, cl, hw[k], side, n_grid, n_classes, skip_conflicts=False))
+        if tiles is None:
+            ys.append(label_grid(bx, cl, hw[k], side, n_grid, n_classes, skip_conflicts=False))
+        else:
+            table = tiles.rects(int(hw[k][0]), int(hw[k][1]))
+            rects.append(table[int(rng.integers(0, len(table)))])
+            ys.append(window_labels(bx, cl, rects[-1], side, n_grid, n_classes))
     pastes = np.concatenate(rows) if rows else np.zeros((0, 9), np.int32)
-    return full_rects(hw), np.array(begin, np.int32), pastes, np.stack(ys)
+    sample_rect = full_rects(hw) if tiles is None else np.array(rects, dtype=np.int64).reshape(-1, 4)
+    return sample_rect, np.array(begin, np.int32), pastes, np.stack(ys)
 
 
 class AugmentFeeder(object):
@@ -208,9 +237,11 @@ class AugmentFeeder(object):
     frame numbers into `frames` (a predict_fns.PackedImages of the raw frames, resident on the device) and `boxes` (per frame a
     [k, 5] array x1, y1, x2, y2, class).  Per batch: the plan on the host, one upload of it, one launch.  Sample f of this feeder
     is seeded by (seed, f, iteration) with iteration = epoch * aug_stride + k, so every epoch sees new pastes and a given
-    (seed, epoch) repeats exactly, whatever the batching or the number of ranks."""
+    (seed, epoch) repeats exactly, whatever the batching or the number of ranks.
+    tiles (a tiles.TileSpec): every sample is one randomly drawn window of its frame's tile table instead of the whole frame
+    (plan_batch), so a detector can be trained on what serve.SignDetector(tiles=) will show it."""
 
-    def __init__(self, frames, boxes, bank, batches, side, n_grid, n_classes, add_signs=0, seed=0, epoch=0, aug_stride=1, k=0):
+    def __init__(self, frames, boxes, bank, batches, side, n_grid, n_classes, add_signs=0, seed=0, epoch=0, aug_stride=1, k=0, tiles=None):
         if not torch.cuda.is_available():
             from ._lib import HipExtensionError
             raise HipExtensionError('AugmentFeeder needs a GPU: the product path has no CPU fallback')
@@ -218,11 +249,12 @@ class AugmentFeeder(object):
         self.batches = [np.asarray(b, dtype=np.int64).reshape(-1) for b in batches]
         self.side, self.n_grid, self.n_classes, self.add_signs = int(side), int(n_grid), int(n_classes), int(add_signs)
         self.seed, self.iteration = int(seed), int(epoch) * int(aug_stride) + int(k)
+        self.tiles = tiles
 
     def plan(self, frame_idx):
         idx = np.asarray(frame_idx, dtype=np.int64).reshape(-1)
         return plan_batch(idx, self.frames.hw[idx], [self.boxes[i] for i in idx], self.bank, self.add_signs, self.seed,
-                          self.iteration, self.side, self.n_grid, self.n_classes)
+                          self.iteration, self.side, self.n_grid, self.n_classes, self.tiles)
 
     def __len__(self):
         return len(self.batches)
@@ -239,17 +271,18 @@ class AugmentSource(object):
     """What `main.py --augment` keeps between the epochs: the raw frames packed on the device, their boxes, the bank, and the epoch
     count.  feeder(batches) is the AugmentFeeder of the next epoch."""
 
-    def __init__(self, frames, boxes, bank, side, n_grid, n_classes, add_signs, seed, device='cuda'):
+    def __init__(self, frames, boxes, bank, side, n_grid, n_classes, add_signs, seed, device='cuda', tiles=None):
         from .predict_fns import PackedImages
         self.frames = PackedImages(frames, device)
         self.boxes = [np.asarray(b, dtype=np.float64).reshape(-1, 5) for b in boxes]
         if len(self.boxes) != self.frames.n:
             raise ValueError('AugmentSource: %d frames, %d box arrays' % (self.frames.n, len(self.boxes)))
         self.bank, self.args, self.seed, self.epoch = bank, (side, n_grid, n_classes, add_signs), seed, 0
+        self.tiles = tiles
         bank.packed(device)
 
     def feeder(self, batches):
-        f = AugmentFeeder(self.frames, self.boxes, self.bank, batches, *self.args, seed=self.seed, epoch=self.epoch)
+        f = AugmentFeeder(self.frames, self.boxes, self.bank, batches, *self.args, seed=self.seed, epoch=self.epoch, tiles=self.tiles)
         self.epoch += 1
         return f
 

@@ -209,47 +209,79 @@ def _as_device_f32(a):
     return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).to(device='cuda', dtype=torch.float32).contiguous()
 
 
-def confusion_sweep(y, y_hat, params, conf_ths, iou_ths, per_class=True):
-    """(TP, FP, FN) of metrics.single_img_confusion summed over the images for EVERY confidence threshold, class and IoU
-    threshold: int64 numpy [K][C or 1][T][3] (per_class=False: boxes are matched per image whatever their class, as in
-    detect_AP).  The reference decodes both arrays again for every confidence threshold (metrics.py:298-302); a pair's IoU does
-    not depend on it, so both are decoded once at min(conf_ths) with their confidences, sorted by image * C + class, and one
-    launch counts everything: a box is hit at (th, iou_t) iff min(its confidence, best partner confidence at iou_t) > th."""
-    C = int(params.n_classes)
-    if per_class and C <= 0:
-        raise ValueError('confusion_sweep(per_class=True) needs a classifying head (n_classes > 0)')
+def confusion_sweep_boxes(gt, pr, n_images, conf_ths, iou_ths, n_classes=0, max_per_group=None):
+    """The sweep of confusion_sweep over two BOX LISTS instead of two label arrays: gt and pr are (image_indices [n], boxes_xy [n, 4] =
+    (x1, y1, x2, y2), conf [n][, classes [n]]), arrays or tensors, both in the same pixels -- e.g. what utils.decode_boxes_device(...,
+    with_conf=True) or predict_fns.dark_pred_tiled returned.  int64 numpy [K][n_classes or 1][T][3] = (TP, FP, FN) summed over the
+    n_images images: a box counts at confidence threshold th iff (double)conf > th and is hit iff additionally a partner of its image
+    (n_classes > 0: and of its class, which both lists must then carry) with IoU > iou_t that also counts exists (`cy_confusion_sweep`).
+    max_per_group: boxes of one image (and class) the kernel has room for; default: the largest group of the two lists."""
+    C = int(n_classes)
     conf_ths = np.ascontiguousarray(np.asarray(conf_ths, dtype=np.float64).reshape(-1))
     iou_ths = np.ascontiguousarray(np.asarray(iou_ths, dtype=np.float64).reshape(-1))
     K, T = len(conf_ths), len(iou_ths)
     if K < 1 or T < 1:
         raise ValueError('confusion_sweep needs at least one confidence and one IoU threshold')
-    lo = np.float32(conf_ths.min())
-    if float(lo) > conf_ths.min():          # the decode compares in float: never start above the lowest threshold
-        lo = np.nextafter(lo, np.float32(-np.inf))
-    yt, ht = _as_device_f32(y), _as_device_f32(y_hat)
-    Cn = C if per_class else 1
+    if int(n_images) < 1:
+        raise ValueError('confusion_sweep_boxes: n_images must be >= 1, got %r' % (n_images,))
+    Cn = C if C > 0 else 1
+
+    def dev_t(a, dtype):
+        return torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).to(device='cuda', dtype=dtype).contiguous()
     sets = []
-    for arr in (yt, ht):
-        n, idx, xy, cls, conf = utils.decode_boxes_device(arr, params, None, float(lo), with_conf=True)
-        if n and per_class:
-            key, order = torch.sort(idx.long() * C + cls.long(), stable=True)
+    for name, boxes in (('gt', gt), ('pr', pr)):
+        if len(boxes) < (4 if C > 0 else 3) or (C > 0 and boxes[3] is None):
+            raise ValueError('confusion_sweep_boxes: %s must be (image_indices, boxes_xy, conf%s)' % (name, ', classes' if C > 0 else ''))
+        idx, xy, conf = dev_t(boxes[0], torch.int32).reshape(-1), dev_t(boxes[1], torch.float64).reshape(-1, 4), dev_t(boxes[2], torch.float32).reshape(-1)
+        n = int(idx.numel())
+        if int(xy.shape[0]) != n or int(conf.numel()) != n:
+            raise ValueError('confusion_sweep_boxes: %s has %d image indices, %d boxes, %d confidences' % (name, n, xy.shape[0], conf.numel()))
+        if n and C > 0:
+            cls = dev_t(boxes[3], torch.int64).reshape(-1)
+            key, order = torch.sort(idx.long() * C + cls, stable=True)
             idx, xy, conf = key.to(torch.int32).contiguous(), xy[order].contiguous(), conf[order].contiguous()
         sets.append((n, idx, xy, conf))
-    batch, g = int(yt.shape[0]), int(yt.shape[1])
-    nb_max = max((int(yt.shape[3]) - C) // 5, (int(ht.shape[3]) - C) // 5)
     (n1, gk, gxy, gcf), (n2, pk, pxy, pcf) = sets
+    if max_per_group is None:
+        max_per_group = max([1] + [int(torch.bincount(k.long()).max().item()) for n, k, _, _ in sets if n])
     ths = torch.from_numpy(np.concatenate([conf_ths, iou_ths])).cuda()
     out = torch.zeros(K * Cn * T * 3 + 1, dtype=torch.int32, device='cuda')          # the table, then the error word
     call('cy_confusion_sweep', gk.data_ptr() if n1 else None, gxy.data_ptr() if n1 else None, gcf.data_ptr() if n1 else None, n1,
          pk.data_ptr() if n2 else None, pxy.data_ptr() if n2 else None, pcf.data_ptr() if n2 else None, n2,
-         batch * Cn, Cn, ths.data_ptr(), K, ths.data_ptr() + 8 * K, T, g * g * nb_max,
+         int(n_images) * Cn, Cn, ths.data_ptr(), K, ths.data_ptr() + 8 * K, T, int(max_per_group),
          out.data_ptr(), out.data_ptr() + 4 * (K * Cn * T * 3), torch.cuda.current_stream().cuda_stream)
     host = out.cpu().numpy()
     if host[-1] >= 1 << 20:
-        raise RuntimeError('confusion_sweep: a group holds more than %d boxes' % (g * g * nb_max))
+        raise RuntimeError('confusion_sweep: a group holds more than %d boxes' % int(max_per_group))
     if host[-1]:
         raise AssertionError('malformed box (x1 > x2 or y1 > y2) in %d case(s)' % host[-1])
     return host[:-1].astype(np.int64).reshape(K, Cn, T, 3)
+
+
+def confusion_sweep(y, y_hat, params, conf_ths, iou_ths, per_class=True):
+    """(TP, FP, FN) of metrics.single_img_confusion summed over the images for EVERY confidence threshold, class and IoU
+    threshold: int64 numpy [K][C or 1][T][3] (per_class=False: boxes are matched per image whatever their class, as in
+    detect_AP).  The reference decodes both arrays again for every confidence threshold (metrics.py:298-302); a pair's IoU does
+    not depend on it, so both are decoded once at min(conf_ths) with their confidences, sorted by image * C + class, and one
+    launch counts everything: a box is hit at (th, iou_t) iff min(its confidence, best partner confidence at iou_t) > th.
+    The counting is confusion_sweep_boxes on the two decoded lists."""
+    C = int(params.n_classes)
+    if per_class and C <= 0:
+        raise ValueError('confusion_sweep(per_class=True) needs a classifying head (n_classes > 0)')
+    conf_ths = np.ascontiguousarray(np.asarray(conf_ths, dtype=np.float64).reshape(-1))
+    if len(conf_ths) < 1 or np.asarray(iou_ths).size < 1:
+        raise ValueError('confusion_sweep needs at least one confidence and one IoU threshold')
+    lo = np.float32(conf_ths.min())
+    if float(lo) > conf_ths.min():          # the decode compares in float: never start above the lowest threshold
+        lo = np.nextafter(lo, np.float32(-np.inf))
+    yt, ht = _as_device_f32(y), _as_device_f32(y_hat)
+    sets = []
+    for arr in (yt, ht):
+        n, idx, xy, cls, conf = utils.decode_boxes_device(arr, params, None, float(lo), with_conf=True)
+        sets.append((idx, xy, conf, cls))
+    batch, g = int(yt.shape[0]), int(yt.shape[1])
+    nb_max = max((int(yt.shape[3]) - C) // 5, (int(ht.shape[3]) - C) // 5)
+    return confusion_sweep_boxes(sets[0], sets[1], batch, conf_ths, iou_ths, C if per_class else 0, g * g * nb_max)
 
 
 def _ap_table(counts):
@@ -271,6 +303,15 @@ def detect_report(y, y_hat, params):
     launches 1000 times."""
     conf_ths, iou_ths = np.concatenate([np.linspace(0, 1, 100), [0.5]]), np.linspace(0.5, 0.95, 10)
     counts = confusion_sweep(y, y_hat, params, conf_ths, iou_ths, per_class=False)
+    p, r = precision_and_recall(*[int(v) for v in counts[100, 0, 0]])
+    return {'detect_AP': np.mean(_ap_table(counts[:100])[0]), 'detect_acc': 2 * p * r / (p + r + 1e-8)}
+
+
+def detect_report_boxes(gt, pr, n_images):
+    """detect_report for two box lists (image_indices, boxes_xy, conf) in the same pixels, e.g. the ground truth decoded with the
+    images' sizes and the merged list of predict_fns.dark_pred_tiled: the same keys, thresholds and folding."""
+    conf_ths, iou_ths = np.concatenate([np.linspace(0, 1, 100), [0.5]]), np.linspace(0.5, 0.95, 10)
+    counts = confusion_sweep_boxes(gt, pr, n_images, conf_ths, iou_ths)
     p, r = precision_and_recall(*[int(v) for v in counts[100, 0, 0]])
     return {'detect_AP': np.mean(_ap_table(counts[:100])[0]), 'detect_acc': 2 * p * r / (p + r + 1e-8)}
 

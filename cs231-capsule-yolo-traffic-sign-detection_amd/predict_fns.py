@@ -206,6 +206,61 @@ def dark_pred(images, model, model_dir, params, restore_file, is_end=True, conf_
     return y_hat.cpu().numpy(), crops.cpu().numpy(), idx, xy
 
 
+def dark_pred_tiled(images, model, model_dir, params, restore_file, tiles, nms_iou, conf_th=0.5, y=None, batch_size=32, draw=False,
+                    nms_class_aware=False):
+    """dark_pred with the detector run on the overlapping windows of every image (tiles: a tiles.TileSpec) instead of the image.
+    images: list of HWC uint8 arrays of different sizes; every image gets the tile table of its own size.  Per chunk of images: one
+    crop + resize of all windows, the eval forward on that batch, utils.decode_tiles_device at confidence > 0 (border rule, frame
+    pixels), utils.nms_boxes_device per image at nms_iou -- once: greedy suppression in descending confidence is prefix-consistent,
+    so the part of the merged list over ANY threshold is what suppressing the boxes over that threshold keeps, and one list serves
+    the drawing at conf_th and every threshold of metrics.detect_report_boxes.
+    Returns ((image_indices int64 [n], boxes_xy float64 [n, 4] in image pixels, conf float32 [n], classes int64 [n] | None), images):
+    the merged list as numpy arrays, image ascending and inside an image confidence descending, and with draw=True copies of the
+    images with the list's boxes over conf_th in green and, when the labels y are given, the ground truth in red (as dark_pred draws
+    them), else None."""
+    from ._lib import query
+    nms = _nms_option(nms_iou, nms_class_aware, params)
+    if nms is None:
+        raise ValueError('dark_pred_tiled needs nms_iou: overlapping windows see the same sign more than once by construction')
+    tiles.check_capacity(params.n_grid, params.n_boxes, query('cy_nms_max_per_image'))
+    _restore(model, model_dir, params, restore_file)
+    n = len(images)
+    bs = max(_chunk_size(n, batch_size) // tiles.n_tiles, 1)            # the detector's batch stays near batch_size tiles
+    side = int(params.darknet_input)
+    idxs, xys, confs, clss, drawn = [], [], [], [], []
+    model.eval()
+    with torch.no_grad():
+        for lo in range(0, n, bs):
+            packed = PackedImages(images[lo:lo + bs], params.device)
+            tables = [tiles.rects(int(h), int(w)) for h, w in packed.hw]
+            tile_idx = np.concatenate([np.full(len(t), k, np.int32) for k, t in enumerate(tables)])
+            tile_rect = np.concatenate(tables)
+            y_hat = model(packed.crop_resize(tile_idx, tile_rect, side, side, 0.0, 1.0, True)).data
+            _, idx, xy, cls, conf, _ = utils.decode_tiles_device(y_hat, params, tile_idx, tile_rect, packed.hw, 0.0, tiles.margin)
+            _, idx, xy, conf, cls, _, _ = utils.nms_boxes_device(idx, xy, conf, cls, nms[0], nms[1], 0, packed.n)
+            idx_np, xy_np, conf_np = idx.cpu().numpy().astype(np.int64), xy.cpu().numpy().reshape(-1, 4), conf.cpu().numpy()
+            cls_np = cls.cpu().numpy().astype(np.int64) if cls is not None else None
+            if draw:
+                over = conf_np > np.float32(conf_th)
+                d_idx, d_xy, d_cls = idx_np[over], xy_np[over], (cls_np[over] if cls_np is not None else None)
+                colors = np.tile(np.array(box_draw.GREEN, dtype=np.uint8), (len(d_idx), 1))
+                if y is not None:
+                    _, t_idx, t_xy, t_cls = utils.decode_boxes_device(y[lo:lo + packed.n], params, packed.hw, conf_th)
+                    d_idx = np.concatenate([d_idx, t_idx.cpu().numpy().astype(np.int64)])
+                    d_xy = np.concatenate([d_xy, t_xy.cpu().numpy().reshape(-1, 4)])
+                    if d_cls is not None:
+                        d_cls = np.concatenate([d_cls, t_cls.cpu().numpy().astype(np.int64)])
+                    colors = np.concatenate([colors, np.tile(np.array(box_draw.RED, dtype=np.uint8), (len(d_idx) - len(colors), 1))])
+                drawn.extend(box_draw.unpack_images(box_draw.draw_boxes_device(packed, d_idx, d_xy, colors, d_cls), packed))
+            idxs.append(idx_np + lo)
+            xys.append(xy_np)
+            confs.append(conf_np)
+            clss.append(cls_np)
+    merged = (np.concatenate(idxs), np.concatenate(xys, 0), np.concatenate(confs),
+              np.concatenate(clss) if int(params.n_classes) else None)
+    return merged, (drawn if draw else None)
+
+
 def dark_class_pred(images, dark_model, dark_model_dir, dark_params, class_model, class_model_dir, class_params, restore_file,
                     batch_size=32, conf_th=0.5, draw=False, nms_iou=None, nms_class_aware=False):
     """predict_fns.py:75-82: detector -> crop of every box -> classifier -> utils.combine_y_hat.  Returns (y_hat float64 numpy

@@ -23,6 +23,7 @@ import torch
 
 from . import ops
 from ._lib import HipExtensionError, call, query
+from .tiles import TileSpec
 
 # the record buffer of cy_pack_detections (include/capsyolo_hip.h): cy_detections_header_t, then max_boxes cy_detection_t
 HEADER_DTYPE = np.dtype([('total', '<i4'), ('kept', '<i4'), ('crop_err', '<i4'), ('resize_err', '<i4')])
@@ -177,7 +178,7 @@ class Detections(object):
 class _State(object):
     """Every buffer of the pipeline for frames of one shape (n, H, W): nothing is allocated per call."""
 
-    def __init__(self, n, H, W, side, ci, K, has_cls, dev):
+    def __init__(self, n, H, W, side, ci, K, has_cls, dev, tiles=None):
         nbytes = n * H * W * 3
         self.n, self.H, self.W, self.nbytes = n, H, W, nbytes
         self.staging = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
@@ -190,7 +191,14 @@ class _State(object):
         self.frame_idx = torch.arange(n, dtype=torch.int32).to(dev)
         self.frame_rect = torch.tensor([[0, H, 0, W]] * n, dtype=torch.int32).to(dev)
         self.words = torch.zeros(4, dtype=torch.int32, device=dev)         # box count, crop error word, resize error word, unused
-        self.x_dark = torch.zeros((n, 3, side, side), dtype=torch.float32, device=dev)
+        self.n_dark = n                 # images in front of the detector: the frames, or with tiles every frame's windows
+        if tiles is not None:
+            # the tile table of this frame shape, frame-major: tile b = rectangle tile_rect[b] of frame tile_idx[b] (ascending)
+            rects = tiles.rects(H, W)
+            self.n_dark = n * len(rects)
+            self.tile_idx = torch.from_numpy(np.repeat(np.arange(n, dtype=np.int32), len(rects))).to(dev)
+            self.tile_rect = torch.from_numpy(np.ascontiguousarray(np.tile(rects, (n, 1)))).to(dev)
+        self.x_dark = torch.zeros((self.n_dark, 3, side, side), dtype=torch.float32, device=dev)
         self.box_img = torch.zeros(K, dtype=torch.int32, device=dev)
         self.box_xy = torch.zeros((K, 4), dtype=torch.float64, device=dev)
         self.box_conf = torch.zeros(K, dtype=torch.float32, device=dev)
@@ -207,7 +215,7 @@ class _State(object):
 class _Candidates(object):
     """The decode kernel's whole output for one frame shape, cap = n g^2 n_boxes entries, and what `cy_nms_boxes` needs beside it."""
 
-    def __init__(self, cap, n, K, has_cls, dev):
+    def __init__(self, cap, n, K, has_cls, dev, tiled=False):
         self.cap = cap
         self.img = torch.zeros(cap, dtype=torch.int32, device=dev)
         self.xy = torch.zeros((cap, 4), dtype=torch.float64, device=dev)
@@ -215,7 +223,8 @@ class _Candidates(object):
         self.cls = torch.zeros(cap, dtype=torch.int32, device=dev) if has_cls else None
         self.keep = torch.zeros(cap, dtype=torch.int32, device=dev)
         self.src = torch.zeros(K, dtype=torch.int32, device=dev)            # the survivors' positions in the list
-        self.words = torch.zeros(2 + n, dtype=torch.int32, device=dev)      # candidate count, error word, per-image scratch
+        # candidate count, error word, per-image scratch; with tiles behind them: boxes the border rule dropped, bad tiles
+        self.words = torch.zeros(2 + n + (2 if tiled else 0), dtype=torch.int32, device=dev)
 
 
 class SignDetector(object):
@@ -234,10 +243,16 @@ class SignDetector(object):
     detector with class scores.  None: no such step, the first max_boxes boxes in decode order as before.
     tracker (optional): a `SignTracker` for the classifier's classes and max_boxes slots on the detector's device.  Every call is then
     ONE frame of the tracker's camera: `cy_track_update` runs behind the pack step on the same stream (with graph=True inside every
-    frame shape's graph, all on the tracker's one state), and the result carries `.tracks`.  The detections' record does not change."""
+    frame shape's graph, all on the tracker's one state), and the result carries `.tracks`.  The detections' record does not change.
+    tiles (optional): a `tiles.TileSpec`.  The detector then sees the T = rows x cols (+ 1 with full) overlapping windows of every
+    frame instead of the frame, each resized to darknet_input: one `cy_crop_resize_u8` for all n T windows, the detector on that
+    batch, `cy_yolo_decode_tiles_conf` (border rule and shift into frame pixels, include/capsyolo_hip.h) into one candidate list of
+    n T g^2 n_boxes entries, `cy_nms_boxes` per frame with room for T g^2 n_boxes boxes (at most cy_nms_max_per_image()).  Needs
+    nms_iou: the overlaps show a sign to more than one window by construction.  Crops, classifier, record and tracker are as
+    without tiles, on the full frames.  None: the launches are exactly those of a detector without the argument."""
 
     def __init__(self, dark_model, dark_params, class_model, class_params, max_boxes=16, conf_th=0.5, graph=False, nms_iou=None,
-                 nms_class_aware=False, per_frame=0, tracker=None):
+                 nms_class_aware=False, per_frame=0, tracker=None, tiles=None):
         if int(max_boxes) != max_boxes or max_boxes < 1:
             raise ValueError('max_boxes must be an integer >= 1, got %r' % (max_boxes,))
         if nms_iou is not None and not (0.0 <= float(nms_iou) <= 1.0):
@@ -248,6 +263,12 @@ class SignDetector(object):
             raise ValueError('nms_class_aware and per_frame belong to the suppression step: give nms_iou')
         if nms_class_aware and int(dark_params.n_classes) == 0:
             raise ValueError('nms_class_aware needs a detector with class scores (n_classes > 0)')
+        if tiles is not None:
+            if not isinstance(tiles, TileSpec):
+                raise ValueError('tiles must be a TileSpec, got %r' % (type(tiles).__name__,))
+            if nms_iou is None:
+                raise ValueError('tiles need nms_iou: overlapping windows see the same sign more than once by construction')
+            tiles.check_capacity(dark_params.n_grid, dark_params.n_boxes, query('cy_nms_max_per_image'))
         if tracker is not None:
             if not isinstance(tracker, SignTracker):
                 raise ValueError('tracker must be a SignTracker, got %r' % (type(tracker).__name__,))
@@ -268,7 +289,7 @@ class SignDetector(object):
             raise ValueError('both models must be on the same GPU; the detector is on %s' % (self.dev,))
         if tracker is not None and tracker.dev != self.dev:
             raise ValueError('the tracker is on %s, the detector on %s' % (tracker.dev, self.dev))
-        self.tracker = tracker
+        self.tracker, self.tiles = tracker, tiles
         for m in (dark_model, class_model):
             if m.training:          # (a switch of mode starts a new fold-cache epoch, which would rebuild other detectors' captures)
                 m.eval()
@@ -294,7 +315,7 @@ class SignDetector(object):
     def _state(self, n, H, W):
         key = (n, H, W)
         if key not in self.states:
-            self.states[key] = _State(n, H, W, self.side, self.ci, self.K, self.C > 0, self.dev)
+            self.states[key] = _State(n, H, W, self.side, self.ci, self.K, self.C > 0, self.dev, self.tiles)
         return self.states[key]
 
     # ------------------------------------------------------------------------------------------------ the device steps
@@ -305,11 +326,15 @@ class SignDetector(object):
         K = self.K
         w = st.words.data_ptr()
         st.words.zero_()
-        call('cy_crop_resize_u8', st.frames.data_ptr(), st.off.data_ptr(), st.hw32.data_ptr(), st.n, st.nbytes, st.frame_idx.data_ptr(),
-             st.frame_rect.data_ptr(), st.n, self.side, self.side, 0.0, 1.0, 1, st.x_dark.data_ptr(), w + 8, stream)
+        if self.tiles is None:
+            call('cy_crop_resize_u8', st.frames.data_ptr(), st.off.data_ptr(), st.hw32.data_ptr(), st.n, st.nbytes, st.frame_idx.data_ptr(),
+                 st.frame_rect.data_ptr(), st.n, self.side, self.side, 0.0, 1.0, 1, st.x_dark.data_ptr(), w + 8, stream)
+        else:               # every window of every frame, each resized as an image of its own
+            call('cy_crop_resize_u8', st.frames.data_ptr(), st.off.data_ptr(), st.hw32.data_ptr(), st.n, st.nbytes, st.tile_idx.data_ptr(),
+                 st.tile_rect.data_ptr(), st.n_dark, self.side, self.side, 0.0, 1.0, 1, st.x_dark.data_ptr(), w + 8, stream)
         y = self.dark(st.x_dark).data
-        if y.dim() != 4 or y.shape[0] != st.n or y.shape[1] != self.g or y.shape[2] != self.g:
-            raise ValueError('the detector returned %s for %d frames on a %d x %d grid' % (tuple(y.shape), st.n, self.g, self.g))
+        if y.dim() != 4 or y.shape[0] != st.n_dark or y.shape[1] != self.g or y.shape[2] != self.g:
+            raise ValueError('the detector returned %s for %d frames on a %d x %d grid' % (tuple(y.shape), st.n_dark, self.g, self.g))
         D = int(y.shape[3])
         nb = int((D - self.C) / 5)
         if nb < 1:          # what utils.decode_boxes_device refuses
@@ -319,6 +344,23 @@ class SignDetector(object):
             call('cy_yolo_decode_boxes_conf', y.data_ptr(), st.hw64.data_ptr(), float(self.side), float(self.side), st.n, self.g, nb, self.C,
                  self.conf_th, w, st.box_img.data_ptr(), st.box_xy.data_ptr(), st.box_cls.data_ptr() if self.C else None,
                  st.box_conf.data_ptr(), K, stream)
+        elif self.tiles is not None:
+            # the boxes of all windows in frame pixels into one candidate list per call (a frame's windows are neighbours in it), then
+            # the suppression step per FRAME, which merges what the overlaps saw twice
+            per_image = self.tiles.check_capacity(self.g, nb, query('cy_nms_max_per_image'))
+            if st.cand is None or st.cand.cap != st.n * per_image:
+                st.cand = _Candidates(st.n * per_image, st.n, K, self.C > 0, self.dev, tiled=True)
+            c = st.cand
+            c.words.zero_()
+            cw = c.words.data_ptr()
+            tw = cw + 4 * (2 + st.n)                     # dropped by the border rule, bad tiles (none: the table is tile_rects')
+            call('cy_yolo_decode_tiles_conf', y.data_ptr(), st.tile_idx.data_ptr(), st.tile_rect.data_ptr(), st.hw32.data_ptr(), st.n,
+                 self.tiles.margin, st.n_dark, self.g, nb, self.C, self.conf_th, cw, tw, c.img.data_ptr(), c.xy.data_ptr(),
+                 c.cls.data_ptr() if self.C else None, c.conf.data_ptr(), None, c.cap, tw + 4, stream)
+            call('cy_nms_boxes', cw, c.img.data_ptr(), c.xy.data_ptr(), c.conf.data_ptr(), c.cls.data_ptr() if self.C else None, c.cap,
+                 st.n, self.nms_iou, int(self.nms_class_aware), self.per_frame, per_image, c.keep.data_ptr(), K, st.box_img.data_ptr(),
+                 st.box_xy.data_ptr(), st.box_conf.data_ptr(), st.box_cls.data_ptr() if self.C else None, c.src.data_ptr(), w, cw + 8,
+                 cw + 4, stream)
         else:
             # every box over the threshold into the candidate list, the survivors into the K slots, their number into the count word
             per_image = self.g * self.g * nb

@@ -136,6 +136,48 @@ def decode_boxes_device(y, params, image_hw=None, conf_th=0.5, with_conf=False):
     return n, idx[:n], xy[:n], (cls[:n] if C else None)
 
 
+def decode_tiles_device(y, params, tile_frame, tile_rect, frame_hw, conf_th=0.5, margin=2.0, with_tile=False, max_boxes=None):
+    """`cy_yolo_decode_tiles_conf` with everything left on the device: y [Bt, g, g, D] is the detector's output for Bt tiles, tile b
+    being rectangle tile_rect[b] = (y0, y1, x0, x1) of frame tile_frame[b] (ascending), frame_hw [n, 2] = (height, width) of the
+    frames.  Returns (n, idx int32[n], xy float64[n,4] in frame pixels, cls int32[n] | None, conf float32[n], dropped[, tile int32[n]]):
+    the boxes the border rule kept (include/capsyolo_hip.h; margin < 0: all) in (tile, row, column, box) order, idx = their frames,
+    dropped = how many the rule dropped, tile = the tile each came from.  max_boxes: output slots (default: all Bt g^2 nb); n may
+    exceed it, min(n, max_boxes) entries are returned.  A bad tile raises ValueError."""
+    from ._lib import call
+    yt = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).to(device='cuda', dtype=torch.float32).contiguous()
+    Bt, g, _, D = yt.shape
+    C = int(params.n_classes)
+    nb = int((D - C) / 5)
+    if nb < 1:
+        raise ValueError('y has %d values per cell: no box left after %d class scores (utils.py:291-293)' % (D, C))
+    dev = yt.device
+
+    def table(a, shape):
+        return torch.as_tensor(a if torch.is_tensor(a) else np.asarray(a)).to(device=dev, dtype=torch.int32).reshape(shape).contiguous()
+    tf, tr, hw = table(tile_frame, (-1,)), table(tile_rect, (-1, 4)), table(frame_hw, (-1, 2))
+    if int(tf.numel()) != Bt or int(tr.shape[0]) != Bt or int(hw.shape[0]) < 1:
+        raise ValueError('decode_tiles_device: y has %d tiles, tile_frame %d, tile_rect %d, frame_hw %d frames'
+                         % (Bt, tf.numel(), tr.shape[0], hw.shape[0]))
+    cap = Bt * g * g * nb if max_boxes is None else int(max_boxes)
+    words = torch.zeros(3, dtype=torch.int32, device=dev)                 # count, dropped, error word
+    idx = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    xy = torch.empty((max(cap, 1), 4), dtype=torch.float64, device=dev)
+    cls = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if C else None
+    conf = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)
+    tile = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if with_tile else None
+    w = words.data_ptr()
+    call('cy_yolo_decode_tiles_conf', yt.data_ptr(), tf.data_ptr(), tr.data_ptr(), hw.data_ptr(), int(hw.shape[0]), float(margin), Bt, g, nb,
+         C, float(conf_th), w, w + 4, idx.data_ptr(), xy.data_ptr(), cls.data_ptr() if C else None, conf.data_ptr(),
+         tile.data_ptr() if with_tile else None, cap, w + 8, torch.cuda.current_stream().cuda_stream)
+    n, dropped, err = (int(v) for v in words.cpu().numpy())
+    if err:
+        raise ValueError('decode_tiles_device: %d tile(s) with a frame index outside 0..%d or a rectangle that is empty or leaves its frame'
+                         % (err, hw.shape[0] - 1))
+    m = min(n, cap)
+    out = (n, idx[:m], xy[:m], (cls[:m] if C else None), conf[:m], dropped)
+    return out + (tile[:m],) if with_tile else out
+
+
 def _nms_call(count, idx, xy, conf, cls, n_cap, n_images, iou_th, class_aware, per_image, max_per_image, K):
     """`cy_nms_boxes` on a device list (count: int32 [1] device tensor): (keep int32 [n_cap], out_img, out_xy, out_conf, out_cls | None,
     out_src, words int32 [2] = (survivors, error word)), all on the device, nothing read back."""

@@ -645,6 +645,29 @@ int cy_nms_max_per_image(void);
 int cy_nms_boxes(const int* count_in, const int* box_img, const double* box_xy, const float* conf, const int* cls, int n_cap,
                  int n_images, double iou_th, int class_aware, int per_image, int max_per_image, int* keep, int K, int* out_img,
                  double* out_xy, float* out_conf, int* out_cls, int* out_src, int* count_out, int* ws, int* err, void* stream);
+/* ------------------------------------------------------------------ tiled detection (csrc/tiles.hip)
+ * The detector run on overlapping windows ("tiles") of a frame at close to native scale, and its outputs put back into the frame:
+ * cy_yolo_decode_boxes_conf for a batch y[Bt][g][g][5 nb + C] whose images are tiles.  tile_frame[Bt] (ascending), tile_rect[Bt][4] =
+ * (y0, y1, x0, x1) half-open and frame_hw[n_frames][2] = (H, W) are the box_img / rect / img_hw tables of the cy_crop_resize_u8 call
+ * that cut the tiles.  The reference has no such step; tests/tiles_ref.py restates the rule in numpy.  All in double, not contracted:
+ *  1. Tile b is an image of th x tw = (y1 - y0) x (x1 - x0) pixels: a cell's box over conf_th gets its tile-pixel corners
+ *     (bx1, by1, bx2, by2) exactly as cy_yolo_decode_boxes_conf computes them with image_hw = (th, tw), the same operations in the
+ *     same order.
+ *  2. Border rule (skipped when margin < 0).  With (H, W) = frame_hw[tile_frame[b]] the box is dropped, and counted in *dropped
+ *     (caller-zeroed, added to), iff  x0 > 0 && bx1 < margin,  or  x1 < W && bx2 > tw - margin,  or  y0 > 0 && by1 < margin,  or
+ *     y1 < H && by2 > th - margin.  Only a window edge inside the frame cuts a sign, and a NaN corner drops nothing: a box at such
+ *     an edge is left to the neighbouring window that sees it whole, so the windows' overlap has to exceed the largest sign (a
+ *     whole-frame view among the tiles serves the signs larger than that).
+ *  3. A kept box: xy = (bx1 + (double)x0, by1 + (double)y0, bx2 + (double)x0, by2 + (double)y0), one addition each;
+ *     image_idx = tile_frame[b]; conf and cls as cy_yolo_decode_boxes_conf; out_tile (optional, NULL: not written) = b.
+ *  4. The kept boxes come out in (tile, row, column, box) order -- frame ascending, what cy_nms_boxes needs -- with no atomic on the
+ *     order: identical bits from run to run.  *count = the kept boxes (may exceed max_boxes: only the first max_boxes are written).
+ * A tile whose frame index is outside 0..n_frames-1, or whose rectangle is empty or leaves its frame, adds 1 to *err (caller-zeroed)
+ * and contributes no box.  Refused before any launch: Bt < 0, g < 1, nb < 1, C < 0, n_frames < 1, max_boxes < 0, a NaN margin, a
+ * null pointer (cls only with C > 0).  Bt = 0 or max_boxes = 0 is valid and launches nothing (no word is written).  One workgroup. */
+int cy_yolo_decode_tiles_conf(const float* y, const int* tile_frame, const int* tile_rect, const int* frame_hw, int n_frames,
+                              double margin, int Bt, int g, int nb, int C, float conf_th, int* count, int* dropped, int* image_idx,
+                              double* xy, int* cls, float* conf, int* out_tile, int max_boxes, int* err, void* stream);
 /* ------------------------------------------------------------------ sign tracks (csrc/track.hip)
  * The step behind cy_pack_detections in serve.SignDetector: the frame's boxes are joined to the tracks of the frames before, so a
  * sign keeps an id, its class is voted over everything seen so far, and a box seen once is told from a sign.  One launch of one

@@ -42,6 +42,11 @@ latency percentiles (see serve()).
 suppression over the detector's boxes on the device (`cy_nms_boxes`) before they are cropped, drawn or scored: the metric files
 then hold the metrics of the suppressed predictions, and one line says how many boxes over 0.5 the step removed.  The reference
 has no such step, so the default is none.  ``--per_frame N`` (serve only) keeps at most the N most confident survivors of a frame.
+``--tiles RxC --tile_overlap PX [--tile_full] [--tile_margin M]`` (new; with --mode serve and --mode detect, both with --nms, and with
+--mode train --model darknet_d|darknet_r --augment) runs the detector on R x C overlapping windows of every frame at close to native
+scale instead of on the resized frame (capsyolo_amd.tiles): the windows' boxes are put back into the frame on the device
+(`cy_yolo_decode_tiles_conf`), the duplicates in the overlaps are merged by the suppression step, and the outputs keep their
+formats; in train mode every augmented sample is one randomly drawn window with the labels of the signs visible in it.
 ``--mode serve ... --track [--max_tracks N --track_iou X --max_misses M --min_hits H --track_decay D --no_motion]`` (new) follows the
 boxes from frame to frame on the device (`cy_track_update` behind serve.SignTracker): track ids, classes voted over a track's frames,
 hit counts; one line per frame goes to <model_dir>/tracks_output.txt, serve_output.txt stays as it is.
@@ -154,6 +159,15 @@ parser.add_argument('--nms_class_aware', action='store_true',
                     help='--nms: a box is suppressed only by a box of the same detector class (a detector with class scores: darknet_r)')
 parser.add_argument('--per_frame', type=int, default=0, metavar='N',
                     help='--mode serve --nms: at most N boxes of a frame survive, the most confident ones (0: no cap)')
+parser.add_argument('--tiles', default=None, metavar='RxC',
+                    help='--mode serve | detect (with --nms), --mode train --augment: run the detector on R x C overlapping windows of '
+                         'a frame at close to native scale instead of on the resized frame (capsyolo_amd.tiles)')
+parser.add_argument('--tile_overlap', type=int, default=None, metavar='PX',
+                    help='--tiles: neighbouring windows overlap by at least PX pixels (more than the largest sign; default 0)')
+parser.add_argument('--tile_full', action='store_true', help='--tiles: the whole frame is one more view (for signs larger than the overlap)')
+parser.add_argument('--tile_margin', type=float, default=None, metavar='M',
+                    help='--tiles: a box within M tile pixels of a window edge inside the frame is left to the neighbouring window '
+                         '(default 2; negative: keep all)')
 parser.add_argument('--track', action='store_true',
                     help='--mode serve: join the boxes of successive frames into tracks on the device (ids, voted classes, hit counts); '
                          'one line per frame goes to <model_dir>/tracks_output.txt')
@@ -517,7 +531,7 @@ def augmented_data(args, params, data_dir):
             x_ev, y_ev = pickle.load(f)
         bank = build_data.load_bank(args.gtsrb)
     params.augment_source = augment.AugmentSource(frames, boxes, bank, side, g, C, int(getattr(params, 'add_signs', 0)),
-                                                  args.seed, params.device)
+                                                  args.seed, params.device, tiles=getattr(args, 'tile_spec', None))
     idx = np.arange(len(frames))
     return idx, idx.copy(), x_ev, y_ev
 
@@ -658,9 +672,21 @@ def detect(args, model, model_dir, data_dir, params):
         with open(data_dir + config.te_d, 'rb') as f:
             _, y = pickle.load(f)
         x = list(np.load(data_dir + '/test_images.npy', allow_pickle=True))
-    y_hat, output = dark_pred(x, model, model_dir, params, args.restore, y=y, batch_size=params.batch_size, draw=True, nms_iou=args.nms,
-                              nms_class_aware=args.nms_class_aware)
-    metric_out = metrics.detect_report(y, y_hat, params)
+    if getattr(args, 'tile_spec', None) is not None:
+        # --tiles: the merged box list of the windows in image pixels against the ground truth decoded with the images' sizes
+        from capsyolo_amd.predict_fns import dark_pred_tiled
+        try:
+            pr, output = dark_pred_tiled(x, model, model_dir, params, args.restore, args.tile_spec, args.nms, y=y,
+                                         batch_size=params.batch_size, draw=True, nms_class_aware=args.nms_class_aware)
+        except ValueError as e:
+            raise SystemExit('--tiles %s: %s' % (args.tiles, e))
+        hw = np.array([np.asarray(im).shape[0:2] for im in x], dtype=np.int64)
+        _, g_idx, g_xy, _, g_conf = utils.decode_boxes_device(y, params, hw, 0.0, with_conf=True)
+        metric_out = metrics.detect_report_boxes((g_idx, g_xy, g_conf), pr[:3], len(x))
+    else:
+        y_hat, output = dark_pred(x, model, model_dir, params, args.restore, y=y, batch_size=params.batch_size, draw=True, nms_iou=args.nms,
+                                  nms_class_aware=args.nms_class_aware)
+        metric_out = metrics.detect_report(y, y_hat, params)
     with open(os.path.join(model_dir, 'metric_output.txt'), 'w') as text_file:
         for k, v in metric_out.items():
             text_file.write("{}:{}, ".format(k, v))
@@ -685,6 +711,33 @@ def check_nms(args):
         raise SystemExit('--per_frame %d: at least 0' % args.per_frame)
     if args.per_frame and args.mode != 'serve':
         raise SystemExit('--per_frame caps the boxes of a frame of --mode serve')
+
+
+def check_tiles(args):
+    """The refusals of --tiles and its options that need neither the data nor a device; sets args.tile_spec (a tiles.TileSpec, or None)."""
+    from capsyolo_amd.tiles import TileSpec, parse_tiles
+    args.tile_spec = None
+    if args.tiles is None:
+        given = [k for k, on in (('--tile_overlap', args.tile_overlap is not None), ('--tile_full', args.tile_full),
+                                 ('--tile_margin', args.tile_margin is not None)) if on]
+        if given:
+            raise SystemExit('%s belongs to the tiling: give --tiles RxC' % given[0])
+        return
+    try:
+        rows, cols = parse_tiles(args.tiles)
+        spec = TileSpec(rows, cols, 0 if args.tile_overlap is None else args.tile_overlap, args.tile_full,
+                        2.0 if args.tile_margin is None else args.tile_margin)
+    except ValueError as e:
+        raise SystemExit('--tiles %s: %s' % (args.tiles, e))
+    if args.mode == 'train' and args.augment:
+        if args.model not in ('darknet_d', 'darknet_r'):
+            raise SystemExit('--tiles trains a detector whose output decodes into boxes: --model darknet_d|darknet_r')
+    elif args.mode in ('serve', 'detect'):
+        if args.nms is None:
+            raise SystemExit('--tiles needs --nms IOU: overlapping windows see the same sign more than once')
+    else:
+        raise SystemExit('--tiles runs the detector on windows of a frame: --mode serve, --mode detect, or --mode train --augment')
+    args.tile_spec = spec
 
 
 TRACK_DEFAULTS = dict(max_tracks=32, track_iou=0.3, max_misses=2, min_hits=2, track_decay=0.9)
@@ -760,7 +813,8 @@ def serve(args, model, model_dir, data_dir, params):
         tracker = SignTracker(int(class_params.n_classes), args.max_boxes, max_tracks=args.max_tracks, iou_th=args.track_iou,
                               max_misses=args.max_misses, min_hits=args.min_hits, decay=args.track_decay, motion=not args.no_motion)
     det = SignDetector(model, params, class_model, class_params, max_boxes=args.max_boxes, graph=args.graph, nms_iou=args.nms,
-                       nms_class_aware=args.nms_class_aware, per_frame=args.per_frame, tracker=tracker)
+                       nms_class_aware=args.nms_class_aware, per_frame=args.per_frame, tracker=tracker,
+                       tiles=getattr(args, 'tile_spec', None))
     seen, ms = set(), []
     out = dict(frames=0, boxes=0, truncated=0, bad_boxes=0)
     confirmed_ids, tracks_born = set(), 0
@@ -933,6 +987,7 @@ def main(argv=None):
     if args.mode == 'attack':
         check_attack(args)
     check_nms(args)
+    check_tiles(args)
     check_track(args)
     data_dir, model_dir = config.data_dir[args.model], config.model_dir[args.model]
     if args.model_dir is not None:
