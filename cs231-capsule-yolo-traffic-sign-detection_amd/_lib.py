@@ -59,6 +59,11 @@ class AdamStep(C.Structure):
                [(k, C.c_float) for k in ('lr', 'beta1', 'beta2', 'eps', 'bias_corr1', 'bias_corr2', 'one_minus_decay')]
 
 
+class YuvCoef(C.Structure):
+    """cy_yuv_coef_t: the coefficient row of the NV12 colour rule, passed by value."""
+    _fields_ = [(k, C.c_int) for k in ('y_off', 'cy', 'cvr', 'cug', 'cvg', 'cub')]
+
+
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_longlong
 
 # name -> argtypes (all return int unless listed in _RET)
@@ -141,6 +146,9 @@ _SIGS = {
     'cy_yolo_decode_boxes_conf': [_P, _P, C.c_double, C.c_double, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P],
     'cy_confusion_sweep': [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P],
     'cy_boxes_crop_resize_u8': [_P, _P, _P, _I, _L, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P],
+    'cy_crop_resize_nv12': [_P, _P, _P, _I, _L, YuvCoef, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P],
+    'cy_boxes_crop_resize_nv12': [_P, _P, _P, _I, _L, YuvCoef, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P],
+    'cy_nv12_to_rgb_u8': [_P, _P, _P, _I, _L, YuvCoef, _P, _P, _L, _P, _P],
     'cy_pack_detections': [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     'cy_nms_boxes': [_P, _P, _P, _P, _P, _I, _I, C.c_double, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     'cy_yolo_decode_tiles_conf': [_P, _P, _P, _P, _I, C.c_double, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],

@@ -14,11 +14,12 @@
 
 namespace {
 
-// One thread per output pixel; the pixel itself is cyi_crop_pixel (crop_pixel.h, shared with serve.hip).
-__global__ __launch_bounds__(256) void crop_resize_u8_kernel(const unsigned char* __restrict__ imgs, const long long* __restrict__ img_off,
-                                                             const int* __restrict__ img_hw, const int* __restrict__ box_img,
-                                                             const int* __restrict__ rect, long long total, int n_images, long long imgs_bytes, int OH, int OW,
-                                                             float shift, float scale, int to_nchw, float* __restrict__ out, int* err) {
+// One thread per output pixel; the pixel itself is cyi_crop_pixel (crop_pixel.h, shared with serve.hip).  Images: where the
+// images lie and how a tap is fetched (cyi_images_rgb: packed HWC; cyi_images_nv12: NV12 converted in the tap fetch).
+template <class Images>
+__global__ __launch_bounds__(256) void crop_resize_kernel(const Images src, const int* __restrict__ box_img, const int* __restrict__ rect,
+                                                          long long total, int n_images, int OH, int OW, float shift, float scale,
+                                                          int to_nchw, float* __restrict__ out, int* err) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int ox = (int)(i % OW);
@@ -28,18 +29,18 @@ __global__ __launch_bounds__(256) void crop_resize_u8_kernel(const unsigned char
   const int img = box_img[b];
   float v[3] = {0.f, 0.f, 0.f};
   bool ok = img >= 0 && img < n_images;
-  int y0 = 0, y1 = 0, x0 = 0, x1 = 0, W = 0;
+  int y0 = 0, y1 = 0, x0 = 0, x1 = 0;
+  typename Images::fetch_t f;
   if (ok) {
-    const int H = img_hw[2 * img];
-    W = img_hw[2 * img + 1];
+    int H, W;
+    const bool inside = src.image(img, H, W, f);
     y0 = rect[4 * b]; y1 = rect[4 * b + 1]; x0 = rect[4 * b + 2]; x1 = rect[4 * b + 3];
-    ok = y0 >= 0 && y0 < y1 && y1 <= H && x0 >= 0 && x0 < x1 && x1 <= W && img_off[img] >= 0 &&
-         img_off[img] + (long long)H * W * 3 <= imgs_bytes;
+    ok = y0 >= 0 && y0 < y1 && y1 <= H && x0 >= 0 && x0 < x1 && x1 <= W && inside;
   }
   if (!ok) {
     if (ox == 0 && oy == 0) atomicAdd(err, 1);       // one count per bad box; its output is zero-filled
   } else {
-    cyi_crop_pixel(imgs + img_off[img], W, y0, y1, x0, x1, oy, ox, OH, OW, shift, scale, v);
+    cyi_crop_pixel(f, y0, y1, x0, x1, oy, ox, OH, OW, shift, scale, v);
   }
   cyi_store_pixel(out, i, b, oy, ox, OH, OW, to_nchw, v[0], v[1], v[2]);
 }
@@ -227,9 +228,25 @@ extern "C" int cy_crop_resize_u8(const unsigned char* imgs, const long long* img
   CY_REQUIRE(n_images > 0 && imgs_bytes > 0 && n > 0 && OH > 0 && OW > 0 && OH < (1 << 20) && OW < (1 << 20), "cy_crop_resize_u8: bad sizes");
   const long long total = (long long)n * OH * OW;
   CY_REQUIRE(cy_ceil_div(total, 256) < (1ll << 31), "cy_crop_resize_u8: %lld output pixels are too many for one launch", total);
-  crop_resize_u8_kernel<<<(unsigned)cy_ceil_div(total, 256), 256, 0, CY_S>>>(imgs, img_off, img_hw, box_img, rect, total, n_images, imgs_bytes, OH, OW,
-                                                                             shift, scale, to_nchw, out, err);
+  const cyi_images_rgb src = {imgs, img_off, img_hw, imgs_bytes};
+  crop_resize_kernel<<<(unsigned)cy_ceil_div(total, 256), 256, 0, CY_S>>>(src, box_img, rect, total, n_images, OH, OW, shift, scale, to_nchw,
+                                                                          out, err);
   CY_LAUNCH_CHECK("cy_crop_resize_u8");
+  return 0;
+}
+
+extern "C" int cy_crop_resize_nv12(const unsigned char* imgs, const long long* img_off, const int* img_geom, int n_images,
+                                   long long imgs_bytes, cy_yuv_coef_t coef, const int* box_img, const int* rect, int n, int OH, int OW,
+                                   float shift, float scale, int to_nchw, float* out, int* err, void* stream) {
+  CY_REQUIRE(imgs && img_off && img_geom && box_img && rect && out && err, "cy_crop_resize_nv12: null argument");
+  CY_REQUIRE(n_images > 0 && imgs_bytes > 0 && n > 0 && OH > 0 && OW > 0 && OH < (1 << 20) && OW < (1 << 20), "cy_crop_resize_nv12: bad sizes");
+  CY_REQUIRE(cyi_yuv_coef_ok(coef), "cy_crop_resize_nv12: " CYI_YUV_COEF_MSG, CYI_YUV_COEF_ARGS(coef));
+  const long long total = (long long)n * OH * OW;
+  CY_REQUIRE(cy_ceil_div(total, 256) < (1ll << 31), "cy_crop_resize_nv12: %lld output pixels are too many for one launch", total);
+  const cyi_images_nv12 src = {imgs, img_off, img_geom, imgs_bytes, coef};
+  crop_resize_kernel<<<(unsigned)cy_ceil_div(total, 256), 256, 0, CY_S>>>(src, box_img, rect, total, n_images, OH, OW, shift, scale, to_nchw,
+                                                                          out, err);
+  CY_LAUNCH_CHECK("cy_crop_resize_nv12");
   return 0;
 }
 

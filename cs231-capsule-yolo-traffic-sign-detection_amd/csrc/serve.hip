@@ -1,7 +1,7 @@
 // The device-side glue of the streaming detector (serve.py, SignDetector): what predict_fns._detect_and_crop does on the host between
 // the detector and the classifier, and what follows the classifier, as two fixed-shape launches that read the box count from device
 // memory -- so the chain frame -> detector -> crops -> classifier -> labelled boxes has no host hop and captures into a HIP graph.
-//   boxes_crop_resize_u8_kernel   utils.crop_rectangles (the rectangle rule) fused with cy_crop_resize_u8, for K slots
+//   boxes_crop_resize_kernel      utils.crop_rectangles (the rectangle rule) fused with cy_crop_resize_u8, for K slots
 //   pack_detections_kernel        np.argmax of the class scores + gather of every slot into one record buffer
 #include "common.h"
 #include "crop_pixel.h"
@@ -18,13 +18,13 @@ __device__ __forceinline__ int trunc_clip(double v, int hi) {
 }
 
 // One thread per output pixel of every slot; the launch does not depend on *count.  Every thread of a slot computes the slot's
-// rectangle again (four doubles), the slot's first thread writes it and counts a bad slot.
-__global__ __launch_bounds__(256) void boxes_crop_resize_u8_kernel(const unsigned char* __restrict__ imgs, const long long* __restrict__ img_off,
-                                                                   const int* __restrict__ img_hw, int n_images, long long imgs_bytes,
-                                                                   const int* __restrict__ count, const int* __restrict__ box_img,
-                                                                   const double* __restrict__ box_xy, long long total, int K, int OH, int OW,
-                                                                   float shift, float scale, int to_nchw, float* __restrict__ out,
-                                                                   int* __restrict__ rect_out, int* err) {
+// rectangle again (four doubles), the slot's first thread writes it and counts a bad slot.  Images: cyi_images_rgb or cyi_images_nv12
+// (crop_pixel.h); the slot rule below is the one copy for both.
+template <class Images>
+__global__ __launch_bounds__(256) void boxes_crop_resize_kernel(const Images src, int n_images, const int* __restrict__ count,
+                                                                const int* __restrict__ box_img, const double* __restrict__ box_xy,
+                                                                long long total, int K, int OH, int OW, float shift, float scale,
+                                                                int to_nchw, float* __restrict__ out, int* __restrict__ rect_out, int* err) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int ox = (int)(i % OW);
@@ -41,13 +41,14 @@ __global__ __launch_bounds__(256) void boxes_crop_resize_u8_kernel(const unsigne
     const double bx0 = box_xy[4 * s], by0 = box_xy[4 * s + 1], bx1 = box_xy[4 * s + 2], by1 = box_xy[4 * s + 3];
     ok = img >= 0 && img < n_images && isfinite(bx0) && isfinite(by0) && isfinite(bx1) && isfinite(by1);
     if (ok) {
-      const int H = img_hw[2 * img], W = img_hw[2 * img + 1];
-      const long long off = img_off[img];
+      int H, W;
+      typename Images::fetch_t f;
+      // (an image that does not lie inside the buffer is never read: its slots are bad)
+      const bool inside = src.image(img, H, W, f);
       x0 = trunc_clip(bx0, W); x1 = trunc_clip(bx1, W);
       y0 = trunc_clip(by0, H); y1 = trunc_clip(by1, H);
-      // (an image that does not lie inside the buffer is never read: its slots are bad)
-      ok = y0 < y1 && x0 < x1 && H > 0 && W > 0 && off >= 0 && off + (long long)H * W * 3 <= imgs_bytes;
-      if (ok) cyi_crop_pixel(imgs + off, W, y0, y1, x0, x1, oy, ox, OH, OW, shift, scale, v);
+      ok = y0 < y1 && x0 < x1 && inside;
+      if (ok) cyi_crop_pixel(f, y0, y1, x0, x1, oy, ox, OH, OW, shift, scale, v);
       else y0 = y1 = x0 = x1 = 0;
     }
   }
@@ -99,22 +100,41 @@ __global__ __launch_bounds__(64) void pack_detections_kernel(const float* __rest
 
 #define CY_S ((hipStream_t)stream)
 
+// the checks and the launch of both image formats; `who` names the entry point in the messages
+template <class Images>
+static int boxes_crop_resize(const char* who, const Images& src, bool tables, int n_images, long long imgs_bytes, const int* count,
+                             const int* box_img, const double* box_xy, int K, int OH, int OW, float shift, float scale, int to_nchw,
+                             float* out, int* rect_out, int* err, void* stream) {
+  CY_REQUIRE(count && out && rect_out && err, "%s: null argument (count, out, rect_out, err)", who);
+  CY_REQUIRE(K >= 0, "%s: K=%d slots", who, K);
+  CY_REQUIRE(OH >= 1 && OW >= 1 && OH < (1 << 20) && OW < (1 << 20), "%s: output size %d x %d", who, OH, OW);
+  if (K == 0) return 0;
+  CY_REQUIRE(tables && box_img && box_xy, "%s: null argument (images or boxes)", who);
+  CY_REQUIRE(n_images > 0 && imgs_bytes > 0, "%s: %d images in %lld bytes", who, n_images, imgs_bytes);
+  const long long total = (long long)K * OH * OW;
+  CY_REQUIRE(cy_ceil_div(total, 256) < (1ll << 31), "%s: %lld output pixels are too many for one launch", who, total);
+  boxes_crop_resize_kernel<<<(unsigned)cy_ceil_div(total, 256), 256, 0, CY_S>>>(src, n_images, count, box_img, box_xy, total, K, OH, OW, shift,
+                                                                                scale, to_nchw, out, rect_out, err);
+  CY_LAUNCH_CHECK(who);
+  return 0;
+}
+
 extern "C" int cy_boxes_crop_resize_u8(const unsigned char* imgs, const long long* img_off, const int* img_hw, int n_images,
                                        long long imgs_bytes, const int* count, const int* box_img, const double* box_xy, int K, int OH,
                                        int OW, float shift, float scale, int to_nchw, float* out, int* rect_out, int* err, void* stream) {
-  CY_REQUIRE(count && out && rect_out && err, "cy_boxes_crop_resize_u8: null argument (count, out, rect_out, err)");
-  CY_REQUIRE(K >= 0, "cy_boxes_crop_resize_u8: K=%d slots", K);
-  CY_REQUIRE(OH >= 1 && OW >= 1 && OH < (1 << 20) && OW < (1 << 20), "cy_boxes_crop_resize_u8: output size %d x %d", OH, OW);
-  if (K == 0) return 0;
-  CY_REQUIRE(imgs && img_off && img_hw && box_img && box_xy, "cy_boxes_crop_resize_u8: null argument (images or boxes)");
-  CY_REQUIRE(n_images > 0 && imgs_bytes > 0, "cy_boxes_crop_resize_u8: %d images in %lld bytes", n_images, imgs_bytes);
-  const long long total = (long long)K * OH * OW;
-  CY_REQUIRE(cy_ceil_div(total, 256) < (1ll << 31), "cy_boxes_crop_resize_u8: %lld output pixels are too many for one launch", total);
-  boxes_crop_resize_u8_kernel<<<(unsigned)cy_ceil_div(total, 256), 256, 0, CY_S>>>(imgs, img_off, img_hw, n_images, imgs_bytes, count, box_img,
-                                                                                   box_xy, total, K, OH, OW, shift, scale, to_nchw, out,
-                                                                                   rect_out, err);
-  CY_LAUNCH_CHECK("cy_boxes_crop_resize_u8");
-  return 0;
+  const cyi_images_rgb src = {imgs, img_off, img_hw, imgs_bytes};
+  return boxes_crop_resize("cy_boxes_crop_resize_u8", src, imgs && img_off && img_hw, n_images, imgs_bytes, count, box_img, box_xy, K, OH, OW,
+                           shift, scale, to_nchw, out, rect_out, err, stream);
+}
+
+extern "C" int cy_boxes_crop_resize_nv12(const unsigned char* imgs, const long long* img_off, const int* img_geom, int n_images,
+                                         long long imgs_bytes, cy_yuv_coef_t coef, const int* count, const int* box_img,
+                                         const double* box_xy, int K, int OH, int OW, float shift, float scale, int to_nchw, float* out,
+                                         int* rect_out, int* err, void* stream) {
+  CY_REQUIRE(cyi_yuv_coef_ok(coef), "cy_boxes_crop_resize_nv12: " CYI_YUV_COEF_MSG, CYI_YUV_COEF_ARGS(coef));
+  const cyi_images_nv12 src = {imgs, img_off, img_geom, imgs_bytes, coef};
+  return boxes_crop_resize("cy_boxes_crop_resize_nv12", src, imgs && img_off && img_geom, n_images, imgs_bytes, count, box_img, box_xy, K, OH,
+                           OW, shift, scale, to_nchw, out, rect_out, err, stream);
 }
 
 extern "C" int cy_pack_detections(const float* scores, int C, const int* count, const int* box_img, const double* box_xy,

@@ -21,7 +21,7 @@ import gc
 import numpy as np
 import torch
 
-from . import ops
+from . import nv12, ops
 from ._lib import HipExtensionError, call, query
 from .tiles import TileSpec
 
@@ -176,16 +176,20 @@ class Detections(object):
 
 
 class _State(object):
-    """Every buffer of the pipeline for frames of one shape (n, H, W): nothing is allocated per call."""
+    """Every buffer of the pipeline for frames of one shape (n, H, W), or for n NV12 surfaces of one `nv12.Layout`: nothing is
+    allocated per call.  The pinned staging buffer belongs to frames that come from the host and is built when the first one does."""
 
-    def __init__(self, n, H, W, side, ci, K, has_cls, dev, tiles=None):
-        nbytes = n * H * W * 3
+    def __init__(self, n, H, W, side, ci, K, has_cls, dev, tiles=None, layout=None):
+        self.layout = layout
+        self.frame_bytes = H * W * 3 if layout is None else layout.nbytes
+        nbytes = n * self.frame_bytes
         self.n, self.H, self.W, self.nbytes = n, H, W, nbytes
-        self.staging = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-        self.staging_np = self.staging.numpy().reshape(n, H, W, 3)
+        self.staging, self.staging_np = None, None
         self.frames = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        self.off = (torch.arange(n, dtype=torch.int64) * (H * W * 3)).to(dev)
+        self.off = (torch.arange(n, dtype=torch.int64) * self.frame_bytes).to(dev)
         self.hw32 = torch.tensor([[H, W]] * n, dtype=torch.int32).to(dev)
+        # the image table of the two crop launches: (H, W) per packed RGB frame, (H, W, pitch, uv_off) per NV12 surface
+        self.img_geom = self.hw32 if layout is None else torch.tensor([layout.geom] * n, dtype=torch.int32).to(dev)
         self.hw64 = torch.tensor([[H, W]] * n, dtype=torch.int64).to(dev)
         # the whole-frame resize in front of the detector: frame i, rectangle (0, H, 0, W)
         self.frame_idx = torch.arange(n, dtype=torch.int32).to(dev)
@@ -212,6 +216,14 @@ class _State(object):
         self.cand = None        # with nms_iou: the candidate list in front of the suppression step (_Candidates, built on first use)
 
 
+    def stage(self):
+        """The pinned host buffer, one row of frame_bytes per frame."""
+        if self.staging is None:
+            self.staging = torch.empty(self.nbytes, dtype=torch.uint8).pin_memory()
+            self.staging_np = self.staging.numpy().reshape(self.n, self.frame_bytes)
+        return self.staging_np
+
+
 class _Candidates(object):
     """The decode kernel's whole output for one frame shape, cap = n g^2 n_boxes entries, and what `cy_nms_boxes` needs beside it."""
 
@@ -229,7 +241,8 @@ class _Candidates(object):
 
 class SignDetector(object):
     """det = SignDetector(dark_model, dark_params, class_model, class_params, max_boxes=16, conf_th=0.5, graph=False,
-                        nms_iou=None, nms_class_aware=False, per_frame=0, tracker=None)
+                        nms_iou=None, nms_class_aware=False, per_frame=0, tracker=None, tiles=None, frame_format='rgb',
+                        yuv_matrix='bt601')
     res = det.detect(frames)
 
     dark_model: a DarkNet on the device (dark_params: darknet_input, n_grid, n_classes, capsule_input); class_model: CapsuleNet, or
@@ -249,12 +262,27 @@ class SignDetector(object):
     batch, `cy_yolo_decode_tiles_conf` (border rule and shift into frame pixels, include/capsyolo_hip.h) into one candidate list of
     n T g^2 n_boxes entries, `cy_nms_boxes` per frame with room for T g^2 n_boxes boxes (at most cy_nms_max_per_image()).  Needs
     nms_iou: the overlaps show a sign to more than one window by construction.  Crops, classifier, record and tracker are as
-    without tiles, on the full frames.  None: the launches are exactly those of a detector without the argument."""
+    without tiles, on the full frames.  None: the launches are exactly those of a detector without the argument.
+    frame_format: 'rgb' (packed HWC uint8, as above) or 'nv12'.  An NV12 frame is a contiguous uint8 [H + H/2, W] array with even H, W
+    (the Y plane, then the rows of interleaved U, V pairs), or, with `detect(frames, layout=nv12.Layout(...))`, a 1-D / 2-D buffer of
+    layout.nbytes bytes: a decoder surface with a row pitch and a chroma offset of its own.  The frames are uploaded as they are, 1.5
+    bytes per pixel, and `cy_crop_resize_nv12` / `cy_boxes_crop_resize_nv12` convert in their tap fetch by the colour rule of
+    include/capsyolo_hip.h with the row yuv_matrix (a name of nv12.MATRICES, an nv12.YuvMatrix or six integers); the record is bit
+    for bit that of an 'rgb' detector on the frame converted by that rule.  yuv_matrix belongs to 'nv12'.
+    Device-resident frames (both formats): detect() also takes a contiguous torch.uint8 tensor on the detector's device, or a list of
+    them, of the shapes above.  They are copied device to device into the state's frame buffer on the current stream (a captured
+    graph keeps its addresses); no staging buffer, no host copy, no further synchronisation, and the tensor is not kept."""
 
     def __init__(self, dark_model, dark_params, class_model, class_params, max_boxes=16, conf_th=0.5, graph=False, nms_iou=None,
-                 nms_class_aware=False, per_frame=0, tracker=None, tiles=None):
+                 nms_class_aware=False, per_frame=0, tracker=None, tiles=None, frame_format='rgb', yuv_matrix='bt601'):
         if int(max_boxes) != max_boxes or max_boxes < 1:
             raise ValueError('max_boxes must be an integer >= 1, got %r' % (max_boxes,))
+        if frame_format not in ('rgb', 'nv12'):
+            raise ValueError("frame_format must be 'rgb' or 'nv12', got %r" % (frame_format,))
+        if frame_format == 'rgb' and not (isinstance(yuv_matrix, str) and yuv_matrix == 'bt601'):
+            raise ValueError("yuv_matrix belongs to frame_format='nv12': packed RGB frames are not converted")
+        self.frame_format, self.yuv = frame_format, nv12.coef(yuv_matrix)
+        self._coef = nv12.c_coef(self.yuv)
         if nms_iou is not None and not (0.0 <= float(nms_iou) <= 1.0):
             raise ValueError('nms_iou must be in [0, 1], got %r' % (nms_iou,))
         if int(per_frame) != per_frame or per_frame < 0:
@@ -312,11 +340,78 @@ class SignDetector(object):
                                  % (k, a.shape[0], a.shape[1], arrs[0].shape[0], arrs[0].shape[1]))
         return arrs
 
-    def _state(self, n, H, W):
-        key = (n, H, W)
+    def _sources(self, frames, layout=None):
+        """(device-resident?, the frames as a list of flat-able arrays or tensors, H, W, layout or None) of one detect() call."""
+        fmt = self.frame_format
+        if layout is not None:
+            if fmt != 'nv12':
+                raise ValueError("layout= describes an NV12 surface: the detector was built with frame_format='rgb'")
+            if not isinstance(layout, nv12.Layout):
+                raise ValueError('layout must be an nv12.Layout, got %r' % (type(layout).__name__,))
+        if isinstance(frames, (np.ndarray, torch.Tensor)):
+            if layout is not None:
+                one = int(np.prod(tuple(frames.shape))) == layout.nbytes and frames.ndim <= 2
+            else:
+                one = frames.ndim == (3 if fmt == 'rgb' else 2)
+            frames = [frames] if one else list(frames)
+        items = list(frames)
+        if not items:
+            raise ValueError('no frames')
+        on_dev = [isinstance(f, torch.Tensor) for f in items]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError('host arrays and device tensors mixed in one call: frame %d is a %s, frame 0 a %s'
+                             % (on_dev.index(not on_dev[0]), 'tensor' if not on_dev[0] else 'host array',
+                                'tensor' if on_dev[0] else 'host array'))
+        if on_dev[0]:
+            for k, t in enumerate(items):
+                if t.device != self.dev:
+                    raise ValueError('frame %d is a tensor on %s, the detector is on %s' % (k, t.device, self.dev))
+                if t.dtype != torch.uint8:
+                    raise ValueError('frame %d: expected a torch.uint8 tensor, got dtype %s' % (k, t.dtype))
+                if not t.is_contiguous():
+                    raise ValueError('frame %d is not contiguous: a frame is copied as one run of bytes' % k)
+        elif fmt == 'rgb':
+            items = self._frames(items)
+        else:
+            items = [np.asarray(f) for f in items]
+            for k, a in enumerate(items):
+                if a.dtype != np.uint8:
+                    raise ValueError('frame %d: expected a uint8 array, got %s %s' % (k, a.dtype, a.shape))
+                if not a.flags['C_CONTIGUOUS']:
+                    raise ValueError('frame %d is not contiguous: an NV12 frame is copied as one run of bytes' % k)
+        tight = None
+        for k, f in enumerate(items):
+            shape = tuple(f.shape)
+            if fmt == 'rgb':
+                if on_dev[0] and (len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1):    # (host frames: _frames did)
+                    raise ValueError('frame %d: expected a uint8 tensor [H, W, 3], got shape %s' % (k, shape))
+            elif layout is not None:
+                if len(shape) not in (1, 2) or int(np.prod(shape)) != layout.nbytes:
+                    raise ValueError('frame %d: %r has %d bytes, got a buffer of shape %s' % (k, layout, layout.nbytes, shape))
+            else:
+                try:
+                    tight = nv12.Layout.of(f) if k == 0 else tight
+                except ValueError as e:
+                    raise ValueError('frame %d: %s (or give layout=)' % (k, e))
+            if shape != tuple(items[0].shape):
+                raise ValueError('frame %d has shape %s, frame 0 has %s: one call takes frames of one size' % (k, shape, tuple(items[0].shape)))
+        if fmt == 'rgb':
+            H, W = items[0].shape[0:2]
+        else:
+            layout = tight if layout is None else layout
+            H, W = layout.H, layout.W
+        return on_dev[0], items, int(H), int(W), layout
+
+    def _state(self, n, H, W, layout=None):
+        key = (n, H, W) if layout is None else (n, layout)
         if key not in self.states:
-            self.states[key] = _State(n, H, W, self.side, self.ci, self.K, self.C > 0, self.dev, self.tiles)
+            self.states[key] = _State(n, H, W, self.side, self.ci, self.K, self.C > 0, self.dev, self.tiles, layout)
         return self.states[key]
+
+    def _images(self, st):
+        """The entry-point suffix and the leading arguments of the two crop launches: where the frames lie and what they are."""
+        head = (st.frames.data_ptr(), st.off.data_ptr(), st.img_geom.data_ptr(), st.n, st.nbytes)
+        return ('u8', head) if st.layout is None else ('nv12', head + (self._coef,))
 
     # ------------------------------------------------------------------------------------------------ the device steps
     def _device_steps(self, st):
@@ -326,12 +421,13 @@ class SignDetector(object):
         K = self.K
         w = st.words.data_ptr()
         st.words.zero_()
+        fmt, images = self._images(st)
         if self.tiles is None:
-            call('cy_crop_resize_u8', st.frames.data_ptr(), st.off.data_ptr(), st.hw32.data_ptr(), st.n, st.nbytes, st.frame_idx.data_ptr(),
-                 st.frame_rect.data_ptr(), st.n, self.side, self.side, 0.0, 1.0, 1, st.x_dark.data_ptr(), w + 8, stream)
+            call('cy_crop_resize_' + fmt, *images, st.frame_idx.data_ptr(), st.frame_rect.data_ptr(), st.n, self.side, self.side, 0.0, 1.0, 1,
+                 st.x_dark.data_ptr(), w + 8, stream)
         else:               # every window of every frame, each resized as an image of its own
-            call('cy_crop_resize_u8', st.frames.data_ptr(), st.off.data_ptr(), st.hw32.data_ptr(), st.n, st.nbytes, st.tile_idx.data_ptr(),
-                 st.tile_rect.data_ptr(), st.n_dark, self.side, self.side, 0.0, 1.0, 1, st.x_dark.data_ptr(), w + 8, stream)
+            call('cy_crop_resize_' + fmt, *images, st.tile_idx.data_ptr(), st.tile_rect.data_ptr(), st.n_dark, self.side, self.side, 0.0, 1.0, 1,
+                 st.x_dark.data_ptr(), w + 8, stream)
         y = self.dark(st.x_dark).data
         if y.dim() != 4 or y.shape[0] != st.n_dark or y.shape[1] != self.g or y.shape[2] != self.g:
             raise ValueError('the detector returned %s for %d frames on a %d x %d grid' % (tuple(y.shape), st.n_dark, self.g, self.g))
@@ -377,9 +473,8 @@ class SignDetector(object):
                  st.n, self.nms_iou, int(self.nms_class_aware), self.per_frame, per_image, c.keep.data_ptr(), K, st.box_img.data_ptr(),
                  st.box_xy.data_ptr(), st.box_conf.data_ptr(), st.box_cls.data_ptr() if self.C else None, c.src.data_ptr(), w, cw + 8,
                  cw + 4, stream)
-        call('cy_boxes_crop_resize_u8', st.frames.data_ptr(), st.off.data_ptr(), st.hw32.data_ptr(), st.n, st.nbytes, w,
-             st.box_img.data_ptr(), st.box_xy.data_ptr(), K, self.ci, self.ci, -128.0, 1.0 / 128.0, 1, st.crops.data_ptr(),
-             st.rect.data_ptr(), w + 4, stream)
+        call('cy_boxes_crop_resize_' + fmt, *images, w, st.box_img.data_ptr(), st.box_xy.data_ptr(), K, self.ci, self.ci, -128.0,
+             1.0 / 128.0, 1, st.crops.data_ptr(), st.rect.data_ptr(), w + 4, stream)
         scores = self.cls(st.crops).data.reshape(K, -1).to(dtype=torch.float32).contiguous()
         call('cy_pack_detections', scores.data_ptr(), int(scores.shape[1]), w, st.box_img.data_ptr(), st.box_xy.data_ptr(),
              st.box_conf.data_ptr(), st.rect.data_ptr(), w + 4, w + 8, K, st.record.data_ptr(), stream)
@@ -418,20 +513,26 @@ class SignDetector(object):
         st.graph, st.graph_key = graph, self._weights_key()
 
     # ------------------------------------------------------------------------------------------------ the call
-    def detect(self, frames):
-        arrs = self._frames(frames)
+    def detect(self, frames, layout=None):
+        on_dev, arrs, H, W, layout = self._sources(frames, layout)
         if self.tracker is not None and len(arrs) != 1:
             raise ValueError('a tracker follows one camera: one frame per call, got %d' % len(arrs))
-        H, W = arrs[0].shape[0:2]
-        st = self._state(len(arrs), H, W)
+        st = self._state(len(arrs), H, W, layout)
         if self.dark.training or self.cls.training:
             self.dark.eval()
             self.cls.eval()
         with torch.no_grad():
-            # the staging buffer is free: the previous call on this state waited for its record, which is behind its upload
-            for k, a in enumerate(arrs):
-                np.copyto(st.staging_np[k], a)
-            st.frames.copy_(st.staging, non_blocking=True)
+            if on_dev:
+                # device to device on the current stream, in front of the steps (or the replay) that read the state's buffer
+                fb = st.frame_bytes
+                for k, t in enumerate(arrs):
+                    st.frames[k * fb:(k + 1) * fb].copy_(t.reshape(-1), non_blocking=True)
+            else:
+                # the staging buffer is free: the previous call on this state waited for its record, which is behind its upload
+                rows = st.stage()
+                for k, a in enumerate(arrs):
+                    np.copyto(rows[k].reshape(a.shape), a)
+                st.frames.copy_(st.staging, non_blocking=True)
             if self.use_graph:
                 if st.graph is None or st.graph_key != self._weights_key():
                     self._capture(st)

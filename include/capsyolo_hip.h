@@ -623,6 +623,46 @@ typedef struct {
 int cy_pack_detections(const float* scores, int C, const int* count, const int* box_img, const double* box_xy,
                        const float* conf, const int* rect, const int* crop_err, const int* resize_err, int K, void* record,
                        void* stream);
+/* ------------------------------------------------------------------ NV12 frames (csrc/crop_pixel.h, predict.hip, serve.hip, nv12.hip)
+ * Cameras and video decode engines deliver NV12: a full-resolution Y plane and a half-resolution plane of interleaved (U, V) pairs,
+ * often with a row pitch wider than the frame.  The two crop + resize entry points above exist a second time for such images: the
+ * conversion to RGB happens in the tap fetch, so the frame never exists as RGB in memory.
+ *
+ * Layout.  imgs is one packed buffer of imgs_bytes bytes; image k has its Y plane at byte img_off[k] and
+ * img_geom[k] = (H, W, pitch, uv_off), int32 x 4.  The Y sample of pixel (y, x) is the byte at img_off + y pitch + x, its chroma pair
+ * (U, V) the two bytes at img_off + uv_off + (y >> 1) pitch + 2 (x >> 1).  Chroma is nearest-neighbour, one pair per 2 x 2 block, and
+ * the block is that of the pixel's coordinate in the FRAME, never in a crop.  H, W >= 1 of any parity: the chroma plane has
+ * ceil(H / 2) rows of ceil(W / 2) pairs.  An image is valid iff  pitch >= 2 ceil(W / 2),  uv_off >= H pitch,  img_off >= 0  and
+ * img_off + uv_off + ceil(H / 2) pitch <= imgs_bytes.  No alignment is assumed: the kernels load bytes.
+ *
+ * Colour rule.  With the coefficient row below, all in int32, >> the arithmetic shift (floor, not truncation: nearly half of all
+ * triples are negative before the clamp in some channel):
+ *     y = max(Y - y_off, 0) cy;   u = U - 128;   v = V - 128
+ *     R = clamp((y + cvr v         + 2^19) >> 20, 0, 255)
+ *     G = clamp((y - cug u - cvg v + 2^19) >> 20, 0, 255)
+ *     B = clamp((y + cub u         + 2^19) >> 20, 0, 255)
+ * A row is accepted iff 0 <= y_off <= 255 and 255 |cy| + 128 max(|cvr|, |cug| + |cvg|, |cub|) + 2^19 fits int32, so no value before
+ * the shift can overflow.  The named rows (capsyolo_amd/nv12.py, MATRICES) are 2^20 fixed point; bt601 = (16, 1220542, 1673527,
+ * 409993, 852492, 2116026), e.g. (Y, U, V) = (0, 0, 0) -> (0, 154, 0) and (81, 90, 240) -> (254, 0, 0).
+ * The bilinear interpolation then runs in fp32 on those rounded, clamped bytes with the arithmetic of the RGB entry points: every
+ * NV12 entry point is bit for bit the RGB entry point on the frame converted by this rule. */
+typedef struct { int y_off, cy, cvr, cug, cvg, cub; } cy_yuv_coef_t;
+/* cy_crop_resize_u8 on NV12 images: a box whose image index or rectangle is out of range, or whose image is not valid, is
+ * zero-filled and counted once in *err. */
+int cy_crop_resize_nv12(const unsigned char* imgs, const long long* img_off, const int* img_geom, int n_images, long long imgs_bytes,
+                        cy_yuv_coef_t coef, const int* box_img, const int* rect, int n, int OH, int OW, float shift, float scale,
+                        int to_nchw, float* out, int* err, void* stream);
+/* cy_boxes_crop_resize_u8 on NV12 images: the same rectangle rule and live / bad / dead slots (a slot of an image that is not valid
+ * is bad); K = 0 launches nothing. */
+int cy_boxes_crop_resize_nv12(const unsigned char* imgs, const long long* img_off, const int* img_geom, int n_images,
+                              long long imgs_bytes, cy_yuv_coef_t coef, const int* count, const int* box_img, const double* box_xy,
+                              int K, int OH, int OW, float shift, float scale, int to_nchw, float* out, int* rect_out, int* err,
+                              void* stream);
+/* Whole images to packed HWC RGB uint8, image k to out + out_off[k] (H W 3 bytes; the layout cy_draw_boxes_u8 and cy_crop_resize_u8
+ * read).  An image that is not valid, or with out_off[k] < 0 or out_off[k] + 3 H W > out_bytes, is left untouched and counted once
+ * in *err (caller-zeroed).  At most 65535 images.  For drawing, debugging and tests: the streaming detector does not use it. */
+int cy_nv12_to_rgb_u8(const unsigned char* imgs, const long long* img_off, const int* img_geom, int n_images, long long imgs_bytes,
+                      cy_yuv_coef_t coef, unsigned char* out, const long long* out_off, long long out_bytes, int* err, void* stream);
 /* ------------------------------------------------------------------ non-maximum suppression (csrc/nms.hip)
  * Greedy confidence-ordered suppression of a decoded box list, per image, with no host synchronisation: two launches whose shapes
  * depend on n_images alone (the list length is read from device memory), so the step captures into a HIP graph.  The reference has

@@ -50,6 +50,9 @@ formats; in train mode every augmented sample is one randomly drawn window with 
 ``--mode serve ... --track [--max_tracks N --track_iou X --max_misses M --min_hits H --track_decay D --no_motion]`` (new) follows the
 boxes from frame to frame on the device (`cy_track_update` behind serve.SignTracker): track ids, classes voted over a track's frames,
 hit counts; one line per frame goes to <model_dir>/tracks_output.txt, serve_output.txt stays as it is.
+``--mode serve ... --frame_format nv12 [--yuv_matrix NAME] [--device_frames]`` (new) hands the detector NV12 frames (encoded from the
+RGB frames with capsyolo_amd.nv12.from_rgb), converted inside the two crop launches; ``--device_frames`` (either format) uploads each
+frame before the timed call and passes a device tensor.
 ``--mode interpret --model capsule --restore last|best [--synthetic N] [--index I]`` is the reference's capsule_interpret.py:
 the 16 x 11 perturbation sweep of sample I's labelled capsule through the fused decoder kernel, written to <model_dir>/img/
 (see interpret()).
@@ -180,6 +183,13 @@ parser.add_argument('--min_hits', type=int, default=None, metavar='H', help='--t
 parser.add_argument('--track_decay', type=float, default=None, metavar='D',
                     help='--track: weight in [0, 1] of the older class scores in a track\'s class vote (default 0.9)')
 parser.add_argument('--no_motion', action='store_true', help='--track: match against a track\'s last box, not against the box moved on by its last step')
+parser.add_argument('--frame_format', default='rgb', choices=['rgb', 'nv12'],
+                    help='--mode serve: what the detector is handed.  nv12: every frame is encoded to NV12 first (capsyolo_amd.nv12.from_rgb, '
+                         'odd frames lose their last row / column) and read in place by the two crop launches')
+parser.add_argument('--yuv_matrix', default=None, metavar='NAME',
+                    help='--frame_format nv12: the coefficient row, one of bt601 (default), bt709, bt601_full, bt709_full')
+parser.add_argument('--device_frames', action='store_true',
+                    help='--mode serve: the frames are uploaded before the timed call and handed over as device tensors')
 parser.add_argument('--clip_norm', type=float, default=None, metavar='X',
                     help='clip the global gradient norm of every step to X (params.json key clip_norm): inside the project\'s Adam on the '
                          'device, without rewriting the gradients; torch.nn.utils.clip_grad_norm_ for the plain-torch cnn baseline')
@@ -771,6 +781,25 @@ def check_track(args):
         raise SystemExit('--track_decay %r: the weight must be in [0, 1]' % (args.track_decay,))
 
 
+def check_frames(args):
+    """The refusals of --frame_format, --yuv_matrix and --device_frames that need neither the data nor a device."""
+    given = [k for k, on in (('--frame_format', args.frame_format != 'rgb'), ('--yuv_matrix', args.yuv_matrix is not None),
+                             ('--device_frames', args.device_frames)) if on]
+    if given and args.mode != 'serve':
+        raise SystemExit('%s describes the frames of --mode serve' % given[0])
+    if args.yuv_matrix is not None:
+        if args.frame_format != 'nv12':
+            raise SystemExit('--yuv_matrix converts NV12 frames: give --frame_format nv12')
+        from capsyolo_amd import nv12
+        if args.yuv_matrix not in nv12.MATRICES:
+            raise SystemExit('--yuv_matrix %s: one of %s' % (args.yuv_matrix, ', '.join(sorted(nv12.MATRICES))))
+
+
+def even_frame(frame):
+    """The frame without its last row / column where the side is odd: what an NV12 frame of the [H + H/2, W] form can hold."""
+    return np.ascontiguousarray(frame[:frame.shape[0] - frame.shape[0] % 2, :frame.shape[1] - frame.shape[1] % 2])
+
+
 def check_serve(args):
     """The refusals of --mode serve that need neither the data nor a device."""
     if args.model not in ('darknet_d', 'darknet_r') or args.combine not in ('cnn', 'capsule'):
@@ -791,12 +820,17 @@ def serve(args, model, model_dir, data_dir, params):
     `--track`: a serve.SignTracker follows the boxes from frame to frame (`--synthetic N`: the N frames are synth.sign_sequence, one
     size, signs drifting over one background); per frame a second line `frame i: live L | confirmed: id/cls/hits ...` (the confirmed
     tracks in slot order) goes to <model_dir>/tracks_output.txt, and the totals gain tracks_born and tracks_confirmed (ids handed out,
-    ids that were confirmed at some frame).  serve_output.txt is what it is without the option."""
+    ids that were confirmed at some frame).  serve_output.txt is what it is without the option.
+    `--frame_format nv12 [--yuv_matrix NAME]`: every frame is encoded to NV12 on the host first (nv12.from_rgb; an odd frame loses its
+    last row / column, and the frame's line says the size used) and the detector reads it in place.  `--device_frames`: the frame, in
+    either format, is uploaded before the timed call and handed over as a device tensor."""
     import contextlib
     import time
+    from capsyolo_amd import nv12
     from capsyolo_amd.serve import SignDetector, SignTracker
     check_serve(args)
     check_track(args)
+    check_frames(args)
     if params.device != 'cuda':
         raise SystemExit('serve mode runs on hand-written gfx950 kernels only; no GPU is visible')
     class_model, class_model_dir, class_params = _combined_classifier(args, model_dir)
@@ -814,7 +848,8 @@ def serve(args, model, model_dir, data_dir, params):
                               max_misses=args.max_misses, min_hits=args.min_hits, decay=args.track_decay, motion=not args.no_motion)
     det = SignDetector(model, params, class_model, class_params, max_boxes=args.max_boxes, graph=args.graph, nms_iou=args.nms,
                        nms_class_aware=args.nms_class_aware, per_frame=args.per_frame, tracker=tracker,
-                       tiles=getattr(args, 'tile_spec', None))
+                       tiles=getattr(args, 'tile_spec', None), frame_format=args.frame_format,
+                       yuv_matrix=args.yuv_matrix or 'bt601')
     seen, ms = set(), []
     out = dict(frames=0, boxes=0, truncated=0, bad_boxes=0)
     confirmed_ids, tracks_born = set(), 0
@@ -823,8 +858,15 @@ def serve(args, model, model_dir, data_dir, params):
         tracks_file = files.enter_context(open(os.path.join(model_dir, 'tracks_output.txt'), 'w')) if args.track else None
         for i, frame in enumerate(frames):
             frame = np.asarray(frame)
+            given = frame
+            if args.frame_format == 'nv12':
+                frame = even_frame(frame)               # (the line below says the size used)
+                given = nv12.from_rgb(frame, args.yuv_matrix or 'bt601')
+            if args.device_frames:
+                given = torch.from_numpy(np.ascontiguousarray(given)).to(det.dev)
+                torch.cuda.synchronize(det.dev)
             t0 = time.perf_counter()
-            res = det.detect(frame)
+            res = det.detect(given)
             dt = (time.perf_counter() - t0) * 1e3
             if frame.shape in seen:
                 ms.append(dt)
@@ -989,6 +1031,7 @@ def main(argv=None):
     check_nms(args)
     check_tiles(args)
     check_track(args)
+    check_frames(args)
     data_dir, model_dir = config.data_dir[args.model], config.model_dir[args.model]
     if args.model_dir is not None:
         model_dir = args.model_dir

@@ -2,6 +2,7 @@
 """Latency of one camera frame through detector + classifier: the existing two-stage chain against serve.SignDetector.
 
     python tools/bench_serve.py [--reps 100] [--warmup 10] [--height 800] [--width 1360] [--max_boxes 16] [--nms IOU] [--track]
+                                [--frame_format nv12] [--device_frames]
 
 Default-initialised DarkNet (448 x 448 input, 14 x 14 grid, 2 boxes, no classes) and CapsuleNet (43 classes, 32 x 32 crops), one
 synthetic frame of the GTSDB size, a confidence threshold chosen between two of the detector's own confidences so that 1..max_boxes
@@ -17,7 +18,13 @@ nms_eager_ms / nms_graph_ms, with nms_boxes survivors of nms_candidates, next to
 process then measures the detector with a serve.SignTracker attached (32 tracks, `cy_track_update` behind the pack step) against the
 detector without one, the two ALTERNATING twice so that the spread between two measurements of the same code is seen next to the
 difference: track_eager / track_graph hold `plain_ms` and `track_ms` (two medians each), `plain_p50_p90` and `track_p50_p90` (the
-percentiles over all the calls of a kind) and the live tracks at the end."""
+percentiles over all the calls of a kind) and the live tracks at the end.
+With --frame_format nv12 the frame is encoded to NV12 (nv12.from_rgb, tight layout; an odd side loses its last row / column) and every
+SignDetector above is built with frame_format='nv12' and handed that frame, 1.5 bytes per pixel; the chain, and the choice of the
+threshold, run on the same frame converted to RGB by the colour rule (nv12.to_rgb_device), so all of them still see the same
+pixels.  With --device_frames the frame (either format) is uploaded once, before the timed calls, and every SignDetector call is
+handed the device tensor: no upload inside the call.  The chain always starts from the host frame.  The output gains frame_format,
+device_frames and frame_bytes (what one call moves to or on the device for its frame)."""
 import argparse
 import json
 import os
@@ -30,7 +37,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import capsyolo_amd  # noqa: E402,F401
-from capsyolo_amd import models, predict_fns, serve, synth  # noqa: E402
+from capsyolo_amd import models, nv12, predict_fns, serve, synth  # noqa: E402
 
 
 def _median_ms(fn, reps, warmup):
@@ -68,6 +75,8 @@ def main():
     ap.add_argument('--max_boxes', type=int, default=16)
     ap.add_argument('--nms', type=float, default=None, help='also measure SignDetector with non-maximum suppression at this IoU')
     ap.add_argument('--track', action='store_true', help='also measure SignDetector with a SignTracker attached, alternating with the plain one')
+    ap.add_argument('--frame_format', default='rgb', choices=['rgb', 'nv12'], help='what SignDetector is handed')
+    ap.add_argument('--device_frames', action='store_true', help='hand SignDetector a device tensor uploaded before the timed calls')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_serve needs a GPU')
@@ -81,6 +90,15 @@ def main():
     dark, caps = models.DarkNet(dp).cuda().eval(), models.CapsuleNet(cp).cuda().eval()
     side = max(a.height, a.width)
     frame = np.ascontiguousarray(synth.raw_images(1, seed=7, min_side=side, max_side=side)[0][:a.height, :a.width])
+
+    given, fmt = frame, dict(frame_format=a.frame_format)
+    if a.frame_format == 'nv12':
+        frame = np.ascontiguousarray(frame[:a.height - a.height % 2, :a.width - a.width % 2])
+        given = nv12.from_rgb(frame)
+        frame = nv12.to_rgb_device(torch.from_numpy(given).cuda().reshape(-1), nv12.Layout.of(given))[0].cpu().numpy()
+    if a.device_frames:
+        given = torch.from_numpy(given).cuda()
+        torch.cuda.synchronize()
 
     with torch.no_grad():
         y = dark(predict_fns.PackedImages([frame]).resize(448, to_nchw=True)).data
@@ -98,36 +116,37 @@ def main():
     if not 1 <= n_chain <= K:
         raise SystemExit('the threshold %.9g lets %d boxes through, wanted 1..%d' % (conf_th, n_chain, K))
     chain_ms, chain_min = _median_ms(chain, a.reps, a.warmup)
-    out = {'frame': [a.height, a.width], 'max_boxes': K, 'boxes': n_chain, 'reps': a.reps, 'chain_ms': chain_ms, 'chain_min_ms': chain_min}
+    out = {'frame': list(frame.shape[:2]), 'frame_format': a.frame_format, 'device_frames': a.device_frames,
+           'frame_bytes': int(given.numel() if a.device_frames else given.size), 'max_boxes': K, 'boxes': n_chain, 'reps': a.reps, 'chain_ms': chain_ms, 'chain_min_ms': chain_min}
     for key, graph in (('eager', False), ('graph', True)):
-        det = serve.SignDetector(dark, dp, caps, cp, max_boxes=K, conf_th=conf_th, graph=graph)
-        res = det.detect(frame)
+        det = serve.SignDetector(dark, dp, caps, cp, max_boxes=K, conf_th=conf_th, graph=graph, **fmt)
+        res = det.detect(given)
         if res.n != n_chain or res.bad['boxes']:
             raise SystemExit('SignDetector (graph=%s) kept %d boxes (%d bad), the chain %d' % (graph, res.n, res.bad['boxes'], n_chain))
-        out[key + '_ms'], out[key + '_min_ms'] = _median_ms(lambda: det.detect(frame), a.reps, a.warmup)
+        out[key + '_ms'], out[key + '_min_ms'] = _median_ms(lambda: det.detect(given), a.reps, a.warmup)
     if a.nms is not None:
         for key, graph in (('nms_eager', False), ('nms_graph', True)):
-            det = serve.SignDetector(dark, dp, caps, cp, max_boxes=K, conf_th=conf_th, graph=graph, nms_iou=a.nms)
-            res = det.detect(frame)
+            det = serve.SignDetector(dark, dp, caps, cp, max_boxes=K, conf_th=conf_th, graph=graph, nms_iou=a.nms, **fmt)
+            res = det.detect(given)
             if not 1 <= res.total <= n_chain or res.bad['boxes']:
                 raise SystemExit('SignDetector (nms, graph=%s) kept %d boxes (%d bad) of the chain\'s %d' % (graph, res.total, res.bad['boxes'], n_chain))
-            out[key + '_ms'], out[key + '_min_ms'] = _median_ms(lambda: det.detect(frame), a.reps, a.warmup)
+            out[key + '_ms'], out[key + '_min_ms'] = _median_ms(lambda: det.detect(given), a.reps, a.warmup)
         out.update(nms_iou=a.nms, nms_candidates=n_chain, nms_boxes=res.total)
     if a.track:
         for key, graph in (('track_eager', False), ('track_graph', True)):
             trk = serve.SignTracker(43, K)
-            dets = {'plain': serve.SignDetector(dark, dp, caps, cp, max_boxes=K, conf_th=conf_th, graph=graph),
-                    'track': serve.SignDetector(dark, dp, caps, cp, max_boxes=K, conf_th=conf_th, graph=graph, tracker=trk)}
-            res = dets['track'].detect(frame)
+            dets = {'plain': serve.SignDetector(dark, dp, caps, cp, max_boxes=K, conf_th=conf_th, graph=graph, **fmt),
+                    'track': serve.SignDetector(dark, dp, caps, cp, max_boxes=K, conf_th=conf_th, graph=graph, tracker=trk, **fmt)}
+            res = dets['track'].detect(given)
             if res.n != n_chain or res.bad['boxes'] or res.tracks.live != n_chain:
                 raise SystemExit('SignDetector (tracker, graph=%s) kept %d boxes, %d tracks, the chain %d' % (graph, res.n, res.tracks.live, n_chain))
             med, calls = {'plain': [], 'track': []}, {'plain': [], 'track': []}
             for _ in range(2):
                 for name in ('plain', 'track'):
-                    ms = _all_ms(lambda: dets[name].detect(frame), a.reps, a.warmup)
+                    ms = _all_ms(lambda: dets[name].detect(given), a.reps, a.warmup)
                     med[name].append(float(np.median(ms)))
                     calls[name].extend(ms)
-            live = dets['track'].detect(frame).tracks
+            live = dets['track'].detect(given).tracks
             if live.live != n_chain or (live.hits < 2 * (a.reps + a.warmup)).any():
                 raise SystemExit('the tracker lost its tracks: %d live, hits %s' % (live.live, live.hits.tolist()))
             out[key] = {'plain_ms': med['plain'], 'track_ms': med['track'], 'tracks': live.live,
